@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the fused HumanoidPingpong VecTask step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one VecTask.step() of every env this rank owns = one launch of the fused kernel
 (action->PD target, 2 physics substeps, reward, masked reset, observations).  Workload at N=1:
@@ -22,6 +22,13 @@ captured once into a HIP graph and replayed: the launches are the same kernels o
 stream in the same order, the graph only removes the per-launch submission from the loop
 (rocprofv3's kernel trace shows the per-kernel duration drop from 12.6 to 11.8 us).  K steps =
 K // 32 replays + one replay of a (K % 32)-step graph; --no-graph launches every step eagerly.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line (`ms_per_step` = wall time
+of the K steps / K; `roofline` = the algorithmic bytes over the timed steps).  --full adds what takes runs of its own: the
+per-kernel roofline regions (PMC traffic, VALU ceiling), the gather collectives' blocking cost, the CPU baselines and the
+secondary BASELINE configs (`configs`).  --dump-outputs DIR writes what the last timed step computed — the arrays a caller
+of the step receives (observations, rewards, resets, progress; for the rollout also the actions, their neglogp and the
+mu | value heads) — as DIR/<name>.npy (float32, or float64 for integer buffers), taken before anything else runs on the env.
 """
 import argparse
 import json
@@ -46,6 +53,7 @@ ALGO_BYTES = {"TT": 608, "TN": 608, "T3": 608, "T4": 1088, "TA": 2040}
 ALGO_BYTES_PER_ENV_STEP = ALGO_BYTES["TT"]
 PREWARM = 512
 ROOFLINE_WARM, ROOFLINE_LAUNCHES, ROOFLINE_REGIONS = 256, 480, 5   # multiples of HORIZON; fixed, whatever --steps is
+DUMP_BYTES_MAX = 64 << 20       # --dump-outputs: above this, a fixed seeded sample of the rows is written
 HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 
 
@@ -439,10 +447,41 @@ class Workload:
                 out.append(ev0.elapsed_time(ev1) * 1e3 / launches)
         return sorted(out)[len(out) // 2], out
 
+    def outputs(self, slot=None, t=None):
+        """name -> host array of what one step handed its caller: observations, rewards, resets and episode progress (in the gather
+        modes the horizon-major slices [slot, t] that step wrote rewards / resets (/ observations) into); for the rollout also the
+        drawn actions, their neglogp and the network's mu | value heads.  Integer buffers as float64 (exact), the rest float32."""
+        torch = self.torch
+        into = self.into if self.into is not None and slot is not None else None
+        out = {"obs": into["obs"][slot, t] if into is not None and into["obs"] is not None else self.obs_buf,
+               "rew": into["rew"][slot, t] if into is not None else self.env.rew_buf,
+               "reset": into["done"][slot, t] if into is not None else self.env.reset_buf,
+               "progress": self.env.progress_buf}
+        if self.rollout:
+            out.update(actions=self.action_buf, neglogp=self.neglogp, mu_value=self.net.head_out)
+        torch.cuda.synchronize(self.device)
+        return {k: v.detach().to("cpu", torch.float32 if v.is_floating_point() else torch.float64).numpy() for k, v in out.items()}
+
     def close(self):
         self.torch.cuda.synchronize(self.device)
         self.graphs.clear()
         self.env.close()
+
+
+def dump_outputs(arrays, out_dir):
+    """arrays (name -> array, all with one row per env row) -> out_dir/<name>.npy.  Above DUMP_BYTES_MAX in all, the same fixed sample of
+    rows (seed 0, sorted) is taken from every array and its row indices go to out_dir/rows.npy."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = len(next(iter(arrays.values())))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES_MAX:
+        per_row = -(-total // rows) + 8                     # + the float64 row index
+        keep = np.sort(np.random.default_rng(0).choice(rows, size=DUMP_BYTES_MAX // per_row, replace=False))
+        arrays = {k: a[keep] for k, a in arrays.items()}
+        arrays["rows"] = keep.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a))
 
 
 def hbm_roofline(variant, n, kernel_us, region_us=None, region=None, observed_kernel=None):
@@ -722,7 +761,7 @@ def main():
                          "rotating slots.  none (default): data-parallel learners, the reference's own mode — no data-path collective")
     ap.add_argument("--gather-pad", type=int, default=0, help="pad every shard to at least this many rows (exercises the ragged path with one rank)")
     ap.add_argument("--no-graph", action="store_true", help="launch every step eagerly instead of replaying a HIP graph of one horizon")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary BASELINE configs (`configs` in the JSON line); they run at N=1 only")
+    ap.add_argument("--no-configs", action="store_true", help="skip the secondary BASELINE configs (`configs` in the JSON line); they run with --full at N=1 only")
     ap.add_argument("--only-config", action="append", default=None,
                     help="run only this secondary config (name as in `configs`; repeatable) and print its row(s) alone — for profiling one at a time")
     ap.add_argument("--rehearse", action="store_true",
@@ -733,7 +772,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="create the process group and issue the per-horizon all-reduces (and gathers) even with ONE rank: the RCCL code path "
                          "(communicator init with device_id, asynchronous collectives beside the graph replays, barrier, max-reduce) on a one-GPU box")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: per-kernel roofline regions, the gather collectives' blocking cost, the CPU "
+                         "baselines (unless --no-cpu-baseline) and the secondary configs (unless --no-configs).  Off: only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy, float32 / float64")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("--steps must be at least 1 and --warmup at least 0")
     rollout = args.workload == "rollout"
     if args.variant is None:
         args.variant = "TA" if rollout else VARIANT
@@ -877,20 +923,26 @@ def main():
         t = torch.tensor([wall], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall = float(t.item())
-    # roofline: average duration of the step kernel alone — regions of back-to-back launches with nothing else on the stream,
-    # bracketed by HIP events on the stream the kernel is launched on (torch's current stream).  The region does not depend on
-    # --steps / --warmup: ROOFLINE_WARM launches to settle the clocks, then ROOFLINE_REGIONS regions of ROOFLINE_LAUNCHES
-    # launches each; the median region is reported (profiles/*_kernel_stats.csv is the same command under rocprofv3).
     if rg is not None:
         for sl in range(GSLOTS):
             rg.wait(sl)
     if obs_rg is not None:
         for sl in range(4):
             obs_rg.wait(sl)
-    kernel_us, region_us = w.kernel_region_us(ROOFLINE_WARM, ROOFLINE_LAUNCHES, ROOFLINE_REGIONS)
-    fwd_us = None
-    if rollout:
-        fwd_us, _ = w.kernel_region_us(32, 96, 5, fn=w.forward)
+    if args.dump_outputs and rank == 0:
+        # the last timed step: step K-1 of its horizon; in the gather modes its outputs went to slice t of the slot that horizon used
+        # (the slot index has already moved on when the K steps ended on a horizon boundary)
+        last_slot = (hz[0] - (1 if args.steps % HORIZON == 0 else 0)) % GSLOTS if gather else None
+        dump_outputs(w.outputs(last_slot, (args.steps - 1) % HORIZON), args.dump_outputs)
+    # roofline (--full): average duration of the step kernel alone — regions of back-to-back launches with nothing else on the stream,
+    # bracketed by HIP events on the stream the kernel is launched on (torch's current stream).  The region does not depend on
+    # --steps / --warmup: ROOFLINE_WARM launches to settle the clocks, then ROOFLINE_REGIONS regions of ROOFLINE_LAUNCHES
+    # launches each; the median region is reported (profiles/*_kernel_stats.csv is the same command under rocprofv3).
+    kernel_us = region_us = fwd_us = None
+    if args.full:
+        kernel_us, region_us = w.kernel_region_us(ROOFLINE_WARM, ROOFLINE_LAUNCHES, ROOFLINE_REGIONS)
+        if rollout:
+            fwd_us, _ = w.kernel_region_us(32, 96, 5, fn=w.forward)
     gather_info = None
     if gather:
         # the collectives' own cost, blocking, on an otherwise idle device: issue + completion of one horizon's (one step's) gathers
@@ -901,13 +953,14 @@ def main():
         per = {}
         for label, g_, tensors, dims in (("horizon_rew_done", rg, [w.into["rew"][0], w.into["done"][0]], [1, 1]),) + \
                 ((("step_obs", obs_rg, [w.into["obs"][0, 0]], [0]),) if per_step_gather else ()):
-            one_call(g_, tensors, dims)
-            tc = time.perf_counter()
-            for _ in range(20):
+            sent = sum(x.numel() * x.element_size() for x in tensors)
+            per[label] = {"bytes_sent_per_rank_per_call": sent, "bytes_received_per_rank_per_call": sent * rg.world}
+            if args.full:
                 one_call(g_, tensors, dims)
-            per[label] = {"us_per_call_blocking": (time.perf_counter() - tc) / 20 * 1e6,
-                          "bytes_sent_per_rank_per_call": sum(x.numel() * x.element_size() for x in tensors),
-                          "bytes_received_per_rank_per_call": sum(x.numel() * x.element_size() for x in tensors) * rg.world}
+                tc = time.perf_counter()
+                for _ in range(20):
+                    one_call(g_, tensors, dims)
+                per[label]["us_per_call_blocking"] = (time.perf_counter() - tc) / 20 * 1e6
         bytes_per_step = per["horizon_rew_done"]["bytes_sent_per_rank_per_call"] / HORIZON + (per["step_obs"]["bytes_sent_per_rank_per_call"] if per_step_gather else 0)
         gather_info = {"mode": args.gather, "backend": args.dist_backend if dist is not None else "none (one rank, local copy)", "ranks": rg.world,
                        "shard_rows": rg.counts, "padded_rows": rg.m, "ragged": rg.ragged, "bytes_per_step_per_rank": bytes_per_step,
@@ -922,18 +975,29 @@ def main():
 
     if rank == 0:
         total_env_steps = n * world * args.steps
+        timed_us = dev_ms * 1e3 / args.steps
         if not rollout:
-            roof = hbm_roofline(args.variant, n, kernel_us, region_us, f"{ROOFLINE_REGIONS} x {ROOFLINE_LAUNCHES} launches after {ROOFLINE_WARM} (median)",
-                                observed_kernel=w.kernel)
-            roof["timed_region_us_per_step"] = dev_ms * 1e3 / args.steps
+            if args.full:
+                roof = hbm_roofline(args.variant, n, kernel_us, region_us, f"{ROOFLINE_REGIONS} x {ROOFLINE_LAUNCHES} launches after {ROOFLINE_WARM} (median)",
+                                    observed_kernel=w.kernel)
+            else:       # a plain run: the algorithmic bytes over the timed steps themselves, no region of its own
+                achieved = ALGO_BYTES[args.variant] * n / (timed_us * 1e-6) / 1e9
+                roof = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "kernel": w.kernel,
+                        "algorithmic_bytes_per_launch": ALGO_BYTES[args.variant] * n,
+                        "region": f"the {args.steps} timed steps (per-kernel regions, PMC traffic and the VALU ceiling: --full)"}
+            roof["timed_region_us_per_step"] = timed_us
             metric = "env-steps/sec at N_envs=16384 (1/2/4/8 GPUs) + achieved HBM GB/s vs roofline"
             what = "random U(-1,1) actions, 2 physics substeps per step, fused step kernel"
         else:
-            tf = w.policy_flops / (fwd_us * 1e-6) / 1e12
-            roof = {"bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS, "traffic": None,
-                    "kernel": "mlp_layer_pp_kernel / mlp_layer_pp1_kernel (policy forward: 8 launches)", "avg_kernel_us": fwd_us,
-                    "flops_per_launch_sequence": w.policy_flops, "us_per_rollout_step_region": kernel_us, "region_us": region_us,
-                    "timed_region_us_per_step": dev_ms * 1e3 / args.steps}
+            if args.full:
+                tf = w.policy_flops / (fwd_us * 1e-6) / 1e12
+                roof = {"bound": "mfma", "achieved": tf, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": tf / MFMA_PEAK_TFLOPS, "traffic": None,
+                        "kernel": "mlp_layer_pp_kernel / mlp_layer_pp1_kernel (policy forward: 8 launches)", "avg_kernel_us": fwd_us,
+                        "flops_per_launch_sequence": w.policy_flops, "us_per_rollout_step_region": kernel_us, "region_us": region_us}
+            else:
+                roof = {"bound": "mfma", "flops_per_launch_sequence": w.policy_flops,
+                        "region": f"the {args.steps} timed steps (the policy forward's own regions and MFMA fraction: --full)"}
+            roof["timed_region_us_per_step"] = timed_us
             metric = "env-steps/sec incl. policy forward (BASELINE.json configs[4] per-GPU slice: 3-actor all-dof + native policy forward)"
             what = "rollout step = actor/critic MLP forward (MFMA; its normalised fp16 input written by the env step itself) + Normal(mu, sigma) draw + fused env step"
         out = {
@@ -952,7 +1016,7 @@ def main():
             "config": {"workload": f"humanoid_pingpong {WORKLOAD_NAMES[args.variant]}, num_envs={n} per GPU, {what}",
                        "variant": args.variant, "kind": args.workload,
                        "num_envs_per_gpu": n, "global_envs": n * world, "horizon_stats_every": HORIZON,
-                       "prewarm_launches": 0 if args.no_prewarm else PREWARM,
+                       "prewarm_launches": 0 if args.no_prewarm else PREWARM, "full": args.full,
                        "launch": "eager" if not use_graph else f"HIP graph of {HORIZON} steps, replayed",
                        "parallelism": f"env-shard x{world}, " + ("no data-path collective" if not gather else f"RCCL all-gather ({args.gather}) for a central learner")},
             "roofline": roof,
@@ -965,11 +1029,11 @@ def main():
     if dist is not None:
         dist.barrier()
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline_rollout(n, usable_cores(), seconds=10.0) if rollout else cpu_baseline(n, variant=args.variant)
             if args.variant == VARIANT and not rollout:
                 out["cpu_baseline_rows"] = cpu_baseline_rows(out["cpu_baseline"]["cores"])
-        if world == 1 and not args.no_configs and not rollout and args.variant == VARIANT and not gather and dist is None:
+        if args.full and world == 1 and not args.no_configs and not rollout and args.variant == VARIANT and not gather and dist is None:
             # The secondary rows run in a freshly started CHILD process (this script with --only-config), after the headline has been
             # measured and its env closed: a device fault, abort or hang in one of them (each touches other kernels) can then cost
             # only that child — it is killed by exact PID at its time limit — never the headline line printed below.

@@ -12,7 +12,6 @@ import pytest
 from helpers import GOLDEN_DIR
 from isaacgym_amd import cfgyaml, scene
 
-REF_CFG = "/root/reference/cfg"
 TASKS = ("HumanoidPingpongG1", "HumanoidPingpongTiltG1", "HumanoidPingpongTiltNoEarlyStopG1", "HumanoidPingpongTiltNESSparse27DOFG1")
 # What a user of the reference has to pass on the command line as well, because the yamls lack keys their own task classes read
 # (SURVEY.md §0.2): TT reads hitTableReward / nothitTablePenalty (TT:106-107; only the NoEarlyStop yaml has them, yaml:21,23); T3 reads
@@ -71,16 +70,41 @@ def test_interpolation_resolver():
         cfgyaml.resolve({"a": {"b": "${...nope}"}})
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CFG), reason="the reference checkout is not on this machine (the snapshot is used instead)")
-def test_reference_yamls_compose_to_the_committed_snapshot():
-    snap = snapshot()
-    for name in TASKS:
-        c = cfgyaml.compose(name, REF_CFG)
-        assert c["task"] == snap[name]["task"], name
-        assert c.get("train") == snap[name]["train"], name
-    tt = cfgyaml.compose("HumanoidPingpongTiltG1", REF_CFG, {"num_envs": 16384, "alpha_velocity_reward": 75})
+def test_compose_reads_the_task_and_train_yamls_and_applies_root_overrides(tmp_path):
+    """cfgyaml.compose on a cfg/ tree laid out as the reference's (task/<name>.yaml, train/<name>PPO.yaml): the task yaml's
+    ${resolve_default:...} interpolations take the root keys, the train yaml reaches into the task through the root, a task without a
+    train yaml composes without one.  (tests/golden/task_cfgs.json holds what compose yields on the reference's own yamls.)"""
+    (tmp_path / "task").mkdir()
+    (tmp_path / "train").mkdir()
+    (tmp_path / "task" / "Demo.yaml").write_text(
+        "name: Demo\n"
+        "physics_engine: ${..physics_engine}\n"
+        "env:\n"
+        "  numEnvs: ${resolve_default:4,${...num_envs}}\n"
+        "  alphaVelocityReward: ${resolve_default:50,${...alpha_velocity_reward}}\n"
+        "  episodeLength: 300\n"
+        "sim:\n"
+        "  use_gpu_pipeline: ${eq:${...pipeline},\"gpu\"}\n")
+    (tmp_path / "train" / "DemoPPO.yaml").write_text(
+        "params:\n"
+        "  network:\n"
+        "    mlp:\n"
+        "      units: [2048, 1536, 1024, 1024, 512, 512]\n"
+        "  config:\n"
+        "    name: ${resolve_default:Demo,${....experiment}}\n"
+        "    num_actors: ${....task.env.numEnvs}\n")
+    (tmp_path / "task" / "Bare.yaml").write_text("name: Bare\nenv:\n  numEnvs: ${resolve_default:8,${...num_envs}}\n")
+    c = cfgyaml.compose("Demo", str(tmp_path))
+    assert c["task"] == {"name": "Demo", "physics_engine": "physx", "env": {"numEnvs": 4, "alphaVelocityReward": 50, "episodeLength": 300},
+                         "sim": {"use_gpu_pipeline": True}}
+    assert c["train"]["params"]["config"] == {"name": "Demo", "num_actors": 4}
+    tt = cfgyaml.compose("Demo", str(tmp_path), {"num_envs": 16384, "alpha_velocity_reward": 75, "experiment": "run"})
     assert tt["task"]["env"]["numEnvs"] == 16384 and tt["task"]["env"]["alphaVelocityReward"] == 75
-    assert tt["train"]["params"]["config"]["num_actors"] == 16384 and tt["train"]["params"]["network"]["mlp"]["units"] == [2048, 1536, 1024, 1024, 512, 512]
+    assert tt["train"]["params"]["config"] == {"name": "run", "num_actors": 16384}
+    assert tt["train"]["params"]["network"]["mlp"]["units"] == [2048, 1536, 1024, 1024, 512, 512]
+    bare = cfgyaml.compose("Bare", str(tmp_path), {"num_envs": 64})
+    assert bare["task"]["env"]["numEnvs"] == 64 and "train" not in bare
+    assert "train" not in cfgyaml.compose("Demo", str(tmp_path), with_train=False)
 
 
 @pytest.mark.parametrize("name", [t for t in TASKS if "27DOF" not in t])

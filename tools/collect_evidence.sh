@@ -1,8 +1,9 @@
 #!/bin/bash
-# After `gpurun -- bash tools/gpu_evidence.sh`: copy the judged summaries from gpurun_out/ (scratch) into profiles/ under a tag.
+# After `bash tools/gpu_evidence.sh` on the GPU machine: copy the judged summaries from $OUT/ (scratch) into profiles/ under a tag.
 #   bash tools/collect_evidence.sh r02_d
 set -e
-tag=$1; go=gpurun_out; out=profiles
+export OUT="${OUT:-out}"      # results directory (relative to the repository root)
+tag=$1; go=$OUT; out=profiles
 python tools/collect_profiles.py $tag
 cp $go/bench_TA.json $out/${tag}_TA_bench.json
 cp "$(ls -t $go/prof_TA/*/*kernel_stats.csv | head -1)" $out/${tag}_TA_kernel_stats.csv

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Copies the evidence of the last tools/gpu_check.sh + tools/gpu_pmc.sh runs from gpurun_out/ into profiles/ under a tag:
+"""Copies the evidence of the last tools/gpu_check.sh + tools/gpu_pmc.sh runs from $OUT (default out/) into profiles/ under a tag:
 
     python tools/collect_profiles.py r01_e [kernel-name-substring]
 
@@ -15,8 +15,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 key = sys.argv[2] if len(sys.argv) > 2 else "step_kernel"
-out = os.environ.get("PROFILES_OUT", os.path.join(ROOT, "profiles"))     # on the GPU box: a directory under gpurun_out/ (the raw counter csvs are then deleted there)
-go = os.path.join(ROOT, "gpurun_out")
+out = os.environ.get("PROFILES_OUT", os.path.join(ROOT, "profiles"))     # or a directory under $OUT (the raw counter csvs are then deleted there)
+go = os.path.join(ROOT, os.environ.get("OUT", "out"))
 os.makedirs(out, exist_ok=True)
 
 shutil.copy(os.path.join(go, "bench.json"), os.path.join(out, f"{tag}_bench.json"))

@@ -11,7 +11,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from isaacgym_amd import _lib  # noqa: E402
-lib = os.path.join(ROOT, "gpurun_out", "libppenv_ppstamp.so")
+lib = os.path.join(ROOT, os.environ.get("OUT", "out"), "libppenv_ppstamp.so")
 os.makedirs(os.path.dirname(lib), exist_ok=True)
 exp = os.environ.get("PP_EXP", "0")      # timing experiments, see ppenv_policy.hip
 subprocess.run(["hipcc"] + _lib.HIPCC_FLAGS + ["-DPPM_STAMP=1", "-DPP_EXP=" + exp, "-o", lib] + _lib.SOURCES, check=True)

@@ -1,19 +1,21 @@
 #!/bin/bash
 # Round 3 check on the GPU box (via gpurun): GPU parity tests, smoke, the bench line with every single-GPU config, kernel trace of the headline.
 set -o pipefail
-mkdir -p gpurun_out
+export OUT="${OUT:-out}"      # results directory (relative to the repository root)
+mkdir -p $OUT
 export TMPDIR=/tmp
-echo "== pytest -m gpu" | tee gpurun_out/progress.log
-timeout -k 10 1000 python -m pytest tests -m gpu -x -q -p no:cacheprovider > gpurun_out/pytest_gpu.log 2>&1
-rc=$?; tail -40 gpurun_out/pytest_gpu.log; echo "pytest rc=$rc" | tee -a gpurun_out/progress.log
+echo "== pytest -m gpu" | tee $OUT/progress.log
+timeout -k 10 1000 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $OUT/pytest_gpu.log 2>&1
+rc=$?; tail -40 $OUT/pytest_gpu.log; echo "pytest rc=$rc" | tee -a $OUT/progress.log
 [ $rc -ne 0 ] && exit $rc
-echo "== smoke" | tee -a gpurun_out/progress.log
-timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee gpurun_out/smoke.log || exit 1
-echo "== bench" | tee -a gpurun_out/progress.log
-timeout -k 10 600 python bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -20 gpurun_out/bench.err; exit 1; }
+echo "== smoke" | tee -a $OUT/progress.log
+timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tee $OUT/smoke.log || exit 1
+echo "== bench" | tee -a $OUT/progress.log
+timeout -k 10 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
 python - <<'PY'
+import os
 import json
-d = json.load(open("gpurun_out/bench.json"))
+d = json.load(open(os.environ["OUT"] + "/bench.json"))
 print("headline %.3f G env-steps/s, kernel %.2f us, frac %.4f" % (d["value"] / 1e9, d["roofline"]["avg_kernel_us"], d["roofline"]["frac"]))
 for r in d.get("configs", []):
     k = r.get("avg_kernel_us", r.get("us_per_rollout_step", r["roofline"]["avg_kernel_us"]))

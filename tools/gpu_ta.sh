@@ -1,9 +1,10 @@
 #!/bin/bash
 # GPU iteration for the 27-DoF variant: its tests, then a timing of TAEnv.step at BASELINE config 5's per-GPU size
 set -o pipefail
-mkdir -p gpurun_out
-timeout -k 10 600 python -m pytest tests/test_ta_physics.py tests/test_ta_golden.py -m gpu -x -q -p no:cacheprovider > gpurun_out/pytest_ta.log 2>&1
-rc=$?; tail -5 gpurun_out/pytest_ta.log; [ $rc -ne 0 ] && { tail -60 gpurun_out/pytest_ta.log; exit $rc; }
+export OUT="${OUT:-out}"      # results directory (relative to the repository root)
+mkdir -p $OUT
+timeout -k 10 600 python -m pytest tests/test_ta_physics.py tests/test_ta_golden.py -m gpu -x -q -p no:cacheprovider > $OUT/pytest_ta.log 2>&1
+rc=$?; tail -5 $OUT/pytest_ta.log; [ $rc -ne 0 ] && { tail -60 $OUT/pytest_ta.log; exit $rc; }
 timeout -k 10 300 python - <<'PY'
 import time, torch
 from isaacgym_amd.tensor_api import TAEnv
