@@ -80,9 +80,11 @@ def test_fused_step_matches_oracle_single_steps(torch_cuda, oracle_lib, variant,
         env.set_state(st)
         o.step(actions)
         env.step(torch.from_numpy(actions).cuda())
-        keep = ~probe.sensitive(st, actions, o)      # envs sitting on a switch of the physics spec this step are skipped
+        keep = ~probe.sensitive(st, actions, o)      # envs sitting on a switch of the physics spec this step: checked by check_excluded
         log.add(keep)
-        v, o_all = mask_envs(DevView(env), keep), o
+        g = DevView(env)
+        probe.check_excluded(log, t, st, actions, o, g, keep, oa, ra)
+        v, o_all = mask_envs(g, keep), o
         o = mask_envs(o_all, keep)
         np.testing.assert_array_equal(v.reset_buf, o.reset_buf, err_msg=f"reset step {t}")
         np.testing.assert_array_equal(v.progress_buf, o.progress_buf, err_msg=f"progress step {t}")
@@ -614,7 +616,9 @@ def test_randomized_step_matches_oracle(torch_cuda, oracle_lib, monkeypatch, sch
         env.step(torch.from_numpy(actions).cuda())
         keep = ~probe.sensitive(st, actions, o)
         log.add(keep)
-        v, om = mask_envs(DevView(env), keep), mask_envs(o, keep)
+        g = DevView(env)
+        probe.check_excluded(log, t, st, actions, o, g, keep, oa, ra)
+        v, om = mask_envs(g, keep), mask_envs(o, keep)
         np.testing.assert_array_equal(v.reset_buf, om.reset_buf, err_msg=f"reset step {t}")
         np.testing.assert_array_equal(v.flags, om.flags, err_msg=f"flags step {t}")
         assert_state_close(v, om, f"step {t}")

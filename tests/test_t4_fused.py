@@ -146,9 +146,11 @@ def test_t4_fused_step_matches_oracle_single_steps(torch_cuda, oracle_lib, monke
         env.set_state(st)
         o.step(actions)
         env.step(torch.from_numpy(actions).cuda())
-        keep = ~probe.sensitive(st, actions, o)      # envs sitting on a switch of the physics spec this step are skipped
+        keep = ~probe.sensitive(st, actions, o)      # envs sitting on a switch of the physics spec this step: checked by check_excluded
         log.add(keep)
-        _check_step(mask_envs(DevView(env), keep, 2), mask_envs(o, keep, 2), t, oa, ra)
+        g = DevView(env)
+        probe.check_excluded(log, t, st, actions, o, g, keep, oa, ra)
+        _check_step(mask_envs(g, keep, 2), mask_envs(o, keep, 2), t, oa, ra)
         resets += int(o.reset_buf.sum())
     assert resets > 50 or n >= 4096       # (the 40 steps of the full-size case end before the first episode does)
     log.close()
@@ -286,7 +288,9 @@ def test_t4_fused_step_with_randomisation_matches_oracle(torch_cuda, oracle_lib)
             moved = float((ref.dof_vel - env.dof_vel).abs().max())
         keep = ~probe.sensitive(st, actions, o)
         log.add(keep)
-        _check_step(mask_envs(DevView(env), keep, 2), mask_envs(o, keep, 2), t, oa, ra)
+        g = DevView(env)
+        probe.check_excluded(log, t, st, actions, o, g, keep, oa, ra)
+        _check_step(mask_envs(g, keep, 2), mask_envs(o, keep, 2), t, oa, ra)
         resets += int(o.reset_buf.sum())
     log.close()
     assert resets > 30 and moved > 1e-2

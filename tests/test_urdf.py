@@ -335,7 +335,8 @@ def test_second_27dof_asset_differs_and_runs_on_the_kernel_arithmetic(oracle_lib
 
     import shim_binding as sb
     import urdf_assets
-    from test_ta_physics import ball_switch_probe, check_step, initial_tensors
+    from helpers import ExclusionLog
+    from test_ta_physics import ball_switch_probe, check_step, initial_tensors, rows_simulate, ta_sim_check_excluded
     m, base = urdf_assets.second_27dof_model(), scene.build_ta_model()
     assert abs(sum(m.link[i].mass for i in range(28)) / sum(base.link[i].mass for i in range(28)) - 1.3) < 1e-6
     assert abs(m.link[4].origin_xyz[2] - (base.link[4].origin_xyz[2] - 0.03)) < 1e-7          # left knee 3 cm lower
@@ -345,6 +346,7 @@ def test_second_27dof_asset_differs_and_runs_on_the_kernel_arithmetic(oracle_lib
     root, dof = initial_tensors(n, seed=5)
     rng = np.random.default_rng(6)
     moved = 0.0
+    log = ExclusionLog("host shim (kernel arithmetic) 27-dof step of the second asset vs oracle", bound=None)
     for t in range(60):
         if t % 4 == 0:
             act = rng.uniform(-1.1, 1.1, (n, 27)).astype(np.float32)
@@ -355,7 +357,10 @@ def test_second_27dof_asset_differs_and_runs_on_the_kernel_arithmetic(oracle_lib
         oracle_lib.ta_simulate(cfg, base, act, r3, d3, threads=8)
         moved = max(moved, float(np.abs(d3[..., 1] - dof[..., 1]).max()))
         hit = ball_switch_probe(oracle_lib, cfg, m, act, root0, dof0, root, seed=t)
+        log.add(~hit)
+        ta_sim_check_excluded(log, t, hit, (r2, d2, rb2, frc2), (root, dof, rb, frc), rows_simulate(oracle_lib, cfg, m, act, root0, dof0), seed=5)
         check_step((r2[~hit], d2[~hit], rb2[~hit], frc2[~hit]), (root[~hit], dof[~hit], rb[~hit], frc[~hit]), f"second asset, step {t}")
+    log.close()
     assert moved > 0.5          # rad/s: the placeholder model would have stepped elsewhere — the tables did reach the arithmetic
 
 
@@ -396,6 +401,7 @@ def test_second_arm_asset_through_modelgen_into_the_kernel_arithmetic(oracle_lib
         moved = max(moved, float(np.abs(o_stock.dof_vel - o.dof_vel).max()))
         keep = ~probe.sensitive(st, actions, o)
         log.add(keep)
+        probe.check_excluded(log, t, st, actions, o, s, keep, oa, ra)
         sm, om = mask_envs(s, keep), mask_envs(o, keep)
         np.testing.assert_array_equal(sm.reset_buf, om.reset_buf)
         np.testing.assert_array_equal(sm.flags, om.flags)
@@ -492,6 +498,7 @@ def test_table_and_ball_from_urdf_reach_the_kernel_arithmetic(oracle_lib, tmp_pa
         moved = max(moved, float(np.abs(o_stock.ball[:3, same_reset] - o.ball[:3, same_reset]).max()) if same_reset.any() else 0.0)     # ball is SoA [13][N]
         keep = ~probe.sensitive(st, actions, o)
         log.add(keep)
+        probe.check_excluded(log, t, st, actions, o, s, keep, oa, ra)
         sm, om = mask_envs(s, keep), mask_envs(o, keep)
         np.testing.assert_array_equal(sm.reset_buf, om.reset_buf)
         np.testing.assert_array_equal(sm.flags, om.flags)
@@ -515,7 +522,7 @@ def test_gpu_27dof_kernels_follow_a_urdf_model_that_differs_from_the_placeholder
     from helpers import ExclusionLog
     from isaacgym_amd import _lib
     from isaacgym_amd.tensor_api import TASim
-    from test_ta_physics import ball_switch_probe, check_step, initial_tensors
+    from test_ta_physics import ball_switch_probe, check_step, initial_tensors, rows_simulate, ta_sim_check_excluded
     if mapping == "lane":
         monkeypatch.setenv("PPENV_TA_KERNEL", "lane")
     else:
@@ -545,8 +552,9 @@ def test_gpu_27dof_kernels_follow_a_urdf_model_that_differs_from_the_placeholder
         moved = max(moved, float(np.abs(d3[..., 1] - dof[..., 1]).max()))
         keep = ~ball_switch_probe(oracle_lib, cfg, m, act, root0, dof0, root, seed=300 + t)
         log.add(keep)
-        got = (root_d.cpu().numpy()[keep], dof_d.cpu().numpy()[keep], rb_d.cpu().numpy()[keep], frc_d.cpu().numpy()[keep])
-        check_step(got, (root[keep], dof[keep], rb[keep], frc[keep]), f"second asset on the GPU, step {t}")
+        g = (root_d.cpu().numpy(), dof_d.cpu().numpy(), rb_d.cpu().numpy(), frc_d.cpu().numpy())
+        ta_sim_check_excluded(log, t, ~keep, g, (root, dof, rb, frc), rows_simulate(oracle_lib, cfg, m, act, root0, dof0), seed=6)
+        check_step(tuple(x[keep] for x in g), (root[keep], dof[keep], rb[keep], frc[keep]), f"second asset on the GPU, step {t}")
     log.close()
     assert moved > 0.5
     sim.close()
@@ -588,6 +596,7 @@ def test_gpu_7dof_step_on_a_library_built_for_the_second_arm_asset(oracle_lib):
         keep = ~probe.sensitive(st, a, o)
         log.add(keep)
         g = DevView(env)
+        probe.check_excluded(log, t, st, a, o, g, keep, oa, ra)
         gm, om = mask_envs(g, keep), mask_envs(o, keep)
         np.testing.assert_array_equal(gm.reset_buf, om.reset_buf)
         np.testing.assert_array_equal(gm.flags, om.flags)
@@ -635,7 +644,9 @@ def test_gpu_fused_step_on_a_table_and_ball_from_urdf(oracle_lib, variant):
             moved = max(moved, float(np.abs(o_stock.ball[:3, same_reset] - o.ball[:3, same_reset]).max()))
         keep = ~probe.sensitive(st, a, o)
         log.add(keep)
-        gm, om = mask_envs(DevView(env), keep, A), mask_envs(o, keep, A)
+        g = DevView(env)
+        probe.check_excluded(log, t, st, a, o, g, keep, oa, ra)
+        gm, om = mask_envs(g, keep, A), mask_envs(o, keep, A)
         np.testing.assert_array_equal(gm.reset_buf, om.reset_buf)
         np.testing.assert_array_equal(gm.flags, om.flags)
         assert_state_close(gm, om, f"urdf table + ball on the GPU, step {t}")
