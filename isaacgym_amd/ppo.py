@@ -1,0 +1,576 @@
+"""A PPO trainer on the native env and network: rl_games' `a2c_continuous` as the reference configures it
+(cfg/train/HumanoidPingpongTiltG1PPO.yaml), with the minibatch tail on the device (C ABI: include/ppenv_ppo.h).
+
+One epoch (`PPOTrainer.train_epoch`):
+
+    rollout      RolloutCollector: horizon x (native forward + action draw + fused env step), bootstrap value, GAE
+    per epoch    value de-normalisation before GAE, old_neglogp on the stored actions, value statistics, advantage normalisation
+    minibatch    forward (input statistics update) -> ppenv_ppo_loss_grad -> NativeMLPLearner.backward(d_head)
+                 -> ppenv_ppo_grad_sumsq -> ppenv_ppo_adam_step -> sync_weights
+
+There is no host synchronisation inside an epoch: the loss scale, the step count and every statistic stay on the device.
+
+Semantics.  The loss terms are restated from rl_games' published a2c_continuous / common_losses (rl_games is absent offline: parity
+unpinned, the same status as tools/ppo_epoch_bench.py): the clipped surrogate, the clipped value loss, the soft bound loss at +-1.1, and
+loss = mean(a) + 0.5 critic_coef mean(c) - entropy_coef entropy + bounds_loss_coef mean(b).  The gradient-norm clip is
+clip_grad_norm_'s, the optimizer torch.optim.Adam's, the loss scale torch GradScaler's (init 65536, x0.5 and a skipped step on a
+non-finite gradient, x2 after 2000 clean steps).
+
+Deviations from rl_games:
+  - rl_games stores the unclamped action draw; the collector stores the CLAMPED actions the env consumed.  The ratio is evaluated on the
+    clamped actions, and old_neglogp is re-evaluated on them under the rollout's mu / sigma once per epoch (as tools/ppo_epoch_bench.py
+    does), so that the ratio starts at 1.
+  - `value_bootstrap` is a no-op here: `time_outs` is identically false for these tasks (vec_task.py, step), so there is nothing to add
+    to the rewards.
+  - The minibatches are the contiguous row ranges of the horizon-major buffers, in order.
+
+Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
+"""
+import argparse
+import ctypes as C
+import dataclasses
+import math
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import _lib
+from .collector import RolloutCollector, gae
+from .policy import UNITS, NativeActorCritic, RunningMeanStd
+
+HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+STATS = ("loss", "a_loss", "c_loss", "b_loss", "entropy", "kl", "clip_frac")     # ppenv_ppo_loss_grad's stats[] (include/ppenv_ppo.h)
+SOFT_BOUND = 1.1                          # rl_games a2c_continuous.bound_loss
+OPT_PARTS = 512                           # workgroups of the optimizer launches: two per CU
+
+
+class PPOLossArgs(C.Structure):
+    """ctypes mirror of ppenv_ppo_loss_args (include/ppenv_ppo.h)."""
+    _fields_ = [("m", C.c_int32), ("a", C.c_int32),
+                ("mu", C.c_void_p), ("ld_mu", C.c_int32), ("value", C.c_void_p), ("ld_value", C.c_int32),
+                ("actions", C.c_void_p), ("ld_actions", C.c_int32), ("old_mu", C.c_void_p), ("ld_old_mu", C.c_int32),
+                ("old_sigma", C.c_void_p), ("old_neglogp", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p),
+                ("returns", C.c_void_p), ("logstd", C.c_void_p),
+                ("e_clip", C.c_float), ("critic_coef", C.c_float), ("bounds_loss_coef", C.c_float), ("soft_bound", C.c_float),
+                ("entropy_coef", C.c_float), ("clip_value", C.c_int32), ("scale", C.c_void_p),
+                ("d_head", C.c_void_p), ("ld_d_head", C.c_int32), ("d_logstd", C.c_void_p), ("stats", C.c_void_p), ("partial", C.c_void_p)]
+
+
+class PPOTensor(C.Structure):
+    """ctypes mirror of ppenv_ppo_tensor."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("ld_p", C.c_int32), ("ld_g", C.c_int32)]
+
+
+class PPOAdam(C.Structure):
+    """ctypes mirror of ppenv_ppo_adam."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("max_norm", C.c_float), ("truncate", C.c_int32),
+                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32)]
+
+
+def _lib_ppo():
+    L = _lib.lib()
+    if getattr(L, "_ppo_bound", False):
+        return L
+    vp, i32 = C.c_void_p, C.c_int32
+    L.ppenv_ppo_loss_partial_floats.restype = C.c_size_t
+    L.ppenv_ppo_loss_partial_floats.argtypes = [i32]
+    L.ppenv_ppo_loss_grad.argtypes = [C.POINTER(PPOLossArgs), vp]
+    L.ppenv_ppo_grad_sumsq.argtypes = [vp, i32, vp, i32, vp]
+    L.ppenv_ppo_adam_step.argtypes = [vp, i32, vp, i32, PPOAdam, vp, vp, vp, vp]
+    L._ppo_bound = True
+    return L
+
+
+def _stream(t):
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+# ---- configuration ----------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class PPOConfig:
+    """rl_games' a2c_continuous settings.  Defaults: cfg/train/HumanoidPingpongTiltG1PPO.yaml (the 27-dof task has no train yaml of its own and
+    uses them too), except minibatch_size, whose yaml value 4 (line 74, commented "# 8192") is not a usable minibatch."""
+    gamma: float = 0.99                   # yaml:58
+    tau: float = 0.95                     # yaml:59
+    learning_rate: float = 2e-5           # yaml:60
+    lr_schedule: str = "constant"         # yaml:61
+    e_clip: float = 0.2                   # yaml:72
+    critic_coef: float = 4.0              # yaml:76
+    clip_value: bool = True               # yaml:77
+    bounds_loss_coef: float = 1e-4        # yaml:79
+    entropy_coef: float = 0.0             # yaml:69
+    grad_norm: float = 10.0               # yaml:68
+    truncate_grads: bool = True           # yaml:70
+    normalize_advantage: bool = True      # yaml:57
+    normalize_input: bool = True          # yaml:51
+    normalize_value: bool = True          # yaml:52
+    mixed_precision: bool = True          # yaml:50
+    horizon_length: int = 32              # yaml:73
+    mini_epochs: int = 5                  # yaml:75
+    minibatch_size: int = 8192            # yaml:74 "# 8192"
+    reward_scale: float = 0.01            # yaml:55-56 reward_shaper.scale_value
+    sigma_init: float = -2.0              # yaml:20-22 sigma_init const_initializer val
+    fixed_sigma: bool = True              # yaml:23
+    max_epochs: int = 200000              # yaml:64
+    save_frequency: int = 1500            # yaml:66
+    units: tuple = tuple(UNITS)           # yaml:29
+    # GradScaler (torch.cuda.amp defaults; rl_games builds it with enabled=mixed_precision)
+    init_scale: float = 65536.0
+    growth_interval: int = 2000
+
+    KEYS = {                              # PPOConfig field <- params.config key
+        "gamma": "gamma", "tau": "tau", "learning_rate": "learning_rate", "lr_schedule": "lr_schedule", "e_clip": "e_clip",
+        "critic_coef": "critic_coef", "clip_value": "clip_value", "bounds_loss_coef": "bounds_loss_coef", "entropy_coef": "entropy_coef",
+        "grad_norm": "grad_norm", "truncate_grads": "truncate_grads", "normalize_advantage": "normalize_advantage",
+        "normalize_input": "normalize_input", "normalize_value": "normalize_value", "mixed_precision": "mixed_precision",
+        "horizon_length": "horizon_length", "mini_epochs": "mini_epochs", "minibatch_size": "minibatch_size", "max_epochs": "max_epochs",
+        "save_frequency": "save_frequency"}
+
+    @classmethod
+    def from_train_cfg(cls, train, task_cfg=None, **overrides):
+        """cfg["train"] (a composed train yaml: `params.config`, `params.network`) -> PPOConfig; `overrides` (field=value) win over the yaml.
+        task_cfg: cfg["task"], checked for `randomize`.  Raises ValueError naming the key for what the trainer does not run."""
+        params = train["params"] if "params" in train else train
+        c, net = params.get("config", {}), params.get("network", {})
+        kw = {}
+        for field, key in cls.KEYS.items():
+            if key in c and c[key] not in ("", None):
+                kw[field] = c[key]
+        if "reward_shaper" in c and "scale_value" in c["reward_shaper"]:
+            kw["reward_scale"] = c["reward_shaper"]["scale_value"]
+        cont = net.get("space", {}).get("continuous", {})
+        if "sigma_init" in cont and "val" in cont["sigma_init"]:
+            kw["sigma_init"] = cont["sigma_init"]["val"]
+        if "fixed_sigma" in cont:
+            kw["fixed_sigma"] = cont["fixed_sigma"]
+        if "units" in net.get("mlp", {}):
+            kw["units"] = tuple(net["mlp"]["units"])
+        kw.update(overrides)
+        types = {f.name: f.type for f in dataclasses.fields(cls)}
+        for k, v in list(kw.items()):
+            t = types[k]
+            if t in (float, "float"):
+                kw[k] = float(v)              # learning_rate: 2e-5 arrives as the string "2e-5" from YAML 1.1
+            elif t in (int, "int"):
+                kw[k] = int(v)
+            elif t in (bool, "bool"):
+                kw[k] = v if isinstance(v, bool) else str(v).lower() == "true"
+        cfg = cls(**kw)
+        cfg.check()
+        if task_cfg is not None and bool(task_cfg.get("task", {}).get("randomize", False)):
+            raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation "
+                             "hook; set task.randomize=False")
+        return cfg
+
+    def check(self, rows=None):
+        """The settings this trainer runs; rows: actor rows of the env (num_envs x num_agents), for the minibatch's divisibility."""
+        mb = self.minibatch_size
+        hint = "; use minibatch_size=8192 (the yaml's comment) or 32768"
+        if mb <= 0 or mb % 64:
+            raise ValueError(f"minibatch_size: {mb} is not a positive multiple of 64 (the learner's row tile){hint}")
+        if rows is not None and (self.horizon_length * rows) % mb:
+            raise ValueError(f"minibatch_size: {mb} does not divide horizon_length x rows = {self.horizon_length} x {rows}{hint}")
+        if self.lr_schedule != "constant":
+            raise ValueError(f"lr_schedule: {self.lr_schedule!r} is not supported (only 'constant', every reference yaml's value)")
+        if not self.fixed_sigma:
+            raise ValueError("fixed_sigma: False is not supported (the network has a learnable, observation-independent log-std)")
+        if tuple(self.units) != tuple(UNITS):
+            raise ValueError(f"units: {list(self.units)} — the native network is built for {UNITS}")
+
+
+# ---- the loss gradient in fp64: what ppenv_ppo_loss_grad computes ------------------------------------------------------------------
+def loss_grad_reference(mu, value, actions, old_neglogp, old_mu, old_sigma, advantages, old_values, returns, logstd, e_clip=0.2, critic_coef=4.0,
+                        bounds_loss_coef=1e-4, entropy_coef=0.0, clip_value=True, scale=1.0, soft_bound=SOFT_BOUND):
+    """numpy fp64, per-row analytic gradient of rl_games' a2c_continuous loss (the kernel's formulas).  mu / actions / old_mu [M, A],
+    value / old_neglogp / advantages / old_values / returns [M], old_sigma / logstd [A] -> dict(d_mu [M, A], d_value [M], d_logstd [A]: all
+    d(loss x scale); and the unscaled statistics named in STATS)."""
+    f = lambda x: np.asarray(x, dtype=np.float64)
+    mu, value, act, onlp, omu, osg = f(mu), f(value).reshape(-1), f(actions), f(old_neglogp), f(old_mu), f(old_sigma)
+    adv, ov, ret, ls = f(advantages), f(old_values), f(returns), f(logstd)
+    m, a = mu.shape
+    sg = np.exp(ls)
+    z = (act - mu) / sg
+    nlp = 0.5 * (z * z).sum(1) + HALF_LOG_2PI * a + ls.sum()
+    ratio = np.exp(onlp - nlp)
+    s1, s2 = -adv * ratio, -adv * np.clip(ratio, 1.0 - e_clip, 1.0 + e_clip)
+    a_loss = np.maximum(s1, s2)
+    g = np.where(s1 >= s2, adv * ratio, 0.0)                 # d a_loss / d nlp
+    cu = (value - ret) ** 2
+    if clip_value:
+        d = value - ov
+        vc = ov + np.clip(d, -e_clip, e_clip)
+        cc = (vc - ret) ** 2
+        c_loss = np.maximum(cu, cc)
+        dv = np.where(cu >= cc, 2.0 * (value - ret), np.where(np.abs(d) <= e_clip, 2.0 * (vc - ret), 0.0))
+    else:
+        c_loss, dv = cu, 2.0 * (value - ret)
+    hi, lo = np.maximum(mu - soft_bound, 0.0), np.minimum(mu + soft_bound, 0.0)
+    b_loss = (hi * hi + lo * lo).sum(1)
+    entropy = (0.5 + HALF_LOG_2PI + ls).sum()
+    kl = (np.log(osg / sg + 1e-5) + (sg * sg + (omu - mu) ** 2) / (2.0 * (osg * osg + 1e-5)) - 0.5).sum(1)
+    gs = scale / m
+    d_mu = gs * (-g[:, None] * z / sg + bounds_loss_coef * (2.0 * hi + 2.0 * lo))
+    d_value = gs * 0.5 * critic_coef * dv
+    d_logstd = gs * (g[:, None] * (1.0 - z * z)).sum(0) - scale * entropy_coef
+    loss = a_loss.mean() + 0.5 * critic_coef * c_loss.mean() - entropy_coef * entropy + bounds_loss_coef * b_loss.mean()
+    return dict(d_mu=d_mu, d_value=d_value, d_logstd=d_logstd, loss=loss, a_loss=a_loss.mean(), c_loss=c_loss.mean(), b_loss=b_loss.mean(),
+                entropy=entropy, kl=kl.mean(), clip_frac=(np.abs(ratio - 1.0) > e_clip).mean())
+
+
+# ---- the device kernels on torch tensors ------------------------------------------------------------------------------------------
+class LossGrad:
+    """ppenv_ppo_loss_grad for minibatches of up to `max_rows` rows: `d_head` [rows, A + 1] (what NativeMLPLearner.backward takes),
+    `d_logstd` [A] (the caller's buffer when given), and one row of STATS per call into the caller's `stats` row."""
+
+    def __init__(self, num_actions, max_rows, device, cfg, d_logstd=None):
+        self.a, self.cfg = int(num_actions), cfg
+        assert 0 < self.a <= 32, "one lane per row holds the row's actions: at most 32"
+        dev = torch.device(device)
+        self.d_head = torch.zeros((max_rows, self.a + 1), dtype=torch.float32, device=dev)
+        self.d_logstd = torch.zeros(self.a, dtype=torch.float32, device=dev) if d_logstd is None else d_logstd     # the optimizer's gradient buffer
+        self.partial = torch.zeros(int(_lib_ppo().ppenv_ppo_loss_partial_floats(max_rows)), dtype=torch.float32, device=dev)
+
+    def __call__(self, mu, value, actions, old_mu, old_sigma, old_neglogp, advantages, old_values, returns, logstd, scale, stats):
+        """mu / actions / old_mu [M, >= A] fp32 with unit column stride (any row stride); value [M, 1] (any row stride); old_sigma / logstd [A];
+        old_neglogp / advantages / old_values / returns [M] contiguous; scale: a device fp32 scalar; stats: fp32 [8] -> d_head[:M]."""
+        m, c = mu.shape[0], self.cfg
+        for t in (mu, value, actions, old_mu):
+            assert t.dtype == torch.float32 and t.stride(1) == 1 and t.shape[0] == m
+        for t in (old_neglogp, advantages, old_values, returns, old_sigma, logstd, scale, stats):
+            assert t.dtype == torch.float32 and t.is_contiguous()
+        assert m <= self.d_head.shape[0] and old_neglogp.numel() == advantages.numel() == old_values.numel() == returns.numel() == m
+        p = PPOLossArgs(m, self.a, mu.data_ptr(), mu.stride(0), value.data_ptr(), value.stride(0), actions.data_ptr(), actions.stride(0),
+                        old_mu.data_ptr(), old_mu.stride(0), old_sigma.data_ptr(), old_neglogp.data_ptr(), advantages.data_ptr(),
+                        old_values.data_ptr(), returns.data_ptr(), logstd.data_ptr(), c.e_clip, c.critic_coef, c.bounds_loss_coef, SOFT_BOUND,
+                        c.entropy_coef, int(c.clip_value), scale.data_ptr(), self.d_head.data_ptr(), self.d_head.stride(0),
+                        self.d_logstd.data_ptr(), stats.data_ptr(), self.partial.data_ptr())
+        _lib.check(_lib_ppo().ppenv_ppo_loss_grad(C.byref(p), _stream(mu)))
+        return self.d_head[:m]
+
+
+def _matrix(t):
+    """(rows, cols, row stride) of a tensor whose rows are evenly strided and whose last dimension is contiguous."""
+    if t.dim() == 1:
+        assert t.stride(0) == 1
+        return 1, t.shape[0], t.shape[0]
+    assert t.stride(-1) == 1
+    for d in range(t.dim() - 2):
+        assert t.stride(d) == t.shape[d + 1] * t.stride(d + 1), "rows must be evenly strided"
+    return int(np.prod(t.shape[:-1])), t.shape[-1], t.stride(-2)
+
+
+class DeviceAdam:
+    """clip_grad_norm_ + torch.optim.Adam + GradScaler on the device, over `params` / `grads` as they are (any evenly strided rows).
+    Two launches per step (ppenv_ppo_grad_sumsq, ppenv_ppo_adam_step).  `scale` is the device scalar the loss gradient multiplies by;
+    the scaler state (include/ppenv_ppo.h ppenv_ppo_scaler) is double-buffered in `state` [2, 8] int32: the step reads row `cur`, writes
+    row 1 - cur, and `cur` flips on the host (the host never reads the state)."""
+
+    def __init__(self, params, grads, lr, max_norm=10.0, truncate=True, init_scale=65536.0, growth_interval=2000, dynamic=True,
+                 betas=(0.9, 0.999), eps=1e-8, parts=OPT_PARTS):
+        assert len(params) == len(grads) and 0 < len(params) <= 64
+        self.params, self.grads = list(params), list(grads)
+        dev = self.device = self.params[0].device
+        self.exp_avg = [torch.zeros(p.shape, dtype=torch.float32, device=dev) for p in self.params]
+        self.exp_avg_sq = [torch.zeros(p.shape, dtype=torch.float32, device=dev) for p in self.params]
+        items = []
+        for p, g, m, v in zip(self.params, self.grads, self.exp_avg, self.exp_avg_sq):
+            assert p.dtype == g.dtype == torch.float32 and p.shape == g.shape and p.device == g.device == dev
+            rows, cols, ld_p = _matrix(p)
+            _, _, ld_g = _matrix(g)
+            items.append(PPOTensor(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), rows, cols, ld_p, ld_g))
+        arr = (PPOTensor * len(items))(*items)
+        self.table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)        # copied once
+        self.count, self.parts = len(items), int(parts)
+        self.slab = torch.zeros(self.parts, dtype=torch.float64, device=dev)
+        self.lr = torch.full((), float(lr), dtype=torch.float32, device=dev)
+        self.hp = PPOAdam(betas[0], betas[1], eps, max_norm, int(truncate), 2.0 if dynamic else 1.0, 0.5 if dynamic else 1.0, int(growth_interval))
+        self.state = torch.zeros((2, 8), dtype=torch.int32, device=dev)
+        self.state[:, 0:1].view(torch.float32).fill_(float(init_scale))
+        self.cur = 0
+
+    @property
+    def scale(self):
+        """The current loss scale: a device fp32 scalar view (the loss gradient reads it; changes in place after every step)."""
+        return self.state[self.cur, 0:1].view(torch.float32)
+
+    def fields(self):
+        """The current state as 0-dim device tensors: scale, growth_tracker, step, skipped, grad_norm."""
+        s = self.state[self.cur]
+        return dict(scale=s[0:1].view(torch.float32)[0], growth_tracker=s[1], step=s[2], skipped=s[3], grad_norm=s[4:5].view(torch.float32)[0])
+
+    def step(self):
+        L = _lib_ppo()
+        st = _stream(self.slab)
+        _lib.check(L.ppenv_ppo_grad_sumsq(self.table.data_ptr(), self.count, self.slab.data_ptr(), self.parts, st))
+        _lib.check(L.ppenv_ppo_adam_step(self.table.data_ptr(), self.count, self.slab.data_ptr(), self.parts, self.hp, self.lr.data_ptr(),
+                                         self.state[self.cur].data_ptr(), self.state[1 - self.cur].data_ptr(), st))
+        self.cur = 1 - self.cur
+
+    def state_dict(self):
+        return {"exp_avg": [t.detach().clone() for t in self.exp_avg], "exp_avg_sq": [t.detach().clone() for t in self.exp_avg_sq],
+                "scaler": self.state[self.cur].detach().clone(), "lr": self.lr.detach().clone()}
+
+    def load_state_dict(self, sd):
+        with torch.no_grad():
+            for dst, src in zip(self.exp_avg + self.exp_avg_sq, list(sd["exp_avg"]) + list(sd["exp_avg_sq"])):
+                dst.copy_(src)
+            self.cur = 0
+            self.state[0].copy_(sd["scaler"])
+            self.state[1].copy_(sd["scaler"])
+            self.lr.copy_(sd["lr"])
+
+
+# ---- the trainer ------------------------------------------------------------------------------------------------------------------
+def _denorm_(x, rms):
+    """rl_games RunningMeanStd(unnorm=True) in place: clamp(+-5), then x sqrt(var + eps) + mean."""
+    return x.clamp_(-5.0, 5.0).div_(rms.inv_std).add_(rms.mean)
+
+
+def _norm(x, rms):
+    return ((x - rms.mean) * rms.inv_std).clamp_(-5.0, 5.0)
+
+
+class PPOTrainer:
+    """rl_games' a2c_continuous on a task built by isaacgym_amd.make(...): its native handle (task.env: PPEnv or TAEnv) runs under
+    RolloutCollector; the network is NativeActorCritic (nn.Linear's default initialisation, rl_games' `initializer: default`) with a learnable
+    fixed log-std (its `sigma` parameter, initialised to sigma_init) and, with normalize_value, a value RunningMeanStd of width 1."""
+
+    def __init__(self, task, cfg=None, seed=0):
+        self.cfg = cfg = PPOConfig() if cfg is None else cfg
+        if getattr(task, "randomize", False):
+            raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
+        self.task, self.env = task, task.env
+        env = self.env
+        self.device = dev = torch.device(env.device)
+        self.rows = getattr(env, "num_rows", env.num_envs)                  # actor rows: num_envs x num_agents (T4: 2 actors per env)
+        cfg.check(self.rows)
+        self.num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
+        self.seed = int(seed)
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(self.seed)
+            actor, critic = self._mlp(self.num_actions), self._mlp(1)
+        self.net = NativeActorCritic(actor, critic, self.num_obs, dev, normalize_input=cfg.normalize_input)
+        self.learner = self.net.learner
+        with torch.no_grad():
+            self.net.sigma.fill_(cfg.sigma_init)
+        self.logstd = self.net.sigma.data                                   # a2c_network.sigma of the checkpoint
+        self.value_rms = RunningMeanStd(1, dev) if cfg.normalize_value else None
+        self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
+        H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
+        self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
+                                    sigma=torch.exp(self.logstd), seed=self.seed)
+        self.g_logstd = torch.zeros(self.num_actions, dtype=torch.float32, device=dev)
+        self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
+        self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
+                              max_norm=cfg.grad_norm, truncate=cfg.truncate_grads, init_scale=cfg.init_scale if cfg.mixed_precision else 1.0,
+                              growth_interval=cfg.growth_interval, dynamic=cfg.mixed_precision)
+        total = H * n
+        z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
+        self.old_nlp, self.adv, self.old_v, self.ret = z(total), z(total), z(total), z(total)
+        self.steps_per_epoch = cfg.mini_epochs * (total // mb)
+        self.stats = z(self.steps_per_epoch, 8)
+        self.ep_ret, self.ep_len = z(n), z(n)                              # the running episode of every row (unscaled rewards)
+        self.epoch, self.frame = 0, 0
+
+    def _mlp(self, n_out):
+        d, out = self.num_obs, []
+        for u in list(self.cfg.units) + [n_out]:
+            lin = torch.nn.Linear(d, u)
+            out.append((lin.weight.detach(), lin.bias.detach()))
+            d = u
+        return out
+
+    # -- the steps of an epoch --
+    def collect(self):
+        """One horizon; with normalize_value the value column is de-normalised and GAE re-run on it (the collector's own GAE ran on the
+        network's normalised output)."""
+        col = self.col
+        col.collect()
+        if self.value_rms is not None:
+            _denorm_(col.values, self.value_rms)
+            gae(col.rewards, col.values, col.dones, self.cfg.gamma, self.cfg.tau, self.cfg.reward_scale, col.advantages, col.returns)
+        return col
+
+    @torch.no_grad()
+    def prepare(self):
+        """old_neglogp on the stored actions, the value statistics (rl_games: updated with the values, then with the returns, each normalised
+        right after its update), advantages = returns - values normalised."""
+        col, H, n, A = self.col, self.cfg.horizon_length, self.rows, self.num_actions
+        total = H * n
+        act, mu = col.actions.reshape(total, A), col.head[:H].reshape(total, A + 1)[:, :A]
+        sg = col.sigma
+        self.old_nlp.copy_((((act - mu) / sg) ** 2).sum(1).mul_(0.5).add_(HALF_LOG_2PI * A).add_(torch.log(sg).sum()))
+        values, returns = col.values[:H].reshape(total, 1), col.returns.reshape(total, 1)
+        adv = col.advantages.reshape(total)
+        if self.cfg.normalize_advantage:
+            self.adv.copy_((adv - adv.mean()) / (adv.std() + 1e-8))
+        else:
+            self.adv.copy_(adv)
+        if self.value_rms is not None:
+            v = values.contiguous()
+            self.value_rms.update(v)
+            self.old_v.copy_(_norm(v, self.value_rms).view(-1))
+            r = returns.contiguous()
+            self.value_rms.update(r)
+            self.ret.copy_(_norm(r, self.value_rms).view(-1))
+        else:
+            self.old_v.copy_(values.view(-1))
+            self.ret.copy_(returns.view(-1))
+
+    def minibatch_step(self, lo, stats_row):
+        """One optimizer step on rows lo .. lo + minibatch_size of the prepared epoch."""
+        cfg, col, A = self.cfg, self.col, self.num_actions
+        mb, total = cfg.minibatch_size, cfg.horizon_length * self.rows
+        sl = slice(lo, lo + mb)
+        obs = col.obs[:cfg.horizon_length].reshape(total, self.num_obs)[sl]
+        mu, value = self.learner.forward(obs, update_stats=cfg.normalize_input)
+        old_mu = col.head[:cfg.horizon_length].reshape(total, A + 1)[sl, :A]
+        d_head = self.loss(mu, value, col.actions.reshape(total, A)[sl], old_mu, col.sigma, self.old_nlp[sl], self.adv[sl], self.old_v[sl],
+                           self.ret[sl], self.logstd, self.opt.scale, stats_row)
+        self.learner.backward(d_head)
+        self.opt.step()
+        self.learner.sync_weights()
+
+    def learn(self):
+        total, mb = self.cfg.horizon_length * self.rows, self.cfg.minibatch_size
+        k = 0
+        for _ in range(self.cfg.mini_epochs):
+            for lo in range(0, total, mb):
+                self.minibatch_step(lo, self.stats[k])
+                k += 1
+
+    @torch.no_grad()
+    def _episodes(self):
+        """Sum of returns, sum of lengths and count of the episodes that finished in the horizon (vectorised over the horizon)."""
+        col, H = self.col, self.cfg.horizon_length
+        r, d = col.rewards, col.dones.bool()
+        cs = r.cumsum(0)
+        t = torch.arange(H, device=self.device).view(H, 1)
+        last = torch.where(d, t, -1).cummax(0).values                          # last done at or before t
+        prev = torch.cat([torch.full_like(last[:1], -1), last[:-1]])           # ... strictly before t
+        fresh = prev < 0
+        ret = cs - torch.where(fresh, 0.0, cs.gather(0, prev.clamp(min=0))) + torch.where(fresh, self.ep_ret, 0.0)
+        length = (t - prev).float() + torch.where(fresh, self.ep_len, 0.0)
+        df = d.float()
+        out = torch.stack([(ret * df).sum(), (length * df).sum(), df.sum()])
+        end = last[-1]
+        self.ep_ret.copy_(torch.where(end < 0, self.ep_ret + cs[-1], cs[-1] - cs.gather(0, end.clamp(min=0).view(1, -1)).view(-1)))
+        self.ep_len.copy_(torch.where(end < 0, self.ep_len + H, (H - 1 - end).float()))
+        return out
+
+    def train_epoch(self):
+        """One epoch; no host synchronisation.  -> dict of 0-dim device tensors: the STATS averaged over the epoch's minibatch steps, the
+        loss scale, the steps skipped in this epoch, the last gradient norm, and the mean return / length of the episodes finished in the
+        horizon (unscaled rewards; 0 when none finished)."""
+        skipped0 = self.opt.fields()["skipped"].clone()
+        self.net.train()
+        self.collect()
+        ep = self._episodes()
+        self.prepare()
+        self.learn()
+        self.col.sigma.copy_(torch.exp(self.logstd))
+        self.col.next_horizon()
+        self.net.eval()
+        self.epoch += 1
+        self.frame += self.cfg.horizon_length * self.rows
+        mean = self.stats.mean(0)
+        f = self.opt.fields()
+        out = {k: mean[i] for i, k in enumerate(STATS)}
+        n = ep[2].clamp(min=1.0)
+        out.update(scale=f["scale"], skipped=f["skipped"] - skipped0, grad_norm=f["grad_norm"], episodes=ep[2], mean_return=ep[0] / n,
+                   mean_length=ep[1] / n)
+        return out
+
+    # -- checkpoints --
+    def state_dict(self):
+        model = self.net.to_rlgames_state_dict()
+        if self.value_rms is not None:
+            for k in ("running_mean", "running_var", "count"):
+                model[f"value_mean_std.{k}"] = getattr(self.value_rms, k).detach().clone()
+        # the fp32 statistics the kernels read, as the update kernel left them (RunningMeanStd.refresh derives them from the fp64 running
+        # statistics in torch and can differ in the last bit): a resumed run normalises exactly as the uninterrupted one
+        stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms))
+                 if rms is not None for k in ("mean", "inv_std")}
+        return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats}
+
+    def save(self, path):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save(self.state_dict(), path)
+
+    def load(self, path):
+        """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame."""
+        ck = torch.load(path, map_location=self.device, weights_only=True)
+        sd, lr = ck["model"], self.learner
+        from .policy import layers_from_rlgames_state_dict
+        actor, critic = layers_from_rlgames_state_dict(sd)
+        with torch.no_grad():
+            for i in range(len(lr.w32)):
+                for j, layers in enumerate((actor, critic)):
+                    lr.w32[i][j].copy_(layers[i][0])
+                    lr.b32[i][j].copy_(layers[i][1])
+            lr.mu_w.copy_(actor[-1][0]); lr.mu_b.copy_(actor[-1][1])
+            lr.value_w.copy_(critic[-1][0]); lr.value_b.copy_(critic[-1][1])
+            self.logstd.copy_(sd["a2c_network.sigma"])
+            for rms, prefix in ((lr.rms, "running_mean_std"), (self.value_rms, "value_mean_std")):
+                if rms is not None:
+                    for k in ("running_mean", "running_var", "count"):
+                        getattr(rms, k).copy_(sd[f"{prefix}.{k}"])
+                    rms.refresh()
+                    for k in ("mean", "inv_std"):
+                        if f"{prefix}.{k}" in ck.get("normalizer", {}):
+                            getattr(rms, k).copy_(ck["normalizer"][f"{prefix}.{k}"])
+            self.col.sigma.copy_(torch.exp(self.logstd))
+        lr.sync_weights()
+        self.opt.load_state_dict(ck["optimizer"])
+        self.epoch, self.frame = int(ck["epoch"]), int(ck["frame"])
+
+
+# ---- CLI --------------------------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.ppo", description="PPO (rl_games a2c_continuous) on the native env and network")
+    ap.add_argument("--task", default="HumanoidPingpongTiltNESSparse27DOFG1")
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--max-epochs", type=int, default=None)
+    ap.add_argument("--minibatch-size", type=int, default=None)
+    ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task and train yamls from")
+    ap.add_argument("--out", default=None, help="run directory (default runs/<task>)")
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--print-every", type=int, default=10)
+    args = ap.parse_args(argv)
+    import isaacgym_amd
+    over = {k: v for k, v in (("max_epochs", args.max_epochs), ("minibatch_size", args.minibatch_size)) if v is not None}
+    task_cfg = None
+    if args.cfg_dir:
+        from . import cfgyaml
+        composed = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})
+        task_cfg = composed["task"]
+        train = composed.get("train")        # the 27-dof task has no train yaml: the defaults (PPOConfig's, the Tilt yaml's)
+        cfg = PPOConfig.from_train_cfg(train, task_cfg=task_cfg, **over) if train else PPOConfig(**over)
+        cfg.check()
+    else:
+        cfg = PPOConfig(**over)
+        cfg.check()
+    task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
+    tr = PPOTrainer(task, cfg, seed=args.seed)
+    out = args.out or os.path.join("runs", args.task)
+    ckpt = os.path.join(out, "nn", f"{args.task}.pth")
+    t0 = time.perf_counter()
+    for e in range(cfg.max_epochs):
+        res = tr.train_epoch()
+        last = e + 1 == cfg.max_epochs
+        if (e + 1) % args.print_every == 0 or last:
+            vals = {k: float(v) for k, v in res.items()}           # the only host read
+            dt = time.perf_counter() - t0
+            print(f"epoch {tr.epoch} frames {tr.frame} fps {tr.frame / dt:.0f} loss {vals['loss']:.4g} a {vals['a_loss']:.4g} c {vals['c_loss']:.4g} "
+                  f"kl {vals['kl']:.3g} clip {vals['clip_frac']:.3f} scale {vals['scale']:.0f} skipped {vals['skipped']:.0f} "
+                  f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f}", flush=True)
+        if (e + 1) % cfg.save_frequency == 0 or last:
+            tr.save(ckpt)
+    print(f"saved {ckpt}")
+
+
+if __name__ == "__main__":
+    main()

@@ -7,10 +7,12 @@ critic_coef 4, clip_value, bounds_loss_coef 1e-4, grad_norm 10, normalize_advant
     learning    mini_epochs x (131072 / minibatch) minibatch steps: network forward + backward   --learner native: NativeActorCritic (MFMA kernels)
                                                                                                    --learner torch : nn.Sequential under autocast(fp16)
                 PPO losses (PyTorch elementwise on [M, 27] tensors), grad-norm clip, fused Adam   [PyTorch either way]
+                --learner ppo   : isaacgym_amd.ppo.PPOTrainer — the same network, the loss gradient, clip, Adam and loss scale as HIP kernels
+                                  (ppenv_ppo_loss_grad, ppenv_ppo_grad_sumsq, ppenv_ppo_adam_step), value normalisation as rl_games does it
 
 rl_games itself is not importable here (absent from the reference and the image); the loss terms are restated from its published a2c_continuous /
 common_losses (actor: clipped surrogate; critic: clipped value loss; bound loss on mu beyond +-1.1) — timing context, parity unpinned.
-Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch] [--num-envs 4096] [--minibatch 32768] [--epochs 3]"""
+Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo] [--num-envs 4096] [--minibatch 32768] [--epochs 3]"""
 import argparse
 import json
 import math
@@ -27,7 +29,7 @@ from isaacgym_amd.policy import NativeActorCritic, UNITS  # noqa: E402
 from isaacgym_amd.tensor_api import TAEnv  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--learner", default="native", choices=["native", "torch"])
+ap.add_argument("--learner", default="native", choices=["native", "torch", "ppo"])
 ap.add_argument("--num-envs", type=int, default=4096)
 ap.add_argument("--minibatch", type=int, default=32768)
 ap.add_argument("--epochs", type=int, default=3)
@@ -45,6 +47,47 @@ if use_dist:
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29571")
     dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
 n, H, A, NOBS = args.num_envs, 32, 27, 313
+
+
+def timed(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, out
+
+
+if args.learner == "ppo":          # the library trainer: the same epoch, its tail on the device
+    if use_dist:
+        raise SystemExit("--learner ppo runs one rank (multi-rank training is not part of PPOTrainer)")
+    import isaacgym_amd  # noqa: E402
+    from isaacgym_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
+    tr = PPOTrainer(isaacgym_amd.make(seed=0, task="HumanoidPingpongTiltNESSparse27DOFG1", num_envs=n, rl_device=str(dev), sim_device=str(dev)),
+                    PPOConfig(minibatch_size=args.minibatch), seed=0)
+    for _ in range(3):             # a run that has been training for a while (see below)
+        tr.col.collect().next_horizon()
+        for t in range(H):
+            tr.learner.rms.update(tr.col.obs[t])
+    tr.collect(); tr.prepare(); tr.learn(); tr.col.next_horizon()          # warm-up
+    roll_s = learn_s = 0.0
+    for _ in range(args.epochs):
+        dt, _ = timed(tr.collect)
+        roll_s += dt
+        dt, _ = timed(lambda: (tr.prepare(), tr.learn()))
+        learn_s += dt
+        tr.col.sigma.copy_(torch.exp(tr.logstd))
+        tr.col.next_horizon()
+    roll_ms, learn_ms = roll_s / args.epochs * 1e3, learn_s / args.epochs * 1e3
+    steps = tr.steps_per_epoch
+    f = tr.opt.fields()
+    print(json.dumps({
+        "what": "one PPO epoch of BASELINE config 5's per-GPU slice (27-dof task, rl_games a2c_continuous settings of cfg/train/HumanoidPingpongTiltG1PPO.yaml), context only",
+        "learner": "ppo", "num_envs": n, "horizon": H, "minibatch_rows": args.minibatch, "mini_epochs": tr.cfg.mini_epochs, "minibatch_steps_per_epoch": steps,
+        "ms_rollout_per_epoch": roll_ms, "ms_learning_per_epoch": learn_ms, "ms_per_minibatch_step": learn_ms / steps, "ranks": 1,
+        "env_steps_per_s_end_to_end": n * H / ((roll_ms + learn_ms) * 1e-3), "last_loss": float(tr.stats[-1, 0]),
+        "loss_scale": float(f["scale"]), "skipped_steps": int(f["skipped"]),
+        "finite": bool(all(torch.isfinite(p).all() for p in tr.learner.parameters()))}))
+    sys.exit(0)
 MINI_EPOCHS, E_CLIP, CRITIC_COEF, BOUNDS_COEF, GRAD_NORM, LR = 5, 0.2, 4.0, 1e-4, 10.0, 2e-5     # yaml:60-85
 torch.manual_seed(0)
 
@@ -137,14 +180,6 @@ def learn():
         native.learner.sync_weights()
         native._seen = native._versions()
     return steps, float(loss.detach())
-
-
-def timed(fn):
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    out = fn()
-    torch.cuda.synchronize()
-    return time.perf_counter() - t0, out
 
 
 native.eval()
