@@ -21,9 +21,6 @@
 using std::min;
 using std::max;
 
-#ifndef PP_ABLATE
-#define PP_ABLATE 0
-#endif
 #if defined(PP_STAMP)
 __device__ unsigned long long pp_stamp_buf[4096 * 32];
 #endif
@@ -35,8 +32,7 @@ namespace {
 
 constexpr int kBlock = 64;   // exactly one wave per workgroup: step_kernel relies on it (no barrier around its LDS tile)
 constexpr int kObsStride = PPENV_NUM_OBS + 1;   // +1 float: lanes write LDS rows bank-conflict-free
-constexpr int kMaxSplitSubsteps = 4;
-constexpr int kDefaultBallWaves = 1;            // ball waves per 64 envs (PPENV_BALL_WAVES overrides; see step_kernel_split's BW)            // the multi-wave step kernels keep one LDS hand-off slot per substep boundary
+constexpr int kMaxSplitSubsteps = 4;            // the multi-wave step kernels keep one LDS hand-off slot per substep boundary
 
 struct DevBuffers {
     float* obs;
@@ -52,22 +48,10 @@ struct DevBuffers {
     float* serve;
 };
 
-// State stores of the step kernels.  PP_STORE_MODE (profiling builds) selects how they leave the CU:
-// 0 plain, 1 non-temporal (default), 2 system-scope (write-through).  Measured at N = 16384 / 65536 (tools/gpu_storemode.sh):
-// 13.03 / 19.50 us, 12.92 / 19.18 us, 13.13 / 20.28 us — nothing in the launch reads the state again, so it may stream out.
-#ifndef PP_STORE_MODE
-#define PP_STORE_MODE 1
-#endif
+// State stores of the step kernels are non-temporal: nothing in the launch reads the state again, so it may stream out.
+// Measured at N = 16384 / 65536: plain 13.03 / 19.50 us, non-temporal 12.92 / 19.18 us, system scope 13.13 / 20.28 us.
 template <class V>
-__device__ __forceinline__ void st_state(V* p, V v) {
-#if PP_STORE_MODE == 1
-    __builtin_nontemporal_store(v, p);
-#elif PP_STORE_MODE == 2
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void st_state(V* p, V v) { __builtin_nontemporal_store(v, p); }
 
 // ------------------------------------------------------------- SoA state <-> registers
 template <int A>
@@ -182,11 +166,6 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const StepConsts K, DevBuf
         PP_STAMP_AT(1);
         BodyState bodies[NB];
         float pre_vx;
-#if PP_ABLATE >= 2   // profiling builds only (tools/gpu_ablate.sh): skip the physics
-        pre_vx = st.ball.v.x;
-#pragma unroll
-        for (int j = 0; j < NB; j++) { bodies[j].pos = mk(act[0], act[1], (float)j); bodies[j].lin = mk(act[2], act[3], act[4]); }
-#else
         EnvDR dr;
         const uint32_t gid = (uint32_t)(K.env_id_offset + i), ep0 = st.episode;
         if (DR) {   // this env's entries of the randomisation tables (a NULL table = scale 1)
@@ -202,19 +181,12 @@ __global__ __launch_bounds__(kBlock) void step_kernel(const StepConsts K, DevBuf
             dr.key_progress = (uint32_t)st.progress;
         }
         simulate_env<T, 1, DR>(K, act, st, bodies, pre_vx, &dr, gid);
-#endif
         V3 ov = mk(0, 0, 0);
         if (serve_on) ov = mk(b.serve[i], b.serve[(size_t)n + i], b.serve[2 * (size_t)n + i]);
         LdsRowStore store{&s_obs[lane * kObsStride]};
         NoisyRowStore nstore{&s_obs[lane * kObsStride], dr.obs_sigma, K.seed, gid, ep0, dr.key_progress};
-#if PP_ABLATE >= 3   // skip reward / reset / observations as well: loads + stores only
-        rew = pre_vx; reset = 0;
-#pragma unroll
-        for (int k = 0; k < PPENV_NUM_OBS; k++) store(k, bodies[k % NB].pos.x);
-#else
         if (DR && drt.obs_sigma > 0.f) post_physics_env<1>(K, gid, st, bodies, pre_vx, serve_on ? &ov : nullptr, &rew, reset, &nstore);
         else post_physics_env<1>(K, gid, st, bodies, pre_vx, serve_on ? &ov : nullptr, &rew, reset, &store);
-#endif
         PP_STAMP_AT(9);
     }
     // One wave per workgroup: DS operations of a wave execute in order, so the tile written above is visible
@@ -332,35 +304,27 @@ struct MovingGeom {
 
 // A = humanoids per env, G = who sweeps the collision geometry.  <A=1, G=0>: two waves (arm, ball); the arm wave is the
 // critical path, so it stays in joint space and the ball wave runs the world-space FK sweep for the geometry itself.
-// <A=2, G=0>: the same with three waves, one per arm on its own base (K.site[arm]).  <A=2, G=1> (the 4-actor default): with
-// two humanoids to collide against the ball wave is the critical path (35k cycles against the arm waves' 21k), so each
-// arm wave's start-of-substep sweep is the world-space one and hands its geometry to the ball wave through two alternating
-// LDS slots; the ball wave is left with the contacts.  (Tried and dropped: separate geometry waves — five waves on four
-// SIMDs slow each other more than the hand-off saves.)
-// BW = ball waves per 64 envs (round 3).  What a ball wave pays per micro-step is the UNION of its lanes' contact branches (DESIGN.md §6:
-// 250-420 instructions where a ball in free flight needs 40, because with 64 envs in a wave some lane is near nearly every shape).  At
-// N = 16384 half of the chip's SIMDs have no wave at all, so the 64 envs of a workgroup can be dealt to BW ball waves of 64 / BW envs
-// each (the upper lanes idle): fewer lanes per wave = a smaller union = a shorter chain, on SIMDs that were empty anyway.  The arm wave
-// keeps all 64 envs (its instruction stream has no divergence to shrink).
+// <A=2, G=1> (the 4-actor kernel): three waves, one per arm on its own base (K.site[arm]); with two humanoids to collide against
+// the ball wave is the critical path (35k cycles against the arm waves' 21k), so each arm wave's start-of-substep sweep is the
+// world-space one and hands its geometry to the ball wave through two alternating LDS slots; the ball wave is left with the
+// contacts.  (Tried and dropped, DESIGN.md §5 / §6: <1, 1>, <2, 0>, and separate geometry waves — five waves on four SIMDs slow
+// each other more than the hand-off saves.)
+// BW = ball waves per 64 envs: always 1.  (Narrower ball waves, 2 or 4 per 64 envs, were measured in round 3 and removed: DESIGN.md §9.
+// The parameter stays so that the kernel's name, which profiles and bench.py key on, does not change; the ball wave's env offsets below
+// are written for BW waves because folding them away changes the generated code.)
 // DR (round 3): the domain-randomisation tables read by the wave that owns the quantity — drive gains and link masses, the
 // action noise and the body block's observation noise on the arm wave; restitution / friction scales and the rest of the row's noise on the
 // ball wave.  Same arithmetic as step_kernel<T, true> (the one-wave instantiation: 427 VGPRs + spills), on the fast schedule.
 template <class T, int A, int G, int BW = 1, bool DR = false>
 __global__ __launch_bounds__((A + BW) * kBlock) void step_kernel_split(const StepConsts K, DevBuffers b, const float* __restrict__ actions, int serve_on,
                                                                        uint32_t* status, int dbg_drop_handoff, const DRTables drt = DRTables{}) {
-    static_assert(BW == 1 || G == 0, "narrow ball waves: each sweeps its own geometry (the s_bflag slot protocol has one consumer)");
+    static_assert(BW == 1, "one ball wave per 64 envs");
     // (DR with two humanoids: both are instances of the yaml's one "humanoid" actor — an env's [7][N] table entries apply to both arms)
     constexpr int kGeo = MovingGeom<T>::count();
     // Who writes dof_pos / dof_vel / dof_force.  With one humanoid the arm wave is the critical path and would sit waiting
     // for the ball wave's reset decision just to pick between q and the initial pose: the ball wave, which has both, stores
-    // them instead.  With two humanoids the ball wave is the critical path and the arm waves keep the stores.
-#ifndef PP_BALL_STORES_DOFS
-#define PP_BALL_STORES_DOFS 1      // profiling builds: 0 = the arm wave stores the dof state of the one-humanoid variants too (it waits for the reset decision)
-#endif
-    constexpr bool kBallStoresDofs = A == 1 && PP_BALL_STORES_DOFS;
-    // With several ball waves each publishes s_flag_ball = 1 on its own and the arm wave's wait is satisfied by the FIRST of them: were the arm wave to
-    // read the reset decisions of all 64 envs after that wait (the PP_BALL_STORES_DOFS=0 diagnostic build), it would race with the slower ball waves.
-    static_assert(A != 1 || BW == 1 || kBallStoresDofs, "BW > 1 needs PP_BALL_STORES_DOFS: the arm wave must not read s_reset behind a flag any one ball wave sets");
+    // them instead (11.51 against 11.70 us).  With two humanoids the ball wave is the critical path and the arm waves keep the stores.
+    constexpr bool kBallStoresDofs = A == 1;
     __shared__ float s_geom[G ? 2 : 1][G ? A : 1][G ? kGeo : 1][G ? kBlock : 1];   // geometry of boundary s in slot s & 1
     __shared__ int s_gflag[A];                         // arm -> ball: boundaries whose geometry is in LDS
     __shared__ int s_bflag;                            // ball -> arm: substeps the ball has finished (slot reuse)
@@ -620,260 +584,6 @@ __global__ __launch_bounds__((A + BW) * kBlock) void step_kernel_split(const Ste
         store_task<A>(b, n, bi, st, rew, reset);
     }
     PP_STAMP_AT(24);
-}
-
-// ---- the single-humanoid step on FOUR waves per 64 envs (round 2; PPENV_STEP_KERNEL=quad) ---------------------------------------------
-//
-// step_kernel_split<T, 1, 0> is two co-critical serial chains: the arm wave (two substeps, then the final-state sweep, the
-// body block of the observation row and its flush) and the ball wave (per substep a kinematics sweep for the collision geometry, then
-// four micro-steps; then reward / reset / the rest of the row, its flush and the state stores).  Here two more waves — on the two SIMDs
-// the launch leaves idle — take what is not inherently on either chain:
-//   wave 2 (geometry): the ball wave's kinematics sweep, from the substep boundary the arm wave publishes, into an LDS slot; and, after
-//           the final sweep, a third of the observation row's body block and of the flush;
-//   wave 3 (auxiliary): the serve draw of a possible reset (a pure function of seed, env id, episode), then a third of the body block
-//           and of the flush.
-// Hand-offs during the substeps are one-way flags as in the two-wave kernel (the consumers wait anyway).  The tail is two workgroup
-// barriers, at which a waiting wave costs no issue slot: X — final sweep done (paddle position, raw body states, final dof state in
-// LDS; the ball wave's substeps done): the three helpers transform the bodies, the ball wave runs the task arithmetic; Y — the whole
-// observation tile is in LDS: waves 0, 2, 3 flush it, the ball wave stores the state.  Nothing reaches HBM before Y, so a hand-off
-// time-out (bounded wait, as elsewhere) simply marks the workgroup dead and nobody stores.
-template <class T>
-__global__ __launch_bounds__(4 * kBlock) void step_kernel_quad(const StepConsts K, DevBuffers b, const float* __restrict__ actions, int serve_on,
-                                                               uint32_t* status, int dbg_drop_handoff) {
-    constexpr int A = 1, kGeo = MovingGeom<T>::count(), kHelpFirst = 4;   // bodies 0 .. kHelpFirst-1: arm wave; then wave 2 and wave 3 split the rest
-    constexpr int kMid = kHelpFirst + (NB - kHelpFirst) / 2;
-    __shared__ float s_geom[2][kGeo][kBlock];          // geometry of boundary s in slot s & 1
-    __shared__ float s_obs[kBlock * kObsStride];
-    __shared__ float s_q[kMaxSplitSubsteps][2 * ND][kBlock];
-    __shared__ float s_tau[ND][kBlock];
-    __shared__ float s_paddle[3][kBlock];
-    __shared__ float s_body[6 * (NB - kHelpFirst)][kBlock];   // final-state position / velocity of the bodies the helpers transform
-    __shared__ float s_serve[3][kBlock];
-    __shared__ int s_flag, s_gflag, s_bflag, s_dead;   // arm: boundaries published; geometry: boundaries swept; ball: substeps done; a wait timed out
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int n = K.num_envs;
-    const int base = blockIdx.x * kBlock;
-    const int i = base + lane;
-    const int nvalid = min(kBlock, n - base);
-    const bool active = i < n;
-    const int substeps = K.substeps;
-    const ArmSite& S = K.site[0];
-    if (threadIdx.x == 0) { s_flag = 0; s_gflag = 0; s_bflag = 0; s_dead = 0; }
-    __syncthreads();
-    bool dead = false;
-#define QD_AWAIT(flag, value)                                                                             \
-    do {                                                                                                  \
-        if (!dead && !await(flag, value)) {                                                               \
-            dead = true;                                                                                  \
-            report_fault(status, PPENV_STATUS_HANDOFF_TIMEOUT);                                           \
-            if (lane == 0) __hip_atomic_store(&s_dead, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-        }                                                                                                 \
-    } while (0)
-    // rows of the tile this wave flushes after Y (waves 0, 2, 3 = parts 0, 1, 2)
-    auto flush_part = [&](int part) {
-        typedef float f4v __attribute__((ext_vector_type(4)));
-        constexpr int per_row = PPENV_NUM_OBS / 4;
-        const int total = nvalid * per_row;
-        for (int k = part * kBlock + lane; k < total; k += 3 * kBlock) {
-            const int r = k / per_row, c = 4 * (k - r * per_row);
-            const float* src = &s_obs[r * kObsStride + c];
-            const f4v val = {src[0], src[1], src[2], src[3]};
-            __builtin_nontemporal_store(val, reinterpret_cast<f4v*>(b.obs + ((size_t)(base + r) * PPENV_NUM_OBS + c)));
-        }
-    };
-    // a helper's share of the body block: bodies J0 .. J1-1 from s_body, the pelvis (the fixed base) from the site constants
-    auto help_bodies = [&](auto j0c, auto j1c) {
-        constexpr int J0 = decltype(j0c)::value, J1 = decltype(j1c)::value;
-        if (!active) return;
-        V3 bpos[NB], bvel[NB];
-        BodyState root;
-        static_body<false>(S, root);
-        bpos[0] = root.pos;
-#pragma unroll
-        for (int j = J0; j < J1; j++) {
-            const int o = 6 * (j - kHelpFirst);
-            bpos[j] = mk(s_body[o][lane], s_body[o + 1][lane], s_body[o + 2][lane]);
-            bvel[j] = mk(s_body[o + 3][lane], s_body[o + 4][lane], s_body[o + 5][lane]);
-        }
-        LdsRowStore store{&s_obs[lane * kObsStride]};
-        write_obs_bodies<J0, J1>(bpos, bvel, S.hinv, store);
-    };
-
-    if (wave == 0) {
-        // ------------------------------------------------------------------ arm wave
-        PP_STAMP_AT(0);
-        float q[ND], qd[ND], target[ND], tau[ND];
-        JointSave js[ND];
-        if (active) {
-#pragma unroll
-            for (int d = 0; d < ND; d++) {
-                q[d] = b.dof_pos[(size_t)d * n + i];
-                qd[d] = b.dof_vel[(size_t)d * n + i];
-                tau[d] = 0.f;
-                target[d] = pd_target(actions[(size_t)i * ND + d], T::drive(d).lower, T::drive(d).upper, K.clip_actions);   // VecTask.step clamp + TT:1008
-            }
-        }
-        PP_STAMP_AT(1);
-        for (int s = 0; s < substeps; s++) {
-            if (active) {
-                NullVisitor nv;   // velocity recursion only
-                fk_sweep<T>(S, q, qd, js, nv);
-                arm_substep<T>(S, js, q, qd, target, K.h, tau);
-#pragma unroll
-                for (int d = 0; d < ND; d++) { s_q[s][d][lane] = q[d]; s_q[s][ND + d][lane] = qd[d]; }
-                if (s + 1 == substeps) {
-#pragma unroll
-                    for (int d = 0; d < ND; d++) s_tau[d][lane] = tau[d];
-                }
-            }
-            if (!dbg_drop_handoff) publish(&s_flag, s + 1);   // (dbg: tests force the partners' time-out path, PPENV_DEBUG_DROP_HANDOFF)
-            PP_STAMP_AT(2 + 2 * s);
-        }
-        BodyState bodies[NB];
-        PP_STAMP_AT(5);
-        if (active) {
-            ArmGeom<T::kShapes> g;
-            BodyVisitor<T, false> bv(g, bodies);
-            fk_sweep<T>(S, q, qd, js, bv);
-            static_body<false>(S, bodies[0]);
-            s_paddle[0][lane] = bodies[NB - 1].pos.x; s_paddle[1][lane] = bodies[NB - 1].pos.y; s_paddle[2][lane] = bodies[NB - 1].pos.z;
-#pragma unroll
-            for (int j = kHelpFirst; j < NB; j++) {
-                const int o = 6 * (j - kHelpFirst);
-                s_body[o][lane] = bodies[j].pos.x; s_body[o + 1][lane] = bodies[j].pos.y; s_body[o + 2][lane] = bodies[j].pos.z;
-                s_body[o + 3][lane] = bodies[j].lin.x; s_body[o + 4][lane] = bodies[j].lin.y; s_body[o + 5][lane] = bodies[j].lin.z;
-            }
-        }
-        PP_STAMP_AT(6);
-        __syncthreads();   // X
-        if (active) {
-            V3 bpos[NB], bvel[NB];
-#pragma unroll
-            for (int j = 0; j < kHelpFirst; j++) { bpos[j] = bodies[j].pos; bvel[j] = bodies[j].lin; }
-            LdsRowStore store{&s_obs[lane * kObsStride]};
-            write_obs_bodies<0, kHelpFirst>(bpos, bvel, S.hinv, store);
-        }
-        __syncthreads();   // Y
-        PP_STAMP_AT(7);
-        if (!s_dead) flush_part(0);
-        PP_STAMP_AT(8);
-        return;
-    }
-    if (wave == 2) {
-        // ------------------------------------------------------------------ geometry wave
-        float qs[ND], qds[ND];
-        ArmGeom<T::kShapes> gg;
-        if (active) {
-#pragma unroll
-            for (int d = 0; d < ND; d++) { qs[d] = b.dof_pos[(size_t)d * n + i]; qds[d] = b.dof_vel[(size_t)d * n + i]; }
-        }
-        for (int s = 0; s < substeps; s++) {
-            if (s > 0) {
-                QD_AWAIT(&s_flag, s);                          // the arm wave has published boundary s
-                if (active) {
-#pragma unroll
-                    for (int d = 0; d < ND; d++) { qs[d] = s_q[s - 1][d][lane]; qds[d] = s_q[s - 1][ND + d][lane]; }
-                }
-            }
-            if (s >= 2) QD_AWAIT(&s_bflag, s - 1);            // the ball is done with the slot's previous content (substep s - 2)
-            if (active && !dead) {
-                JointSave js[ND];        // dead code: only the geometry (points + velocities) of this sweep is used
-                GeomVisitor<T> gv(gg);
-                fk_sweep<T>(S, qs, qds, js, gv);
-                MovingGeom<T>::each(gg, [&](int k, float& v) { s_geom[s & 1][k][lane] = v; });
-            }
-            if (!dead) publish(&s_gflag, s + 1);
-        }
-        __syncthreads();   // X
-        help_bodies(std::integral_constant<int, kHelpFirst>{}, std::integral_constant<int, kMid>{});
-        __syncthreads();   // Y
-        if (!s_dead) flush_part(1);
-        return;
-    }
-    if (wave == 3) {
-        // ------------------------------------------------------------------ auxiliary wave
-        if (active) {
-            // The serve this env gets if it resets at the end of the step: the counter RNG is a pure function of (seed, env id, episode + 1)
-            V3 sv = serve_on ? mk(b.serve[i], b.serve[(size_t)n + i], b.serve[2 * (size_t)n + i])
-                             : serve_velocity(K, (uint32_t)(K.env_id_offset + i), b.episode[i] + 1u);
-            s_serve[0][lane] = sv.x; s_serve[1][lane] = sv.y; s_serve[2][lane] = sv.z;
-        }
-        __syncthreads();   // X
-        help_bodies(std::integral_constant<int, kMid>{}, std::integral_constant<int, NB>{});
-        __syncthreads();   // Y
-        if (!s_dead) flush_part(2);
-        return;
-    }
-
-    // ---------------------------------------------------------------------- ball wave
-    PP_STAMP_AT(16);
-    EnvStateT<A> st;
-    float rew[A], pre_vx = 0.f;
-    long long reset = 0;
-    V3 next_serve = mk(0, 0, 0);
-    ArmGeom<T::kShapes> g[A];
-    V3 bound[A];
-    rew[0] = 0.f;
-    if (active) {
-        float bl[13];
-#pragma unroll
-        for (int k = 0; k < 13; k++) bl[k] = b.ball[(size_t)k * n + i];
-        st.ball.p = mk(bl[0], bl[1], bl[2]);
-#pragma unroll
-        for (int k = 0; k < 4; k++) st.ball.quat[k] = bl[3 + k];
-        st.ball.v = mk(bl[7], bl[8], bl[9]);
-        st.ball.w = mk(bl[10], bl[11], bl[12]);
-        st.progress = b.progress[(size_t)i];
-        st.flags[0] = b.flags[i];
-        st.episode = b.episode[i];
-        pre_vx = st.ball.v.x;   // TT:1020
-        static_geometry<T>(S, g[0]);
-        bound[0] = ld3(S.bound_center);
-    }
-    PP_STAMP_AT(17);
-    for (int s = 0; s < substeps; s++) {
-        QD_AWAIT(&s_gflag, s + 1);                             // the geometry wave has boundary s in LDS
-        PP_STAMP_AT(18 + 2 * s);
-        if (active && !dead) {
-            MovingGeom<T>::each(g[0], [&](int k, float& v) { v = s_geom[s & 1][k][lane]; });
-            ball_substep<T, A>(K, st.ball, g, bound);
-        }
-        if (!dead) publish(&s_bflag, s + 1);
-        PP_STAMP_AT(19 + 2 * s);
-    }
-    QD_AWAIT(&s_flag, substeps);                               // (only fails when the arm wave withheld a publish: it then never reaches X either way)
-    __syncthreads();   // X: final dof state, drive torques, paddle position, serve
-    if (active && !dead && !s_dead) {
-        BodyState bodies[NB];   // the task part reads the pelvis (row 0) and the paddle (row 9) only
-        LdsRowStore stores[A];
-#pragma unroll
-        for (int d = 0; d < ND; d++) {
-            st.q[d] = s_q[substeps - 1][d][lane];
-            st.qd[d] = s_q[substeps - 1][ND + d][lane];
-            st.dof_force[d] = s_tau[d][lane];
-        }
-        static_body<false>(S, bodies[0]);
-        bodies[NB - 1].pos = mk(s_paddle[0][lane], s_paddle[1][lane], s_paddle[2][lane]);
-        stores[0].row = &s_obs[lane * kObsStride];
-        next_serve = mk(s_serve[0][lane], s_serve[1][lane], s_serve[2][lane]);
-        post_physics_env<A, false>(K, (uint32_t)(K.env_id_offset + i), st, bodies, pre_vx, &next_serve, rew, reset, stores);
-    }
-    PP_STAMP_AT(22);
-    __syncthreads();   // Y
-    PP_STAMP_AT(23);
-    if (active && !s_dead) {   // st.q / st.qd already show the reset state where the env reset (TN keeps its dof state)
-#pragma unroll
-        for (int d = 0; d < ND; d++) {
-            st_state(&b.dof_pos[(size_t)d * n + i], st.q[d]);
-            st_state(&b.dof_vel[(size_t)d * n + i], st.qd[d]);
-            st_state(&b.dof_force[(size_t)d * n + i], st.dof_force[d]);
-        }
-        store_ball(b, n, i, st.ball);
-        store_task<A>(b, n, i, st, rew, reset);
-    }
-    PP_STAMP_AT(24);
-#undef QD_AWAIT
 }
 
 // create (mode 0: creation is episode 0) / reset_all (mode 1: next episode): state as after
@@ -1280,11 +990,10 @@ struct ppenv {
     void* arena;
     bool owns_arena;
     int serve_on;
-    int split;               // 1: step_kernel_split (two waves per 64 envs; three for the 4-actor variant), 2: 4-actor with the arm waves sweeping the geometry, 0: step_kernel
+    bool one_wave;           // step_kernel (PPENV_STEP_KERNEL=fused, or more substeps than step_kernel_split has LDS slots for); ignored by the 4-actor variant
     int agents;              // 1, or 2 for PPENV_VARIANT_T4
     uint32_t* status_host;   // PPENV_STATUS_* bits, pinned host memory mapped into the device: kernels write it through, the host reads it without a sync
     uint32_t* status_dev;
-    int ball_waves;          // ball waves per 64 envs of the two-wave schedule (1, 2 or 4: step_kernel_split's BW)
     int dbg_drop_handoff;    // PPENV_DEBUG_DROP_HANDOFF=1 at create (tests): the arm wave withholds its last hand-off, so the partner waves time out
     int dr_on;               // a randomisation is set: ppenv_step launches step_kernel<ModelG1, true> with these tables
     DRTables dr;
@@ -1326,28 +1035,21 @@ int ppenv_create(const ppenv_config* cfg, void* arena_dev, size_t arena_bytes, v
     int ndev = 0;
     PP_HIP(hipGetDeviceCount(&ndev));
     if (cfg->device_id < 0 || cfg->device_id >= ndev) { set_err("device_id out of range"); return PPENV_EINVAL; }
+    // PPENV_STEP_KERNEL=split|fused forces a schedule (same arithmetic either way).  The two-wave schedule wins at every size measured
+    // (us per step, split vs one-wave: N = 16384 13.1 / 20.5, 65536 19.6 / 22.8, 131072 35.3 / 41.5): it needs 187 VGPRs (two waves
+    // per SIMD) against 256 + 79 AGPRs.
+    const char* kernel = getenv("PPENV_STEP_KERNEL");
+    if (kernel && strcmp(kernel, "split") != 0 && strcmp(kernel, "fused") != 0) {
+        set_err("PPENV_STEP_KERNEL=%s: the accepted values are split and fused (or leave it unset)", kernel);
+        return PPENV_EINVAL;
+    }
     ppenv* e = new (std::nothrow) ppenv;
     if (!e) { set_err("out of host memory"); return PPENV_ENOMEM; }
     e->cfg = *cfg;
     e->agents = agents_of(cfg);
     e->lay = layout_for(cfg->num_envs, e->agents);
     e->serve_on = 0;
-    {   // PPENV_STEP_KERNEL=fused|split forces a schedule (same arithmetic either way)
-        // The two-wave schedule wins at every size measured (us per step, split vs one-wave: N = 16384 13.1 / 20.5,
-        // 65536 19.6 / 22.8, 131072 35.3 / 41.5): it needs 187 VGPRs (two waves per SIMD) against 256 + 79 AGPRs.
-        const char* k = getenv("PPENV_STEP_KERNEL");
-        e->split = k ? (strcmp(k, "fused") != 0) : 1;
-        if (k && strcmp(k, "quad") == 0) e->split = 3;          // four waves per 64 envs (single-humanoid variants)
-        if (k && strcmp(k, "split_g1") == 0) e->split = 4;      // two waves, the ARM wave sweeps the collision geometry (round-3 experiment, single-humanoid variants)
-        if (cfg->substeps > kMaxSplitSubsteps) e->split = 0;   // one LDS hand-off slot per substep boundary
-        if (e->agents == 2) e->split = (k && strcmp(k, "split3") == 0) ? 1 : 2;
-        else if (e->split == 3 && cfg->substeps > kMaxSplitSubsteps) e->split = 0;   // 4-actor: arm waves sweep the geometry (default), or the ball wave
-    }
-    {   // PPENV_BALL_WAVES=1|2|4: ball waves per 64 envs (single-humanoid two-wave schedule only)
-        const char* bwv = getenv("PPENV_BALL_WAVES");
-        e->ball_waves = bwv ? atoi(bwv) : kDefaultBallWaves;
-        if (e->ball_waves != 1 && e->ball_waves != 2 && e->ball_waves != 4) e->ball_waves = kDefaultBallWaves;
-    }
+    e->one_wave = (kernel && strcmp(kernel, "fused") == 0) || cfg->substeps > kMaxSplitSubsteps;   // one LDS hand-off slot per substep boundary
     e->arena = nullptr;
     e->owns_arena = false;
     e->status_host = e->status_dev = nullptr;
@@ -1430,21 +1132,16 @@ int ppenv_config_of(ppenv* e, ppenv_config* out) {
 // Which kernel ppenv_step launches for this handle NOW (the randomisation state included).  One decision, two readers: launch_step
 // switches on it, ppenv_step_kernel_name reports it — so what bench.py prints as `roofline.kernel` is what ran, not a guess from the
 // environment.  The names are the demangled ones rocprofv3's kernel trace shows (default template arguments written out).
-enum StepSchedule { SCH_DR_T4, SCH_DR_SPLIT, SCH_DR_FUSED, SCH_T4_ARMS_SWEEP, SCH_T4_BALL_SWEEPS, SCH_SPLIT_ARM_SWEEPS, SCH_QUAD, SCH_SPLIT_BW4, SCH_SPLIT_BW2,
-                    SCH_SPLIT, SCH_FUSED };
+enum StepSchedule { SCH_DR_T4, SCH_DR_SPLIT, SCH_DR_FUSED, SCH_T4, SCH_SPLIT, SCH_FUSED };
 static const char* const kScheduleNames[] = {
     "step_kernel_split<pp::ModelG1, 2, 1, 1, true>", "step_kernel_split<pp::ModelG1, 1, 0, 1, true>", "step_kernel<pp::ModelG1, true>",
-    "step_kernel_split<pp::ModelG1, 2, 1, 1, false>", "step_kernel_split<pp::ModelG1, 2, 0, 1, false>", "step_kernel_split<pp::ModelG1, 1, 1, 1, false>",
-    "step_kernel_quad<pp::ModelG1>", "step_kernel_split<pp::ModelG1, 1, 0, 4, false>", "step_kernel_split<pp::ModelG1, 1, 0, 2, false>",
-    "step_kernel_split<pp::ModelG1, 1, 0, 1, false>", "step_kernel<pp::ModelG1, false>"};
+    "step_kernel_split<pp::ModelG1, 2, 1, 1, false>", "step_kernel_split<pp::ModelG1, 1, 0, 1, false>", "step_kernel<pp::ModelG1, false>"};
 static StepSchedule schedule_of(const ppenv* e) {
-    if (e->dr_on)   // domain randomisation: the table-reading instantiation — of the two-wave schedule (default) or of the one-wave kernel (PPENV_STEP_KERNEL=fused)
-        return e->agents == 2 ? SCH_DR_T4 : e->split ? SCH_DR_SPLIT : SCH_DR_FUSED;
-    if (e->agents == 2) return e->split == 2 ? SCH_T4_ARMS_SWEEP : SCH_T4_BALL_SWEEPS;
-    if (e->split == 4) return SCH_SPLIT_ARM_SWEEPS;
-    if (e->split == 3) return SCH_QUAD;
-    if (e->split) return e->ball_waves == 4 ? SCH_SPLIT_BW4 : e->ball_waves == 2 ? SCH_SPLIT_BW2 : SCH_SPLIT;
-    return SCH_FUSED;
+    // the 4-actor variant has no one-wave kernel (its substeps are capped at kMaxSplitSubsteps by validate())
+    if (e->agents == 2) return e->dr_on ? SCH_DR_T4 : SCH_T4;
+    // domain randomisation: the table-reading instantiation of the same schedule
+    if (e->one_wave) return e->dr_on ? SCH_DR_FUSED : SCH_FUSED;
+    return e->dr_on ? SCH_DR_SPLIT : SCH_SPLIT;
 }
 
 static int launch_step(ppenv* e, const DevBuffers& buf, const float* actions_dev, void* stream) {
@@ -1463,23 +1160,8 @@ static int launch_step(ppenv* e, const DevBuffers& buf, const float* actions_dev
     case SCH_DR_FUSED:
         hipLaunchKernelGGL((step_kernel<ModelG1, true>), grid, dim3(kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->dr);
         break;
-    case SCH_T4_ARMS_SWEEP:
+    case SCH_T4:
         hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 1>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
-        break;
-    case SCH_T4_BALL_SWEEPS:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 0>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
-        break;
-    case SCH_SPLIT_ARM_SWEEPS:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 1>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
-        break;
-    case SCH_QUAD:
-        hipLaunchKernelGGL((step_kernel_quad<ModelG1>), grid, dim3(4 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
-        break;
-    case SCH_SPLIT_BW4:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0, 4>), grid, dim3(5 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
-        break;
-    case SCH_SPLIT_BW2:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0, 2>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
         break;
     case SCH_SPLIT:
         hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);

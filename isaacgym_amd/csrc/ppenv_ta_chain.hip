@@ -48,41 +48,23 @@ void ppenv_set_error(const char* msg);   // ppenv.hip
 
 namespace {
 using T = ModelG1Tree;
-constexpr int kE = 64;                 // lanes per wave = envs of a workgroup = columns of every LDS tile
-// Row pitch of the [row][env] tiles.  A role reads and writes a tile with lane = env (conflict-free at any pitch); the staging at the start and
-// the flush at the end move the Isaac-Gym-layout tensors ([env][row]) as flat float4 — lane = a run of four ROWS of one env — where a pitch of 64
-// floats puts the lanes of an env into one LDS bank.  Round 4 measured the odd pitch (-DTA_TILE_PAD=1): the staging 5.9k -> 5.2k cycles and the state
-// tiles' flush 4.6k -> 3.7k (stamps), the launch 30.4 -> 30.7 us in a same-box A/B (the roles' row addresses lose their shifts): not adopted.
-#ifndef TA_TILE_PAD
-#define TA_TILE_PAD 0
-#endif
-constexpr int kP = kE + TA_TILE_PAD;
-// Envs per workgroup.  64 in the product.  Diagnostic builds (tools/gpu_ta_narrow.sh, round 3) set 32 or 16: the upper lanes of every wave idle (they chew on
-// a copy of the workgroup's last env, like the lanes of a ragged last workgroup) and the grid has 2x / 4x the workgroups — at 4096 envs 128 / 256 CUs get one
-// instead of 64.  Measured: the chain does not get shorter (a wave issues an instruction in four passes whatever its EXEC mask), see DESIGN.md §9.
-#ifndef TA_ENVS_PER_WG
-#define TA_ENVS_PER_WG 64
-#endif
-constexpr int kEPW = TA_ENVS_PER_WG;
-static_assert(kEPW == 64 || kEPW == 32 || kEPW == 16, "envs per workgroup");
+// Lanes per wave = envs of a workgroup = columns, and row pitch, of every [row][env] LDS tile.
+// 64 envs per workgroup: round 3 measured 32 and 16 (the upper lanes of every wave idle, 2x / 4x the workgroups — at 4096 envs 128 / 256 CUs get one
+// instead of 64) and the chain did not get shorter (a wave issues an instruction in four passes whatever its EXEC mask), see DESIGN.md §9.
+// A pitch of 64: a role reads and writes a tile with lane = env (conflict-free at any pitch); the staging at the start and the flush at the end move
+// the Isaac-Gym-layout tensors ([env][row]) as flat float4 — lane = a run of four ROWS of one env — where a pitch of 64 floats puts the lanes of an env
+// into one LDS bank.  Round 4 measured an odd pitch of 65: the staging 5.9k -> 5.2k cycles and the state tiles' flush 4.6k -> 3.7k (stamps), the launch
+// 30.4 -> 30.7 us in a same-box A/B (the roles' row addresses lose their shifts): not adopted.
+constexpr int kE = 64;
 constexpr int kWaves = 6;
 // Role -> wave index.  A workgroup's waves are dealt round-robin over the CU's four SIMDs (wave i on SIMD i & 3), so six waves leave two SIMDs with two waves
-// each.  The critical path is waist -> arms -> waist, with the legs close behind.  Round 3 (tools/gpu_ta_rolemap.sh, profiles/r03_d_ta_rolemap.txt): the waist
+// each.  The critical path is waist -> arms -> waist, with the legs close behind.  Round 3 (profiles/r03_d_ta_rolemap.txt): the waist
 // shares SIMD 0 with the RIGHT ARM — the two take turns by construction (the arm waits for the torso's pose, the waist for the arms' inertias, the arm for the
 // torso's acceleration), so they hardly ever want the same issue slot — the right leg shares SIMD 1 with the (short) ball wave, and the left leg and the left arm
-// (seven links) get SIMDs 2 and 3 to themselves: 30.6 us at 4096 envs.  Round 2's placement (TA_ROLE_MAP=0: the waist with the LEFT LEG, both arms alone) made
-// the left leg the last to deliver its inertia (24.2k cycles into the step against 20.8k for the right leg): 31.4 us.  The waist with the left arm
-// (TA_ROLE_MAP=2): 32.5 us.  (Round 2, first numbering — right arm on the left leg's SIMD: the right arm's five links took 15.7k cycles against 11k for the left's seven.)
-#ifndef TA_ROLE_MAP
-#define TA_ROLE_MAP 1
-#endif
-#if TA_ROLE_MAP == 1
+// (seven links) get SIMDs 2 and 3 to themselves: 30.6 us at 4096 envs.  Round 2's placement (the waist with the LEFT LEG, both arms alone) made
+// the left leg the last to deliver its inertia (24.2k cycles into the step against 20.8k for the right leg): 31.4 us.  The waist with the left arm:
+// 32.5 us.  (Round 2, first numbering — right arm on the left leg's SIMD: the right arm's five links took 15.7k cycles against 11k for the left's seven.)
 enum { W_WAIST = 0, W_RL = 1, W_LL = 2, W_LA = 3, W_RA = 4, W_BALL = 5 };
-#elif TA_ROLE_MAP == 2
-enum { W_WAIST = 0, W_RL = 1, W_LL = 2, W_RA = 3, W_LA = 4, W_BALL = 5 };
-#else
-enum { W_WAIST = 0, W_RL = 1, W_LA = 2, W_RA = 3, W_LL = 4, W_BALL = 5 };
-#endif
 constexpr int kTorso = 15;
 constexpr int kGeoW = 39, kGeoRA = 48; // floats of collision geometry the waist / right-arm wave hand to the ball wave
 
@@ -128,19 +110,19 @@ static_assert(T::kPaddleLink == 27 && T::kBoundLink == kTorso, "collision geomet
 struct __attribute__((aligned(16))) Shared {
     float dof[kE * 2 * NDOF];         // (q, qd) pairs: element (e, d, k) at e * 54 + 2 d + k
     float act[kE * NDOF];             // raw actions at the start, the reported drive torques at the end: (e, d) at e * 27 + d
-    float root[39][kP];               // rows 0..12: the base state (start of the current substep / final), 13..25 table, 26..38 ball ([row][env]: the waist and the ball wave read and write it every substep)
-    float torso[18][kP];              // pass 1 hand-off: Rw 9, pw 3, w 3, v 3 of the torso (link 15)
-    float sums[5][3][kP];             // final phase: each chain wave's share of the balance sums (pos, vel, norm)
-    float paddle[3][kP];              // final phase: paddle position (body 39)
+    float root[39][kE];               // rows 0..12: the base state (start of the current substep / final), 13..25 table, 26..38 ball ([row][env]: the waist and the ball wave read and write it every substep)
+    float torso[18][kE];              // pass 1 hand-off: Rw 9, pw 3, w 3, v 3 of the torso (link 15)
+    float sums[5][3][kE];             // final phase: each chain wave's share of the balance sums (pos, vel, norm)
+    float paddle[3][kE];              // final phase: paddle position (body 39)
     float pre_vx[kE];                 // the ball's vx before the step (TA:1143)
     union {
         struct {
-            float art_leg[2][27][kP]; // pass 2: what a leg adds to the pelvis (A6 B9 D6 pn3 pf3)
-            float art_arm[2][27][kP]; // pass 2: what an arm adds to the torso
-            float acc_base[6][kP];    // pelvis acceleration (alpha, a)
-            float acc_torso[6][kP];   // torso acceleration
-            float geo_w[2][kGeoW][kP];   // collision geometry of the pelvis / torso shapes + bound centre, slot = substep & 1
-            float geo_ra[2][kGeoRA][kP]; // ... of the forearm / hand shapes and the paddle blade
+            float art_leg[2][27][kE]; // pass 2: what a leg adds to the pelvis (A6 B9 D6 pn3 pf3)
+            float art_arm[2][27][kE]; // pass 2: what an arm adds to the torso
+            float acc_base[6][kE];    // pelvis acceleration (alpha, a)
+            float acc_torso[6][kE];   // torso acceleration
+            float geo_w[2][kGeoW][kE];   // collision geometry of the pelvis / torso shapes + bound centre, slot = substep & 1
+            float geo_ra[2][kGeoRA][kE]; // ... of the forearm / hand shapes and the paddle blade
         } hub;
         float obs[kE * PPENV_TA_NUM_OBS];   // final phase: the observation rows, row-major (flushed as one contiguous block)
     } u;
@@ -152,13 +134,10 @@ static_assert(sizeof(Shared) <= 160 * 1024, "LDS budget");
 __device__ __forceinline__ void publish(int* flag, int value) {
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
-#ifndef TA_POLL_SLEEP
-#define TA_POLL_SLEEP 1      // s_sleep argument between two polls of a hand-off flag (x 64 cycles)
-#endif
 __device__ __forceinline__ bool await(int* flag, int value) {
     for (int spin = 0; spin < (1 << 22); spin++) {
         if (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) >= value) return true;
-        __builtin_amdgcn_s_sleep(TA_POLL_SLEEP);
+        __builtin_amdgcn_s_sleep(1);     // 64 cycles between two polls of a hand-off flag
     }
     return false;
 }
@@ -172,15 +151,15 @@ __device__ __forceinline__ bool await(int* flag, int value) {
         }                                                                                                            \
     } while (0)
 
-__device__ __forceinline__ V3 row3(const float (*r)[kP], int k0, int e) { return mk(r[k0][e], r[k0 + 1][e], r[k0 + 2][e]); }
-__device__ __forceinline__ void put3(float (*r)[kP], int k0, int e, V3 v) { r[k0][e] = v.x; r[k0 + 1][e] = v.y; r[k0 + 2][e] = v.z; }
-__device__ __forceinline__ void put_art(float (*r)[kP], int e, const ArtI& I) {
+__device__ __forceinline__ V3 row3(const float (*r)[kE], int k0, int e) { return mk(r[k0][e], r[k0 + 1][e], r[k0 + 2][e]); }
+__device__ __forceinline__ void put3(float (*r)[kE], int k0, int e, V3 v) { r[k0][e] = v.x; r[k0 + 1][e] = v.y; r[k0 + 2][e] = v.z; }
+__device__ __forceinline__ void put_art(float (*r)[kE], int e, const ArtI& I) {
     const float v[27] = {I.A.xx, I.A.yy, I.A.zz, I.A.xy, I.A.xz, I.A.yz, I.B.m[0], I.B.m[1], I.B.m[2], I.B.m[3], I.B.m[4], I.B.m[5], I.B.m[6], I.B.m[7], I.B.m[8],
                          I.D.xx, I.D.yy, I.D.zz, I.D.xy, I.D.xz, I.D.yz, I.pn.x, I.pn.y, I.pn.z, I.pf.x, I.pf.y, I.pf.z};
 #pragma unroll
     for (int t = 0; t < 27; t++) r[t][e] = v[t];
 }
-__device__ __forceinline__ ArtI get_art(const float (*r)[kP], int e) {
+__device__ __forceinline__ ArtI get_art(const float (*r)[kE], int e) {
     float v[27];
 #pragma unroll
     for (int t = 0; t < 27; t++) v[t] = r[t][e];
@@ -225,7 +204,7 @@ __device__ __forceinline__ void kin_step(float q, float qd, Frame& f, float& c, 
     f.Rw = mul(f.Rw, E);
     f.w = wn; f.v = vn;
 }
-__device__ __forceinline__ Frame base_frame(const float (*root)[kP], int e) {
+__device__ __forceinline__ Frame base_frame(const float (*root)[kE], int e) {
     float quat[4] = {root[3][e], root[4][e], root[5][e], root[6][e]};
     Frame f;
     f.Rw = quat_to_m3(quat);
@@ -467,7 +446,7 @@ __device__ __forceinline__ void limb_out(TaskCtx& c, const Limb<FIRST, N>& lb, F
 
 // collision geometry of the shapes riding on link LI -> rows of a hand-off slot (a va b vb per shape in the order of ArmGeom; paddle; bound)
 template <int LI, int NROWS>
-__device__ __forceinline__ void geo_capture(float (*slot)[kP], int e, const Frame& f, int& row) {
+__device__ __forceinline__ void geo_capture(float (*slot)[kE], int e, const Frame& f, int& row) {
     constexpr LinkC L = T::link(LI);
     static_for<T::kShapes>([&](auto sc) {
         constexpr int s = decltype(sc)::value;
@@ -527,18 +506,9 @@ constexpr bool geo_owners_ok() {   // every shape, the paddle and the bound cent
 }
 static_assert(geo_owners_ok(), "collision shapes must ride on the pelvis, the waist chain or the right arm");
 
-// How the full-workgroup flush leaves the CU (profiling builds: -DTA_FLUSH_MODE=0 plain stores; 1 = non-temporal, the default)
-#ifndef TA_FLUSH_MODE
-#define TA_FLUSH_MODE 1
-#endif
+// The full-workgroup flush leaves the CU with non-temporal stores
 template <class V>
-__device__ __forceinline__ void flush_store(V v, V* p) {
-#if TA_FLUSH_MODE == 1
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
+__device__ __forceinline__ void flush_store(V v, V* p) { __builtin_nontemporal_store(v, p); }
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ Frame torso_frame(const Shared& S, int e) {
     Frame f;
@@ -559,9 +529,9 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
     __shared__ Shared S;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int e0 = blockIdx.x * kEPW;
+    const int e0 = blockIdx.x * kE;
     const int n = a.p.num_envs;
-    const int nvalid = min(kEPW, n - e0);
+    const int nvalid = min(kE, n - e0);
     const int e = lane;
     const int env = e0 + min(e, nvalid - 1);      // lanes past the workgroup's last env compute on a copy of it and store nothing (or the same values to its rows)
     const bool live = e < nvalid;
@@ -659,7 +629,7 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
             if constexpr (decltype(with_geo)::value) {              // the right arm carries collision shapes and the paddle
                 if (sub >= 2) TA_AWAIT(&S.f_ball, sub - 1);         // the ball wave is done with this geometry slot
                 int grow = 0;
-                float (*gslot)[kP] = S.u.hub.geo_ra[sub & 1];
+                float (*gslot)[kE] = S.u.hub.geo_ra[sub & 1];
                 L.pass1(ft, [&](auto lc, const Frame& f) { geo_capture<decltype(lc)::value, kGeoRA>(gslot, e, f, grow); });
                 publish(&S.f_geo_ra, sub + 1);
             } else {
@@ -701,7 +671,7 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
             publish(&S.f_torso, sub + 1);
             {   // collision geometry of the pelvis / torso shapes for the ball wave
                 int grow = 0;
-                float (*gslot)[kP] = S.u.hub.geo_w[sub & 1];
+                float (*gslot)[kE] = S.u.hub.geo_w[sub & 1];
                 geo_capture<0, kGeoW>(gslot, e, f0, grow);
                 static_for<3>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
@@ -770,12 +740,12 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
             V3 bound[1];
             static_for<T::kShapes>([&](auto sc) {
                 constexpr int s = decltype(sc)::value;
-                const float (*slot)[kP] = gm.slot[s] == 0 ? S.u.hub.geo_w[sub & 1] : S.u.hub.geo_ra[sub & 1];
+                const float (*slot)[kE] = gm.slot[s] == 0 ? S.u.hub.geo_w[sub & 1] : S.u.hub.geo_ra[sub & 1];
                 g[0].a[s] = row3(slot, gm.row[s], e); g[0].va[s] = row3(slot, gm.row[s] + 3, e);
                 g[0].b[s] = row3(slot, gm.row[s] + 6, e); g[0].vb[s] = row3(slot, gm.row[s] + 9, e);
             });
             {
-                const float (*slot)[kP] = S.u.hub.geo_ra[sub & 1];
+                const float (*slot)[kE] = S.u.hub.geo_ra[sub & 1];
                 g[0].pc = row3(slot, gm.paddle_row, e); g[0].pn = row3(slot, gm.paddle_row + 3, e);
                 g[0].vpc = row3(slot, gm.paddle_row + 6, e); g[0].pnd = row3(slot, gm.paddle_row + 9, e);
                 bound[0] = row3(S.u.hub.geo_w[sub & 1], gm.bound_row, e);
@@ -1179,8 +1149,8 @@ bool ta_chain_model_matches(const TAConsts& C, char* why, size_t nwhy) {
 
 int ta_chain_launch(const TAScal& P, const TAChainArgs& a, void* stream) {
     const int n = a.p.num_envs;
-    if (a.dr_on()) hipLaunchKernelGGL(ta_chain_kernel<true>, dim3((n + kEPW - 1) / kEPW), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
-    else hipLaunchKernelGGL(ta_chain_kernel<false>, dim3((n + kEPW - 1) / kEPW), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
+    if (a.dr_on()) hipLaunchKernelGGL(ta_chain_kernel<true>, dim3((n + kE - 1) / kE), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
+    else hipLaunchKernelGGL(ta_chain_kernel<false>, dim3((n + kE - 1) / kE), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
     if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching the chain-wave 27-dof step failed"); return PPENV_EHIP; }
     return PPENV_OK;
 }

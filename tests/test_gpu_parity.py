@@ -101,15 +101,13 @@ def test_fused_step_matches_oracle_single_steps(torch_cuda, oracle_lib, variant,
 
 
 @pytest.mark.parametrize("schedule,n", [("split", 1000), ("fused", 1000), ("fused", 130), ("split", 63), ("split", 1), ("fused", 1),
-                                        ("quad", 1000), ("quad", 63), ("quad", 1),
                                         ("split:1", 1000), ("split:2", 1000), ("split:2", 95), ("split:2", 1), ("split:4", 1000), ("split:4", 81), ("split:4", 17)])
 def test_both_schedules_on_ragged_sizes(torch_cuda, oracle_lib, monkeypatch, schedule, n):
-    """The two-wave (default), the one-wave and the four-wave (round-2 experiment, DESIGN.md §9) step kernels run the same arithmetic;
-    sizes that are not a multiple of 64.  "split:B": the two-wave schedule with B ball waves of 64 / B envs each (round 3)."""
+    """The two-wave (default) and the one-wave step kernels run the same arithmetic; sizes that are not a multiple of 64.
+    "split:B": the sizes the narrow-ball-wave kernels (B ball waves per 64 envs, removed: DESIGN.md §6) were checked at, now on the
+    two-wave kernel, which has one ball wave."""
     torch = torch_cuda
-    if ":" in schedule:
-        schedule, bw = schedule.split(":")
-        monkeypatch.setenv("PPENV_BALL_WAVES", bw)
+    schedule = schedule.split(":")[0]
     monkeypatch.setenv("PPENV_STEP_KERNEL", schedule)
     cfg = scene.build_config("TT", num_envs=n, seed=21)
     o = oracle_lib.OracleEnv(cfg)
@@ -136,23 +134,21 @@ def test_schedules_agree_step_by_step(torch_cuda, monkeypatch):
     torch = torch_cuda
     n = 4096
     envs = {}
-    for schedule in ("split", "fused", "quad"):
+    for schedule in ("split", "fused"):
         monkeypatch.setenv("PPENV_STEP_KERNEL", schedule)
         envs[schedule] = make_env(scene.build_config("TN", num_envs=n, seed=2))
     gen = torch.Generator(device="cuda").manual_seed(1)
     for t in range(100):
         a = torch.rand(n, 7, device="cuda", generator=gen) * 2 - 1
         envs["fused"].set_state(envs["split"].get_state())
-        envs["quad"].set_state(envs["split"].get_state())
         for e in envs.values():
             e.step(a)
-        for other in ("fused", "quad"):
-            for name in ("reset_buf", "progress_buf", "flags", "episode"):
-                assert torch.equal(getattr(envs["split"], name), getattr(envs[other], name)), (other, name, t)
-            # rew: alpha = 1000 (TN) times the ball-velocity agreement of ~1e-4 m/s right after a paddle hit
-            for name, atol in (("obs_buf", 2e-4), ("rew_buf", 1e-1), ("dof_pos", 1e-5), ("dof_vel", 1e-3), ("ball", 5e-3)):
-                x, y = getattr(envs["split"], name), getattr(envs[other], name)
-                assert torch.allclose(x, y, rtol=1e-5, atol=atol), (other, name, t, float((x - y).abs().max()))
+        for name in ("reset_buf", "progress_buf", "flags", "episode"):
+            assert torch.equal(getattr(envs["split"], name), getattr(envs["fused"], name)), (name, t)
+        # rew: alpha = 1000 (TN) times the ball-velocity agreement of ~1e-4 m/s right after a paddle hit
+        for name, atol in (("obs_buf", 2e-4), ("rew_buf", 1e-1), ("dof_pos", 1e-5), ("dof_vel", 1e-3), ("ball", 5e-3)):
+            x, y = getattr(envs["split"], name), getattr(envs["fused"], name)
+            assert torch.allclose(x, y, rtol=1e-5, atol=atol), (name, t, float((x - y).abs().max()))
     for e in envs.values():
         e.close()
 
@@ -505,7 +501,7 @@ def test_vectask_reset_idx_and_control_frequency(torch_cuda):
     np.testing.assert_allclose(dx, 2 * 0.0083 * ball0[7].cpu().numpy(), rtol=1e-3)
 
 
-@pytest.mark.parametrize("schedule", ["split", "quad"])
+@pytest.mark.parametrize("schedule", ["split"])
 def test_handoff_timeout_is_reported_not_stored(torch_cuda, monkeypatch, schedule):
     """A wave of the multi-wave step kernel that never receives its partner's LDS hand-off must not store plausible garbage:
     it sets the handle's status word and every later call fails with PPENV_EDEVICE.  PPENV_DEBUG_DROP_HANDOFF withholds the
@@ -534,6 +530,18 @@ def test_handoff_timeout_is_reported_not_stored(torch_cuda, monkeypatch, schedul
     torch.cuda.synchronize()
     assert ok.status == 0
     ok.close()
+
+
+@pytest.mark.parametrize("name", ["quad", "split_g1", "split3", "bogus"])
+def test_unknown_step_kernel_is_refused(torch_cuda, monkeypatch, name):
+    """PPENV_STEP_KERNEL accepts split and fused only: a retired schedule or a typo fails at create instead of quietly
+    running the default (an A/B run would then compare the default with itself)."""
+    from isaacgym_amd import _lib
+    monkeypatch.setenv("PPENV_STEP_KERNEL", name)
+    with pytest.raises(_lib.PPEnvError, match="PPENV_STEP_KERNEL"):
+        make_env(scene.build_config("TT", num_envs=64, seed=2))
+    with pytest.raises(_lib.PPEnvError, match="PPENV_STEP_KERNEL"):
+        make_env(scene.build_config("T4", num_envs=64, seed=2))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -120,11 +120,10 @@ class DevView:
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("schedule,n", [("split", 1024), ("split", 200), ("split3", 200), ("split", 8192)])   # 8192: BASELINE config 4's per-GPU size, as named
+@pytest.mark.parametrize("schedule,n", [("split", 1024), ("split", 200), ("split", 8192)])   # 8192: BASELINE config 4's per-GPU size, as named
 def test_t4_fused_step_matches_oracle_single_steps(torch_cuda, oracle_lib, monkeypatch, schedule, n):
-    """The three-wave kernel (arm 1 / arm 2 / ball) in both hand-off forms — the arm waves sweep the collision geometry
-    (default), or the ball wave does from the published (q, qd) — vs the oracle, restarted from the oracle's state every
-    step; n = 200 leaves a ragged last workgroup."""
+    """The three-wave kernel (arm 1 / arm 2 / ball; the arm waves sweep the collision geometry) vs the oracle, restarted
+    from the oracle's state every step; n = 200 leaves a ragged last workgroup."""
     torch = torch_cuda
     from isaacgym_amd.env import PPEnv
     monkeypatch.setenv("PPENV_STEP_KERNEL", schedule)
