@@ -10,6 +10,7 @@
  *   (the learner's backward)
  *   ppenv_ppo_grad_sumsq     per-workgroup partial sums of the squared, still scaled gradients of every tensor in a table
  *   ppenv_ppo_adam_step      every workgroup sums the partials in the same order; unscale, clip, Adam; a non-finite norm skips the step
+ *                            (with ppenv_ppo_adam.world > 1: on the rank means of all-reduced gradient sums)
  *
  * No float atomics anywhere: every sum has a fixed order, so results are bitwise reproducible run to run.  The loss scale and the
  * step count live in a ppenv_ppo_scaler on the device and are never read by the host: ppenv_ppo_adam_step reads `state_in` and writes
@@ -84,6 +85,9 @@ typedef struct ppenv_ppo_adam {
     int32_t truncate;          /* truncate_grads: clip_grad_norm_(max_norm) */
     float growth_factor, backoff_factor;   /* 2.0, 0.5 (1.0, 1.0: a constant scale) */
     int32_t growth_interval;   /* 2000 */
+    int32_t world;             /* data-parallel ranks; 0 or 1: one.  Above 1 the gradient buffers hold the SUMS over the ranks (each x the loss
+                                  scale, as a gradient all-reduce leaves them): Adam consumes fl(g_sum / world), a correctly rounded fp32 division
+                                  (rl_games' all_grads / world_size), then unscales; the norm, the clip and the skip are those of these means */
 } ppenv_ppo_adam;
 
 /* table: `count` ppenv_ppo_tensor in DEVICE memory (written once by the caller).  parts: the workgroups of both launches and the length

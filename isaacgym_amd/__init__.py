@@ -9,11 +9,12 @@ __all__ = ["make", "scene"]
 
 
 def make(seed=0, task="HumanoidPingpongTiltG1", num_envs=None, sim_device="cuda:0", rl_device="cuda:0", graphics_device_id=-1,
-         headless=True, multi_gpu=False, virtual_screen_capture=False, force_render=False, cfg=None):
+         headless=True, multi_gpu=False, virtual_screen_capture=False, force_render=False, cfg=None, device=None):
     """Create a task by its reference name.  With multi_gpu=True the rank comes from LOCAL_RANK/RANK (reference
     train.py:117-120): each rank owns its own env shard on its own GPU.  The seed is used as given — train.py:119 has already
     added the rank to the seed it passes in — and the shard is told apart by its global env-id offset, which keys the reset
-    draws: a sharded run with one common seed reproduces the single-handle run env for env (isaacgym_amd.distributed)."""
+    draws: a sharded run with one common seed reproduces the single-handle run env for env (isaacgym_amd.distributed).
+    device: with multi_gpu, the rank's device instead of cuda:LOCAL_RANK (ranks that share a GPU over gloo: cuda:LOCAL_RANK % device_count)."""
     import os
 
     from .tasks import isaacgym_task_map
@@ -24,7 +25,7 @@ def make(seed=0, task="HumanoidPingpongTiltG1", num_envs=None, sim_device="cuda:
     if multi_gpu:
         local_rank = int(os.environ.get("LOCAL_RANK", "0"))
         rank = int(os.environ.get("RANK", "0"))
-        sim_device = rl_device = f"cuda:{local_rank}"
+        sim_device = rl_device = f"cuda:{local_rank}" if device is None else str(device)
         cfg["seed"] = int(seed)
         cfg["env_id_offset"] = rank * int(cfg["env"]["numEnvs"])
     else:

@@ -219,9 +219,10 @@ __device__ __forceinline__ bool finite64(double x) {
     return (__double_as_longlong(x) & 0x7ff0000000000000LL) != 0x7ff0000000000000LL;
 }
 
-struct AdamCoef { float gmul, b1, b2, one_m_b1, one_m_b2, step_size, bc2_sqrt, eps; };
+struct AdamCoef { float gmul, b1, b2, one_m_b1, one_m_b2, step_size, bc2_sqrt, eps, world; bool mean; };
 
 __device__ __forceinline__ void adam1(float& p, float& m, float& v, float g, const AdamCoef& k) {
+    if (k.mean) g = g / k.world;                                  // the rank mean of an all-reduced sum: all_grads / world_size (IEEE division)
     g *= k.gmul;                                                  // unscale and clip
     m = m + k.one_m_b1 * (g - m);                                 // exp_avg.lerp_(grad, 1 - beta1)
     v = v * k.b2 + k.one_m_b2 * g * g;                            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
@@ -236,7 +237,10 @@ __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_t
     __shared__ double red[kOptThreads / 64];
     double part = 0.0;
     for (int b = threadIdx.x; b < parts; b += kOptThreads) part += slab[b];
-    const double sumsq = block_sum(part, red);
+    const bool mean = hp.world > 1;
+    // the rank means' square sum: the sums' over world^2, in fp64 (exact for a power-of-two world: identical shards then reproduce one rank)
+    const double raw = block_sum(part, red);
+    const double sumsq = mean ? raw / ((double)hp.world * (double)hp.world) : raw;
     const ppenv_ppo_scaler st = *state_in;
     const bool finite = finite64(sumsq);
     const double norm = sqrt(sumsq) / (double)st.scale;            // of the unscaled gradients
@@ -268,6 +272,8 @@ __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_t
     k.step_size = (float)((double)*lr / bc1);
     k.bc2_sqrt = (float)sqrt(bc2);
     k.eps = hp.eps;
+    k.world = (float)hp.world;
+    k.mean = mean;
     const long long total = s.start[count], stride = (long long)gridDim.x * kOptThreads;
     int t = 0;
     for (long long it = (long long)blockIdx.x * kOptThreads + threadIdx.x; it < total; it += stride) {
@@ -333,8 +339,8 @@ extern "C" int ppenv_ppo_grad_sumsq(const ppenv_ppo_tensor* table, int32_t count
 extern "C" int ppenv_ppo_adam_step(const ppenv_ppo_tensor* table, int32_t count, const double* slab, int32_t parts, ppenv_ppo_adam hp, const float* lr,
                                    const ppenv_ppo_scaler* state_in, ppenv_ppo_scaler* state_out, void* stream) {
     if (!table || !slab || !lr || !state_in || !state_out || state_in == state_out || count <= 0 || count > PPENV_PPO_MAX_TENSORS || parts <= 0 ||
-        parts > 65535 || hp.growth_interval <= 0) {
-        ppenv_set_error("ppenv_ppo_adam_step: NULL pointer, state_in == state_out (the state is double-buffered), or bad sizes");
+        parts > 65535 || hp.growth_interval <= 0 || hp.world < 0) {
+        ppenv_set_error("ppenv_ppo_adam_step: NULL pointer, state_in == state_out (the state is double-buffered), bad sizes or world < 0");
         return PPENV_EINVAL;
     }
     hipLaunchKernelGGL(ppo_adam_kernel, dim3(parts), dim3(kOptThreads), 0, (hipStream_t)stream, table, count, slab, parts, hp, lr, state_in, state_out);

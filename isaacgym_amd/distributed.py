@@ -187,33 +187,62 @@ class GradientBuckets:
     are all-reduced as soon as the backward has ENQUEUED the kernels that produce them — asynchronously, so the collective of layer l runs on RCCL's
     stream beside the dX / dW kernels of the layers below it (a layer's dW of both networks is 0.5–25 MB: a bucket by itself; xGMI is point to point,
     large buckets keep its per-link rings busy).  `wait()` joins them (the compute stream then waits for the collectives) and turns the sums into means;
-    call it before the optimizer step.  force: issue the collectives even in a one-rank group (the RCCL path on a one-GPU box)."""
+    call it before the optimizer step.  force: issue the collectives even in a one-rank group (the RCCL path on a one-GPU box).
+    mean=False: `wait()` leaves the sums in place, for an optimizer that averages them itself (ppo.DeviceAdam(world=...): the division happens inside
+    its Adam kernel instead of one in-place division launch per tensor here)."""
 
-    def __init__(self, group=None, force=False):
-        self.group = group
+    def __init__(self, group=None, force=False, mean=True):
+        self.group, self.mean = group, bool(mean)
         self.active = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or force)
         self.world = dist.get_world_size(group) if self.active else 1
-        self.works, self.tensors, self.names, self.bytes = [], [], [], 0
+        self.works, self.tensors, self.names, self.bytes, self.collectives = [], [], [], 0, 0
         self._joined = True                     # wait() has run since the last bucket: the next bucket starts a new backward
 
     def __call__(self, name, tensors):
         """Not for `backward(accumulate=True)`: the gradient buffers then hold sums that earlier backward passes already reduced, and reducing
         them again would count those once more — accumulate locally (on_grads=None) and pass this callable to the LAST micro-batch's backward only
-        (NativeMLPLearner.backward refuses the combination)."""
-        if self._joined:                        # `names` / `bytes` describe ONE backward: they start over here instead of growing for ever
-            self.names, self.bytes, self._joined = [], 0, False
+        (NativeMLPLearner.backward refuses the combination).
+        A bucket whose tensors tile one contiguous stretch of memory (NativeMLPLearner allocates each layer's weight and bias gradients so) goes into
+        ONE collective over that stretch; other tensors get one collective each.  `collectives` counts them for the current backward."""
+        if self._joined:                        # `names` / `bytes` / `collectives` describe ONE backward: they start over here instead of growing for ever
+            self.names, self.bytes, self.collectives, self._joined = [], 0, 0, False
         self.names.append(name)
-        for t in tensors:
+        self.bytes += sum(t.numel() * t.element_size() for t in tensors)
+        for t in _coalesce(list(tensors)):
             self.tensors.append(t)
-            self.bytes += t.numel() * t.element_size()
             if self.active:
+                self.collectives += 1
                 self.works.append(dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
     def wait(self):
         for w in self.works:
             w.wait()
-        if self.world > 1:
+        if self.world > 1 and self.mean:
             for t in self.tensors:
                 t.div_(self.world)
         self.works, self.tensors = [], []
         self._joined = True
+
+
+def _coalesce(tensors):
+    """The tensors with every run of neighbours merged into one flat view: contiguous, one dtype, and each starting in the same storage where
+    the one before ends (an element-wise collective over the view is the collectives over the run's tensors, in one launch)."""
+    out, run, end = [], [], None
+    for t in tensors:
+        if run and t.is_contiguous() and t.dtype == run[0].dtype and t.device == run[0].device and \
+                t.untyped_storage().data_ptr() == run[0].untyped_storage().data_ptr() and t.data_ptr() == end:
+            run.append(t)
+        else:
+            out.append(_flat(run))
+            run = [t]
+        end = t.data_ptr() + t.numel() * t.element_size() if t.is_contiguous() else None
+    out.append(_flat(run))
+    return [t for t in out if t is not None]
+
+
+def _flat(run):
+    if not run:
+        return None
+    if len(run) == 1:
+        return run[0]
+    return run[0].new_empty(0).set_(run[0].untyped_storage(), run[0].storage_offset(), (sum(t.numel() for t in run),))

@@ -13,6 +13,7 @@ kernel (v_mfma_f32_32x32x16_f16, fp32 accumulation):
 PyTorch is only the owner of the device buffers here.  Weights are cast to fp16 once (`load`), as autocast does per call.
 """
 import ctypes as C
+import math
 import os
 
 import torch
@@ -460,7 +461,9 @@ class NativeMLPLearner:
     ([M, A + 1] fp32, already multiplied by the loss scale if one is used) and fills `grads` — fp32 tensors of the parameters' shapes.
     An optimizer (rl_games: Adam) steps on `parameters()` / `grads` and calls `sync_weights()`; that part stays PyTorch."""
 
-    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0):
+    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, head_grad_extra=0):
+        """head_grad_extra: fp32 slots right after the heads' bias gradient, `grad_extra` (a caller's gradient, e.g. the log-std's, that then
+        travels in the heads' all-reduce: each layer's gradients — and the heads' with these slots — are ONE contiguous buffer, one collective)."""
         self.net = NativeMLP(actor, critic, num_obs, device, mean=mean, var=var, eps=eps, clip=clip)
         self.device = self.net.device
         f = lambda t: t.detach().to(self.device, torch.float32).contiguous()
@@ -476,7 +479,16 @@ class NativeMLPLearner:
         self.wt = [None] + [z16(2, u[i - 1], u[i]) for i in range(1, len(u))]
         self.head_w32 = z32(na + 1, 2 * u[-1])                              # the block-diagonal master image the head launches read
         self.head_wt = z16(2 * u[-1], self.nh)
-        self.grads = dict(w=[z32(*w.shape) for w in net.w], b=[z32(2, n) for n in u], head_w=z32(self.nh, 2 * u[-1]), head_b=z32(na + 1))
+        def flat(*shapes):                                                 # consecutive views of one zeroed buffer
+            buf = z32(sum(math.prod(sh) for sh in shapes))
+            out, at = [], 0
+            for sh in shapes:
+                out.append(buf[at:at + math.prod(sh)].view(sh))
+                at += math.prod(sh)
+            return out
+        layers = [flat(tuple(w.shape), (2, n)) for w, n in zip(net.w, u)]
+        head_w, head_b, self.grad_extra = flat((self.nh, 2 * u[-1]), (na + 1,), (int(head_grad_extra),))
+        self.grads = dict(w=[w for w, _ in layers], b=[b for _, b in layers], head_w=head_w, head_b=head_b)
         self._rows = 0
         self.rms = None
         self._cast_items = None
@@ -612,9 +624,9 @@ class NativeActorCritic(torch.nn.Module):
     masters of NativeMLPLearner (`hidden_w.i` [2, n, k] = actor | critic, `hidden_b.i`, `mu_w`, `mu_b`, `value_w`, `value_b`); `from_rlgames`
     builds one from an rl_games state dict.  The minibatch must be a multiple of 64 rows (the weight-gradient kernel's contraction tile)."""
 
-    def __init__(self, actor, critic, num_obs, device, normalize_input=True, eps=1e-5, clip=5.0):
+    def __init__(self, actor, critic, num_obs, device, normalize_input=True, eps=1e-5, clip=5.0, head_grad_extra=0):
         super().__init__()
-        self.learner = NativeMLPLearner(actor, critic, num_obs, device, eps=eps, clip=clip)
+        self.learner = NativeMLPLearner(actor, critic, num_obs, device, eps=eps, clip=clip, head_grad_extra=head_grad_extra)
         self.learner.rms = None
         if normalize_input:
             # a SUBMODULE under rl_games' own name: state_dict() / load_state_dict() carry `running_mean_std.running_mean | running_var | count`

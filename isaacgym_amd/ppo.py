@@ -25,6 +25,20 @@ Deviations from rl_games:
   - The minibatches are the contiguous row ranges of the horizon-major buffers, in order.
 
 Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
+
+Data-parallel training (the reference's multi_gpu mode: `torchrun --nproc_per_node=N train.py multi_gpu=True`; rl_games' multi-GPU a2c).  Each
+rank owns an env shard (isaacgym_amd.make(multi_gpu=True)) and a learner; `PPOTrainer(..., group=...)` switches it on when the group has more
+than one rank (or with force=True: RCCL with one rank).  Restated from rl_games' published code like the rest of this module (absent offline:
+parity unpinned):
+  - at the start rank 0's parameters, log-std and input / value statistics are broadcast (rl_games broadcasts its model state_dict);
+  - every minibatch step all-reduces the gradients (one collective per layer beside the backward, distributed.GradientBuckets; the log-std
+    gradient lives right after the heads' gradients and travels in their collective) and steps on their rank mean, formed inside the Adam kernel (DeviceAdam(world=...): rl_games' all_grads / world_size);
+    all ranks see the same summed bits, so parameters, moments and the loss scale stay identical, and a non-finite sum skips the step on all;
+  - per rank, as in rl_games: the input and value statistics (updated from the rank's own shard, never synchronised), advantage
+    normalisation, minibatch_size;
+  - global: the epoch statistics of train_epoch() (loss terms, KL and clip fraction averaged over the ranks; episode sums and counts summed),
+    in one all-reduce per epoch, and `frame` (horizon x rows x world).
+Only rank 0 writes checkpoints; load() on every rank reads the same file, so the ranks resume identical — all with rank 0's statistics.
 """
 import argparse
 import ctypes as C
@@ -37,6 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from . import distributed as D
 from .collector import RolloutCollector, gae
 from .policy import UNITS, NativeActorCritic, RunningMeanStd
 
@@ -67,7 +82,7 @@ class PPOTensor(C.Structure):
 class PPOAdam(C.Structure):
     """ctypes mirror of ppenv_ppo_adam."""
     _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("max_norm", C.c_float), ("truncate", C.c_int32),
-                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32)]
+                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32), ("world", C.c_int32)]
 
 
 def _lib_ppo():
@@ -266,10 +281,12 @@ class DeviceAdam:
     """clip_grad_norm_ + torch.optim.Adam + GradScaler on the device, over `params` / `grads` as they are (any evenly strided rows).
     Two launches per step (ppenv_ppo_grad_sumsq, ppenv_ppo_adam_step).  `scale` is the device scalar the loss gradient multiplies by;
     the scaler state (include/ppenv_ppo.h ppenv_ppo_scaler) is double-buffered in `state` [2, 8] int32: the step reads row `cur`, writes
-    row 1 - cur, and `cur` flips on the host (the host never reads the state)."""
+    row 1 - cur, and `cur` flips on the host (the host never reads the state).
+    world: data-parallel ranks.  Above 1, `grads` hold the all-reduced SUMS over the ranks (distributed.GradientBuckets(mean=False)) and the
+    kernels step on their rank means fl(g / world); 0 or 1: one rank, bit-identical to the default."""
 
     def __init__(self, params, grads, lr, max_norm=10.0, truncate=True, init_scale=65536.0, growth_interval=2000, dynamic=True,
-                 betas=(0.9, 0.999), eps=1e-8, parts=OPT_PARTS):
+                 betas=(0.9, 0.999), eps=1e-8, parts=OPT_PARTS, world=1):
         assert len(params) == len(grads) and 0 < len(params) <= 64
         self.params, self.grads = list(params), list(grads)
         dev = self.device = self.params[0].device
@@ -286,7 +303,10 @@ class DeviceAdam:
         self.count, self.parts = len(items), int(parts)
         self.slab = torch.zeros(self.parts, dtype=torch.float64, device=dev)
         self.lr = torch.full((), float(lr), dtype=torch.float32, device=dev)
-        self.hp = PPOAdam(betas[0], betas[1], eps, max_norm, int(truncate), 2.0 if dynamic else 1.0, 0.5 if dynamic else 1.0, int(growth_interval))
+        if int(world) < 0:
+            raise ValueError(f"world: {world} ranks")
+        self.hp = PPOAdam(betas[0], betas[1], eps, max_norm, int(truncate), 2.0 if dynamic else 1.0, 0.5 if dynamic else 1.0, int(growth_interval),
+                          int(world))
         self.state = torch.zeros((2, 8), dtype=torch.int32, device=dev)
         self.state[:, 0:1].view(torch.float32).fill_(float(init_scale))
         self.cur = 0
@@ -336,9 +356,11 @@ def _norm(x, rms):
 class PPOTrainer:
     """rl_games' a2c_continuous on a task built by isaacgym_amd.make(...): its native handle (task.env: PPEnv or TAEnv) runs under
     RolloutCollector; the network is NativeActorCritic (nn.Linear's default initialisation, rl_games' `initializer: default`) with a learnable
-    fixed log-std (its `sigma` parameter, initialised to sigma_init) and, with normalize_value, a value RunningMeanStd of width 1."""
+    fixed log-std (its `sigma` parameter, initialised to sigma_init) and, with normalize_value, a value RunningMeanStd of width 1.
+    group: a torch.distributed process group (None: the default group, if one is initialised); data-parallel when it has more than one rank, or
+    with force=True (the collectives with one rank, as bench.py --force-dist).  See the module docstring for what is per rank and what is global."""
 
-    def __init__(self, task, cfg=None, seed=0):
+    def __init__(self, task, cfg=None, seed=0, group=None, force=False):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if getattr(task, "randomize", False):
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
@@ -349,10 +371,19 @@ class PPOTrainer:
         cfg.check(self.rows)
         self.num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
         self.seed = int(seed)
+        dist = torch.distributed
+        initialised = dist.is_available() and dist.is_initialized()
+        if force and not initialised:
+            raise RuntimeError("PPOTrainer(force=True) needs an initialised torch.distributed process group")
+        self.group = group
+        self.multi = initialised and (dist.get_world_size(group) > 1 or bool(force))
+        self.world = dist.get_world_size(group) if self.multi else 1
+        self.rank = dist.get_rank(group) if self.multi else 0
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
             actor, critic = self._mlp(self.num_actions), self._mlp(1)
-        self.net = NativeActorCritic(actor, critic, self.num_obs, dev, normalize_input=cfg.normalize_input)
+        # the log-std gradient in the slots right after the heads' gradients: one collective carries both
+        self.net = NativeActorCritic(actor, critic, self.num_obs, dev, normalize_input=cfg.normalize_input, head_grad_extra=self.num_actions)
         self.learner = self.net.learner
         with torch.no_grad():
             self.net.sigma.fill_(cfg.sigma_init)
@@ -362,11 +393,13 @@ class PPOTrainer:
         H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
                                     sigma=torch.exp(self.logstd), seed=self.seed)
-        self.g_logstd = torch.zeros(self.num_actions, dtype=torch.float32, device=dev)
+        self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
                               max_norm=cfg.grad_norm, truncate=cfg.truncate_grads, init_scale=cfg.init_scale if cfg.mixed_precision else 1.0,
-                              growth_interval=cfg.growth_interval, dynamic=cfg.mixed_precision)
+                              growth_interval=cfg.growth_interval, dynamic=cfg.mixed_precision, world=self.world)
+        # the gradient all-reduce: sums left in place, averaged inside the Adam kernel
+        self.buckets = D.GradientBuckets(group, force=force, mean=False) if self.multi else None
         total = H * n
         z = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)
         self.old_nlp, self.adv, self.old_v, self.ret = z(total), z(total), z(total), z(total)
@@ -374,6 +407,22 @@ class PPOTrainer:
         self.stats = z(self.steps_per_epoch, 8)
         self.ep_ret, self.ep_len = z(n), z(n)                              # the running episode of every row (unscaled rewards)
         self.epoch, self.frame = 0, 0
+        if self.multi:
+            self._broadcast_start()
+
+    @torch.no_grad()
+    def _broadcast_start(self):
+        """Rank 0's fp32 parameters, log-std and input / value statistics (running and the fp32 images the kernels read) to every rank."""
+        dist = torch.distributed
+        src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
+        tensors = self.learner.parameters() + [self.logstd]
+        for rms in (self.learner.rms, self.value_rms):
+            if rms is not None:
+                tensors += [rms.running_mean, rms.running_var, rms.count, rms.mean, rms.inv_std]
+        for t in tensors:
+            dist.broadcast(t, src, group=self.group)
+        self.learner.sync_weights()
+        self.col.sigma.copy_(torch.exp(self.logstd))
 
     def _mlp(self, n_out):
         d, out = self.num_obs, []
@@ -430,9 +479,17 @@ class PPOTrainer:
         old_mu = col.head[:cfg.horizon_length].reshape(total, A + 1)[sl, :A]
         d_head = self.loss(mu, value, col.actions.reshape(total, A)[sl], old_mu, col.sigma, self.old_nlp[sl], self.adv[sl], self.old_v[sl],
                            self.ret[sl], self.logstd, self.opt.scale, stats_row)
-        self.learner.backward(d_head)
+        if self.buckets is not None:
+            self.learner.backward(d_head, on_grads=self._on_grads)
+            self.buckets.wait()                                              # the stream waits for the collectives, the host does not
+        else:
+            self.learner.backward(d_head)
         self.opt.step()
         self.learner.sync_weights()
+
+    def _on_grads(self, name, tensors):
+        """The backward's per-layer callback: the heads' bucket takes the log-std gradient (adjacent in memory) along: layers + 1 collectives."""
+        self.buckets(name, list(tensors) + [self.g_logstd] if name == "heads" else tensors)
 
     def learn(self):
         total, mb = self.cfg.horizon_length * self.rows, self.cfg.minibatch_size
@@ -475,8 +532,12 @@ class PPOTrainer:
         self.col.next_horizon()
         self.net.eval()
         self.epoch += 1
-        self.frame += self.cfg.horizon_length * self.rows
+        self.frame += self.cfg.horizon_length * self.rows * self.world
         mean = self.stats.mean(0)
+        if self.multi:                                                       # one all-reduce: the rank means' sum, the episode sums
+            g = torch.cat([mean[:len(STATS)], ep])
+            torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM, group=self.group)
+            mean, ep = g[:len(STATS)] / self.world, g[len(STATS):]
         f = self.opt.fields()
         out = {k: mean[i] for i, k in enumerate(STATS)}
         n = ep[2].clamp(min=1.0)
@@ -497,11 +558,15 @@ class PPOTrainer:
         return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats}
 
     def save(self, path):
+        """Data-parallel: rank 0 writes, the other ranks return (their parameters and optimizer state are rank 0's)."""
+        if self.rank != 0:
+            return
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         torch.save(self.state_dict(), path)
 
     def load(self, path):
-        """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame."""
+        """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame.
+        Data-parallel: every rank loads the same file (rank 0's), so all resume identical, each with rank 0's input and value statistics."""
         ck = torch.load(path, map_location=self.device, weights_only=True)
         sd, lr = ck["model"], self.learner
         from .policy import layers_from_rlgames_state_dict
@@ -529,17 +594,52 @@ class PPOTrainer:
 
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
+def init_rank(backend="nccl", force=False):
+    """The process group of a data-parallel run under torch.distributed.run (train.py's rank semantics): -> (rank, device).  nccl: one GPU per
+    rank, cuda:LOCAL_RANK, the communicator bound to it (device_id, as bench.py); gloo: ranks may share cuda:LOCAL_RANK % device_count.
+    force: a one-rank world (no launcher) is accepted and gets the group too."""
+    rank, local_rank, world = D.rank_info()
+    if world <= 1 and not force:
+        raise SystemExit("--multi-gpu needs a world above 1: launch it with `python -m torch.distributed.run --nproc_per_node=N -m isaacgym_amd.ppo "
+                         "--multi-gpu ...`, or pass --force-dist to run the collectives with one rank")
+    os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+    if "MASTER_PORT" not in os.environ:              # a one-rank world without a launcher (--force-dist): any free port of this host
+        import socket
+        with socket.socket() as sk:
+            sk.bind(("127.0.0.1", 0))
+            os.environ["MASTER_PORT"] = str(sk.getsockname()[1])
+    dist = torch.distributed
+    if backend == "nccl":
+        dev = torch.device("cuda", local_rank)
+        torch.cuda.set_device(dev)
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    else:
+        dev = torch.device("cuda", local_rank % torch.cuda.device_count())
+        torch.cuda.set_device(dev)
+        dist.init_process_group(backend, rank=rank, world_size=world)
+    return rank, dev
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.ppo", description="PPO (rl_games a2c_continuous) on the native env and network")
     ap.add_argument("--task", default="HumanoidPingpongTiltNESSparse27DOFG1")
-    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--num-envs", type=int, default=4096, help="envs per rank with --multi-gpu")
     ap.add_argument("--max-epochs", type=int, default=None)
-    ap.add_argument("--minibatch-size", type=int, default=None)
+    ap.add_argument("--minibatch-size", type=int, default=None, help="rows per rank with --multi-gpu")
     ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task and train yamls from")
     ap.add_argument("--out", default=None, help="run directory (default runs/<task>)")
-    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--seed", type=int, default=42, help="with --multi-gpu, rank r uses seed + r (train.py)")
     ap.add_argument("--print-every", type=int, default=10)
+    ap.add_argument("--multi-gpu", action="store_true", help="data-parallel, one rank per process under python -m torch.distributed.run")
+    ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl (RCCL) one GPU per rank; gloo: ranks may share a GPU")
+    ap.add_argument("--force-dist", action="store_true", help="with --multi-gpu: accept a one-rank world and run the collectives anyway")
     args = ap.parse_args(argv)
+    if args.force_dist and not args.multi_gpu:
+        ap.error("--force-dist belongs to --multi-gpu")
+    rank, seed, dev = 0, args.seed, None
+    if args.multi_gpu:
+        rank, dev = init_rank(args.dist_backend, force=args.force_dist)
+        seed = args.seed + rank
     import isaacgym_amd
     over = {k: v for k, v in (("max_epochs", args.max_epochs), ("minibatch_size", args.minibatch_size)) if v is not None}
     task_cfg = None
@@ -553,23 +653,30 @@ def main(argv=None):
     else:
         cfg = PPOConfig(**over)
         cfg.check()
-    task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
-    tr = PPOTrainer(task, cfg, seed=args.seed)
+    if args.multi_gpu:
+        task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, multi_gpu=True, device=dev, cfg=task_cfg)
+    else:
+        task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
+    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist)
     out = args.out or os.path.join("runs", args.task)
     ckpt = os.path.join(out, "nn", f"{args.task}.pth")
     t0 = time.perf_counter()
     for e in range(cfg.max_epochs):
         res = tr.train_epoch()
         last = e + 1 == cfg.max_epochs
-        if (e + 1) % args.print_every == 0 or last:
+        if ((e + 1) % args.print_every == 0 or last) and rank == 0:
             vals = {k: float(v) for k, v in res.items()}           # the only host read
             dt = time.perf_counter() - t0
             print(f"epoch {tr.epoch} frames {tr.frame} fps {tr.frame / dt:.0f} loss {vals['loss']:.4g} a {vals['a_loss']:.4g} c {vals['c_loss']:.4g} "
                   f"kl {vals['kl']:.3g} clip {vals['clip_frac']:.3f} scale {vals['scale']:.0f} skipped {vals['skipped']:.0f} "
                   f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f}", flush=True)
         if (e + 1) % cfg.save_frequency == 0 or last:
-            tr.save(ckpt)
-    print(f"saved {ckpt}")
+            tr.save(ckpt)                                          # rank 0 only
+    if rank == 0:
+        print(f"saved {ckpt}" + (f" (ranks: {tr.world}, frames global)" if tr.multi else ""), flush=True)
+    if args.multi_gpu:
+        torch.distributed.barrier()
+        torch.distributed.destroy_process_group()
 
 
 if __name__ == "__main__":

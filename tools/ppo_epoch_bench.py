@@ -12,7 +12,9 @@ critic_coef 4, clip_value, bounds_loss_coef 1e-4, grad_norm 10, normalize_advant
 
 rl_games itself is not importable here (absent from the reference and the image); the loss terms are restated from its published a2c_continuous /
 common_losses (actor: clipped surrogate; critic: clipped value loss; bound loss on mu beyond +-1.1) — timing context, parity unpinned.
-Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo] [--num-envs 4096] [--minibatch 32768] [--epochs 3]"""
+Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo] [--num-envs 4096] [--minibatch 32768] [--epochs 3]
+Data-parallel (every learner, --learner ppo included: PPOTrainer with its gradient all-reduce and the mean inside the Adam kernel): under
+`python -m torch.distributed.run --nproc_per_node=N`, or with --force-dist for one rank on RCCL; --dist-backend gloo lets ranks share a GPU."""
 import argparse
 import json
 import math
@@ -34,18 +36,22 @@ ap.add_argument("--num-envs", type=int, default=4096)
 ap.add_argument("--minibatch", type=int, default=32768)
 ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--force-dist", action="store_true", help="create the nccl group and all-reduce the gradients even with ONE rank (the RCCL path on a one-GPU box)")
+ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share cuda:LOCAL_RANK %% device_count (rehearsal on one GPU)")
 args = ap.parse_args()
 # data-parallel learners, one rank per GPU (the reference's multi_gpu mode, train.py:117-120): launched by torch.distributed.run, each rank owns num_envs envs
 # and its own learner; the gradients are averaged over the ranks before every optimizer step (native learner: one all-reduce per layer beside the backward)
 import torch.distributed as dist  # noqa: E402
 from isaacgym_amd import distributed as D  # noqa: E402
 rank, local_rank, world = D.rank_info()
-dev = torch.device("cuda", local_rank)
+dev = torch.device("cuda", local_rank if args.dist_backend == "nccl" else local_rank % torch.cuda.device_count())
 torch.cuda.set_device(dev)
 use_dist = world > 1 or args.force_dist
 if use_dist:
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29571")
-    dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    if args.dist_backend == "nccl":
+        dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev)
+    else:
+        dist.init_process_group("gloo", rank=rank, world_size=world)
 n, H, A, NOBS = args.num_envs, 32, 27, 313
 
 
@@ -57,13 +63,11 @@ def timed(fn):
     return time.perf_counter() - t0, out
 
 
-if args.learner == "ppo":          # the library trainer: the same epoch, its tail on the device
-    if use_dist:
-        raise SystemExit("--learner ppo runs one rank (multi-rank training is not part of PPOTrainer)")
+if args.learner == "ppo":          # the library trainer: the same epoch, its tail on the device (data-parallel under torchrun / --force-dist)
     import isaacgym_amd  # noqa: E402
     from isaacgym_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
-    tr = PPOTrainer(isaacgym_amd.make(seed=0, task="HumanoidPingpongTiltNESSparse27DOFG1", num_envs=n, rl_device=str(dev), sim_device=str(dev)),
-                    PPOConfig(minibatch_size=args.minibatch), seed=0)
+    tr = PPOTrainer(isaacgym_amd.make(seed=rank, task="HumanoidPingpongTiltNESSparse27DOFG1", num_envs=n, multi_gpu=True, device=dev),
+                    PPOConfig(minibatch_size=args.minibatch), seed=rank, force=args.force_dist)
     for _ in range(3):             # a run that has been training for a while (see below)
         tr.col.collect().next_horizon()
         for t in range(H):
@@ -78,15 +82,24 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
         tr.col.sigma.copy_(torch.exp(tr.logstd))
         tr.col.next_horizon()
     roll_ms, learn_ms = roll_s / args.epochs * 1e3, learn_s / args.epochs * 1e3
+    if use_dist:
+        t = torch.tensor([roll_ms, learn_ms], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        roll_ms, learn_ms = float(t[0]), float(t[1])
     steps = tr.steps_per_epoch
     f = tr.opt.fields()
-    print(json.dumps({
+    if rank == 0:
+      print(json.dumps({
         "what": "one PPO epoch of BASELINE config 5's per-GPU slice (27-dof task, rl_games a2c_continuous settings of cfg/train/HumanoidPingpongTiltG1PPO.yaml), context only",
         "learner": "ppo", "num_envs": n, "horizon": H, "minibatch_rows": args.minibatch, "mini_epochs": tr.cfg.mini_epochs, "minibatch_steps_per_epoch": steps,
-        "ms_rollout_per_epoch": roll_ms, "ms_learning_per_epoch": learn_ms, "ms_per_minibatch_step": learn_ms / steps, "ranks": 1,
-        "env_steps_per_s_end_to_end": n * H / ((roll_ms + learn_ms) * 1e-3), "last_loss": float(tr.stats[-1, 0]),
+        "ms_rollout_per_epoch": roll_ms, "ms_learning_per_epoch": learn_ms, "ms_per_minibatch_step": learn_ms / steps, "ranks": world,
+        "gradient_all_reduce": f"{args.dist_backend}, one collective per layer beside the backward, the log-std with the heads; the mean inside the Adam kernel" if use_dist else "none (one rank)",
+        "env_steps_per_s_end_to_end": world * n * H / ((roll_ms + learn_ms) * 1e-3), "last_loss": float(tr.stats[-1, 0]),
         "loss_scale": float(f["scale"]), "skipped_steps": int(f["skipped"]),
         "finite": bool(all(torch.isfinite(p).all() for p in tr.learner.parameters()))}))
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
     sys.exit(0)
 MINI_EPOCHS, E_CLIP, CRITIC_COEF, BOUNDS_COEF, GRAD_NORM, LR = 5, 0.2, 4.0, 1e-4, 10.0, 2e-5     # yaml:60-85
 torch.manual_seed(0)
