@@ -221,13 +221,17 @@ __device__ __forceinline__ bool finite64(double x) {
 
 struct AdamCoef { float gmul, b1, b2, one_m_b1, one_m_b2, step_size, bc2_sqrt, eps, world; bool mean; };
 
+// Every rounding is spelled out (contraction off, the fused steps written as fma): left to the compiler, the two products of the second
+// moment were fused differently in the 16-byte loop and in the element loop, and a tensor's bits depended on its alignment and strides
+// (tests/test_ppo_edges_gpu.py::test_adam_layouts_agree_bitwise_and_match_torch).
 __device__ __forceinline__ void adam1(float& p, float& m, float& v, float g, const AdamCoef& k) {
+    #pragma clang fp contract(off)
     if (k.mean) g = g / k.world;                                  // the rank mean of an all-reduced sum: all_grads / world_size (IEEE division)
-    g *= k.gmul;                                                  // unscale and clip
-    m = m + k.one_m_b1 * (g - m);                                 // exp_avg.lerp_(grad, 1 - beta1)
-    v = v * k.b2 + k.one_m_b2 * g * g;                            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
+    g *= k.gmul;                                                  // unscale and clip: rounded, as torch's in-place unscale leaves the gradient
+    m = __builtin_fmaf(k.one_m_b1, g - m, m);                     // exp_avg.lerp_(grad, 1 - beta1)
+    v = __builtin_fmaf(k.one_m_b2 * g, g, v * k.b2);              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, 1 - beta2)
     const float denom = sqrtf(v) / k.bc2_sqrt + k.eps;
-    p = p - k.step_size * (m / denom);                            // param.addcdiv_(exp_avg, denom, -step_size)
+    p = __builtin_fmaf(-k.step_size, m / denom, p);               // param.addcdiv_(exp_avg, denom, -step_size)
 }
 
 __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_tensor* table, int count, const double* slab, int parts,

@@ -102,7 +102,7 @@ def _autograd(b, e_clip, critic_coef, bounds_coef, entropy_coef, clip_value):
 
 
 @pytest.mark.parametrize("clip_value", [True, False])
-@pytest.mark.parametrize("a", [7, 27])
+@pytest.mark.parametrize("a", [1, 7, 27, 32])
 def test_analytic_loss_gradient_matches_autograd(a, clip_value):
     rng = np.random.default_rng(a + 100 * clip_value)
     m, e_clip, cc, bc, ec = 512, 0.2, 4.0, 1e-4, 0.01
