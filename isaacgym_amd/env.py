@@ -141,9 +141,39 @@ class PPEnv:
         r.action_noise_sigma, r.observation_noise_sigma = float(action_noise_sigma), float(observation_noise_sigma)
         _lib.check(self.L.ppenv_set_randomization(self.h, C.byref(r)), self.L)
 
+    DR_TABLE_ROWS = {"dof_stiffness_scale": 7, "dof_damping_scale": 7, "link_mass_scale": 7, "restitution_scale": 0, "friction_scale": 0}
+
+    def set_reset_randomization(self, plan, seed=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """Reset-time randomisation, the reference's rule (TT:849-850, 1025; include/ppenv_dr.h): `plan` (scene.reset_randomization_plan
+        of the task's randomization_params) names the tables to draw.  They are allocated here — 1 for a scaling, 0 for an additive term
+        until an env's first redraw — and handed to set_randomization together with the two noise amplitudes; from then on
+        apply_reset_randomization(), once after every step, redraws the columns of the envs that reset.  seed: default the handle's.
+        -> the ResetRandomizer (tables, randomize_buf, draws)."""
+        from .dr import ResetRandomizer
+        rr = ResetRandomizer(self.L, self.device, self.num_envs, plan, self.DR_TABLE_ROWS, seed=self.config.seed if seed is None else seed,
+                             env_id_offset=self.config.env_id_offset, reset_rows=self.num_agents)
+        self.set_randomization(**rr.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+        self.reset_randomization = rr
+        return rr
+
+    def set_noise_sigmas(self, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """The two noise amplitudes alone, over the tables of set_reset_randomization (they stay the same tensors)."""
+        self.set_randomization(**self.reset_randomization.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+
+    def apply_reset_randomization(self, env_ids=None):
+        """The per-step launch (ppenv_dr_apply on this handle's reset_buf); env_ids: the id variant, for reset_idx(env_ids)."""
+        rr = getattr(self, "reset_randomization", None)
+        if rr is None:
+            raise _lib.PPEnvError("apply_reset_randomization: no plan is set (set_reset_randomization)")
+        if env_ids is None:
+            rr.apply(self.reset_buf)
+        else:
+            rr.apply_ids(env_ids)
+
     def clear_randomization(self):
         _lib.check(self.L.ppenv_set_randomization(self.h, None), self.L)
         self._dr = None
+        self.reset_randomization = None
 
     def set_gravity(self, gravity_z):
         _lib.check(self.L.ppenv_set_gravity(self.h, float(gravity_z)), self.L)

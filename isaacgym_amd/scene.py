@@ -113,6 +113,71 @@ class Randomization(C.Structure):
                 ("observation_noise_sigma", C.c_float)]
 
 
+# Reset-time domain randomisation drawn on the device (include/ppenv_dr.h)
+DR_MAX_TABLES, DR_MAX_ROWS, DR_BLOCK = 8, 64, 256
+DR_SEED_SALT = 0xD1B54A32D192ED03
+DR_DISTRIBUTIONS = {"uniform": 0, "gaussian": 1}
+DR_OPERATIONS = {"scaling": 0, "additive": 1}
+DR_SCHEDULES = {None: 0, "linear": 1, "constant": 2}
+
+
+class DREntry(C.Structure):
+    """ctypes mirror of ppenv_dr_entry."""
+    _fields_ = [("table", C.c_void_p), ("rows", C.c_int32), ("distribution", C.c_int32), ("operation", C.c_int32), ("schedule", C.c_int32),
+                ("a", C.c_float), ("b", C.c_float), ("schedule_steps", C.c_int32), ("reserved", C.c_int32)]
+
+
+class DRPlan(C.Structure):
+    """ctypes mirror of ppenv_dr_plan."""
+    _fields_ = [("num_envs", C.c_int32), ("env_id_offset", C.c_int32), ("seed", C.c_uint64), ("frequency", C.c_int32), ("reset_rows", C.c_int32),
+                ("num_tables", C.c_int32), ("reserved", C.c_int32), ("entry", DREntry * DR_MAX_TABLES)]
+
+
+# set_randomization's table names, where the yaml keeps each under actor_params.humanoid, and which row count it takes
+_DR_TABLE_KEYS = (("dof_stiffness_scale", ("dof_properties", "stiffness"), "dof"), ("dof_damping_scale", ("dof_properties", "damping"), "dof"),
+                  ("link_mass_scale", ("rigid_body_properties", "mass"), "mass"), ("restitution_scale", ("rigid_shape_properties", "restitution"), None),
+                  ("friction_scale", ("rigid_shape_properties", "friction"), None))
+
+
+def reset_randomization_plan(dr_params, dof_rows=NUM_DOF, mass_rows=NUM_DOF):
+    """task.randomization_params (cfg/task/HumanoidPingpongTiltG1.yaml:102-169) -> the plan of its actor parameters, in
+    set_randomization's terms: {"frequency": f, "tables": {name: {"rows", "distribution", "operation", "range", "schedule",
+    "schedule_steps"}}}.  rows: dof_rows for the two drive-gain tables, mass_rows for the link masses (7 / 7 for the 7-dof variants,
+    27 / 28 for the 27-dof task), 1 for the two per-env scalars.  `color`, `lower` / `upper` and `setup_only` are ignored, as the
+    per-step path ignores them."""
+    hum = ((dr_params.get("actor_params") or {}).get("humanoid") or {})
+    tables = {}
+    for name, (group, key), kind in _DR_TABLE_KEYS:
+        p = (hum.get(group) or {}).get(key)
+        if not p:
+            continue
+        dist, op, sch = p.get("distribution", "uniform"), p.get("operation"), p.get("schedule")
+        if dist not in DR_DISTRIBUTIONS or op not in DR_OPERATIONS or sch not in DR_SCHEDULES:
+            raise ValueError(f"randomization_params ...{group}.{key}: unknown distribution / operation / schedule ({dist!r}, {op!r}, {sch!r})")
+        tables[name] = {"rows": {"dof": int(dof_rows), "mass": int(mass_rows), None: 1}[kind], "distribution": dist, "operation": op,
+                        "range": (float(p["range"][0]), float(p["range"][1])), "schedule": sch,
+                        "schedule_steps": int(p.get("schedule_steps", 0)) if sch else 0}
+    return {"frequency": int(dr_params.get("frequency", 1)), "tables": tables}
+
+
+def build_dr_plan(plan, table_ptrs, num_envs, env_id_offset=0, seed=0, reset_rows=1):
+    """reset_randomization_plan's dict + the device address of each table -> ppenv_dr_plan.  Entry order (it enters the RNG key) is
+    set_randomization's argument order, whatever the dict's."""
+    names = [n for n, _, _ in _DR_TABLE_KEYS if n in plan["tables"]]
+    unknown = set(plan["tables"]) - set(names)
+    if unknown or not names:
+        raise ValueError(f"reset randomisation plan: no tables, or names set_randomization does not have: {sorted(unknown)}")
+    P = DRPlan()
+    P.num_envs, P.env_id_offset, P.seed, P.frequency, P.reset_rows, P.num_tables = int(num_envs), int(env_id_offset), int(seed) & (2 ** 64 - 1), \
+        int(plan["frequency"]), int(reset_rows), len(names)
+    for en, n in zip(P.entry, names):
+        t = plan["tables"][n]
+        en.table, en.rows = int(table_ptrs[n]), int(t["rows"])
+        en.distribution, en.operation, en.schedule = DR_DISTRIBUTIONS[t["distribution"]], DR_OPERATIONS[t["operation"]], DR_SCHEDULES[t.get("schedule")]
+        en.a, en.b, en.schedule_steps = float(t["range"][0]), float(t["range"][1]), int(t.get("schedule_steps", 0))
+    return P
+
+
 class Buffers(C.Structure):
     _fields_ = [
         ("num_envs", C.c_int32), ("num_agents", C.c_int32),

@@ -174,9 +174,22 @@ class TASim:
         r.action_noise_sigma, r.observation_noise_sigma = float(action_noise_sigma), float(observation_noise_sigma)
         self._ck(self.L.ppenv_ta_sim_set_randomization(self.h, C.byref(r)))
 
+    DR_TABLE_ROWS = {"dof_stiffness_scale": 27, "dof_damping_scale": 27, "link_mass_scale": 28, "restitution_scale": 0, "friction_scale": 0}
+
+    def set_reset_randomization(self, plan, seed=0, env_id_offset=0, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """Reset-time randomisation (include/ppenv_dr.h) of this simulation's tables: allocates the ones `plan` names
+        (scene.reset_randomization_plan with dof_rows 27, mass_rows 28), hands them to set_randomization and builds the device plan.
+        -> the ResetRandomizer; its apply(reset_buf) is the per-step launch."""
+        from .dr import ResetRandomizer
+        rr = ResetRandomizer(self.L, self.device, self.num_envs, plan, self.DR_TABLE_ROWS, seed=seed, env_id_offset=env_id_offset)
+        self.set_randomization(**rr.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+        self.reset_randomization = rr
+        return rr
+
     def clear_randomization(self):
         self._ck(self.L.ppenv_ta_sim_set_randomization(self.h, None))
         self._dr = None
+        self.reset_randomization = None
 
     def pd_targets(self, actions):
         """pre_physics_step's PD targets (TA:1131) for actions [N,27]."""
@@ -273,6 +286,30 @@ class TAEnv:
         """Domain-randomisation tables + noise amplitudes for every later step (TASim.set_randomization; fused step on the chain-wave kernel)."""
         assert self.fused, "the randomisation tables are read by the fused step (ppenv_ta_step)"
         self.sim.set_randomization(**kw)
+
+    def set_reset_randomization(self, plan, seed=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """Reset-time randomisation, the reference's rule (TASim.set_reset_randomization; PPEnv.set_reset_randomization has the contract).
+        seed: default the task's."""
+        assert self.fused, "the randomisation tables are read by the fused step (ppenv_ta_step)"
+        return self.sim.set_reset_randomization(plan, seed=self.params.seed if seed is None else seed, env_id_offset=self.params.env_id_offset,
+                                                action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+
+    @property
+    def reset_randomization(self):
+        return getattr(self.sim, "reset_randomization", None)
+
+    def set_noise_sigmas(self, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        self.sim.set_randomization(**self.reset_randomization.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+
+    def apply_reset_randomization(self, env_ids=None):
+        """The per-step launch (ppenv_dr_apply on reset_buf); env_ids: the id variant, for reset_idx(env_ids)."""
+        rr = self.reset_randomization
+        if rr is None:
+            raise _lib.PPEnvError("apply_reset_randomization: no plan is set (set_reset_randomization)")
+        if env_ids is None:
+            rr.apply(self.reset_buf)
+        else:
+            rr.apply_ids(env_ids)
 
     def clear_randomization(self):
         self.sim.clear_randomization()

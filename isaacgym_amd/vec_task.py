@@ -78,10 +78,18 @@ class VecTask:
         self.randomize = bool(task_cfg.get("randomize", False))                     # cfg/task/HumanoidPingpongTiltG1.yaml:101
         self.randomization_params = task_cfg.get("randomization_params", {}) or {}  # yaml:102-169
         self.first_randomization, self.last_step, self.last_rand_step = True, -1, -1
+        # when the actor parameters are redrawn: "step" — every env's, every `frequency` control steps, on the host (apply_randomizations);
+        # "reset" — the reference's rule (TT:849-850, 1025): an env's, when it resets, on the device (include/ppenv_dr.h)
+        self.randomize_apply_at = self.randomization_params.get("apply_at", "step")
+        if self.randomize_apply_at not in ("step", "reset"):
+            raise ValueError(f"task.randomization_params.apply_at must be 'step' or 'reset', got {self.randomize_apply_at!r}")
+        self._dr_reset = False
         self.stats_every = int(config.get("stats_every", 40))                       # TT:763: the reference prints the means every 40 steps
 
         self.sim = self.create_sim()       # the reference's VecTask.__init__ calls back create_sim (TT:325)
         self.allocate_buffers()
+        if self.randomize and self.randomize_apply_at == "reset":
+            self._set_reset_randomization()
 
     # -- hooks the task class fills in
     def create_sim(self):
@@ -101,6 +109,17 @@ class VecTask:
         self.reset_buf_force = torch.zeros(rows, device=self.device, dtype=torch.long)
         self._obs_clipped = None if not np.isfinite(self.clip_obs) else torch.empty_like(self.obs_buf)
 
+    def _set_reset_randomization(self):
+        """apply_at: "reset" — the actor-parameter tables of randomization_params become a device plan of the environment
+        (set_reset_randomization); `randomize_buf` is from now on the buffer the kernel maintains: control steps since the env's last
+        redraw (TT:1025), zeroed for exactly the envs that redraw."""
+        plan = scene.reset_randomization_plan(self.randomization_params, dof_rows=getattr(self, "DR_DOF_ROWS", scene.NUM_DOF),
+                                              mass_rows=getattr(self, "DR_MASS_ROWS", scene.NUM_DOF))
+        if not plan["tables"]:
+            return
+        self.randomize_buf = self.env.set_reset_randomization(plan).randomize_buf
+        self._dr_reset = True
+
     # -- the surface rl_games drives
     def step(self, actions):
         """One control step: K1..K8 in a single kernel launch (TT:1002-1052).  controlFrequencyInv = k (upstream: pre_physics_step
@@ -109,6 +128,8 @@ class VecTask:
         if self.randomize:                   # upstream applies them from _reset_idx (TT:849-850); here once per step, gated by `frequency`
             self.apply_randomizations(self.randomization_params)
         self.env.step(actions)              # action clamp (clipActions) happens inside the kernel
+        if self._dr_reset:                  # randomize_buf += 1; the envs this step reset redraw their table columns (one launch, no sync)
+            self.env.apply_reset_randomization()
         self.control_steps += 1
         self.last_step = self.control_steps
         if self.stats_every > 0 and self.control_steps % self.stats_every == 0:
@@ -174,6 +195,12 @@ class VecTask:
             base = self.native_config.gravity_z if hasattr(self, "native_config") else scene.TA_GRAVITY_Z
             dz = float(sample(g, (1,)).item()) if g.get("operation") == "additive" else 0.0
             self.env.set_gravity(min(base + dz, 0.0) if g.get("operation") == "additive" else base * float(sample(g, (1,)).item()))
+        if self.randomize_apply_at == "reset":       # the actor parameters are drawn on the device, per env, at reset time (_set_reset_randomization);
+            if self._dr_reset:                      # the noise amplitudes and gravity above keep this global rule, as upstream's non-env randomisations do
+                self.env.set_noise_sigmas(**kw)
+            else:
+                self.env.set_randomization(**kw)
+            return
         hum = ((dr_params.get("actor_params") or {}).get("humanoid") or {})
         mass = (hum.get("rigid_body_properties") or {}).get("mass")
         if mass:
@@ -204,6 +231,12 @@ class VecTask:
             self.env.reset_all()
         else:
             self.env.reset_idx(env_ids)
+        self._reset_idx_randomization(env_ids)
+
+    def _reset_idx_randomization(self, env_ids):
+        """_reset_idx's apply_randomizations (TT:849-850) for a reset from outside a step: the listed envs (None: all) count as resetting."""
+        if self._dr_reset:
+            self.env.apply_reset_randomization(torch.arange(self.num_envs, device=self.device) if env_ids is None else env_ids)
 
     def reset_done(self):
         return self._obs_dict(), torch.nonzero(self.reset_buf, as_tuple=False).flatten()
@@ -418,6 +451,8 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
         if self.randomize:                  # as the 7-dof tasks: once per step, gated by `frequency` (upstream: from _reset_idx, TA's reset path)
             self.apply_randomizations(self.randomization_params)
         self.env.step(actions)              # the clipActions clamp happens inside the kernel
+        if self._dr_reset:
+            self.env.apply_reset_randomization()
         self.control_steps += 1
         self.last_step = self.control_steps
         if self.stats_every > 0 and self.control_steps % self.stats_every == 0:   # TA:860-866 prints the same two means every 40 steps
@@ -430,3 +465,4 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
         """_reset_idx (TA:965-1028) for the listed envs (None: all): root states, dof states, ball y / z and serve of the env's
         next episode, progress 0, the four sticky flags cleared.  Like the reference's, it leaves obs_buf to the next step."""
         self.env.reset_idx(env_ids)
+        self._reset_idx_randomization(env_ids)
