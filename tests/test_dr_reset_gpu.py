@@ -97,10 +97,12 @@ def test_entry_points_refuse_bad_arguments(torch_cuda):
 
 
 # ------------------------------------------------------------------------------------------------ 5. the property that matters
-def make_task(name, n, seed, block, **task_over):
+def make_task(name, n, seed, block, env_id_offset=0, env=None, **task_over):
+    """env: cfg["env"] keys to override (episodeLength); task_over: keys of randomization_params to override."""
     from isaacgym_amd.tasks import isaacgym_task_map
     cfg = scene.default_task_cfg(scene.TASK_VARIANTS[name])
-    cfg["env"]["numEnvs"], cfg["seed"] = n, seed
+    cfg["env"]["numEnvs"], cfg["seed"], cfg["env_id_offset"] = n, seed, env_id_offset
+    cfg["env"].update(env or {})
     cfg["task"] = dict(randomize=True, randomization_params=dict(copy.deepcopy(block), **task_over))
     return isaacgym_task_map[name](cfg, "cuda:0", "cuda:0", -1, True, False, False)
 

@@ -576,45 +576,36 @@ def test_ta_oracle_randomisation_with_unit_tables_is_the_plain_step(oracle_lib):
     assert len(np.unique(both)) == both.size
 
 
-@pytest.mark.gpu
-def test_ta_chain_kernel_with_randomisation_matches_oracle(oracle_lib, monkeypatch):
-    """The table-reading instantiation of the chain-wave kernel (per-env drive gains, link masses, materials, action and observation noise)
-    against the oracle with the same tables (every env its own scaled copy of the model), restarted from the oracle's tensors every step; with
-    the randomisation cleared the plain kernel runs again, bit for bit."""
+def load_chain_state(e, root, dof, flags, episode, progress):
+    """The oracle's tensors into a TAEnv: what every step of the restarted comparisons begins from."""
     import torch
-    from isaacgym_amd.tensor_api import TAEnv
-    monkeypatch.setenv("PPENV_TA_KERNEL", "chain")
-    n = 640
-    cfg, m = scene.build_ta_scene(n), scene.build_ta_model()
-    env = TAEnv(n, device="cuda:0", seed=11, env={"episodeLength": 40}, materialize_rb=True)
-    ref = TAEnv(n, device="cuda:0", seed=11, env={"episodeLength": 40}, materialize_rb=True)
-    p = env.params
-    rng = np.random.default_rng(21)
-    tabs = _ta_dr_tables(n, rng)
-    kw = dict(action_noise_sigma=0.02, observation_noise_sigma=0.002)
-    env.set_randomization(**tabs, **kw)
-    root, dof = env.root_states.cpu().numpy().copy(), env.dof_states.cpu().numpy().copy()
-    irb = np.broadcast_to(env.initial_rb_states.cpu().numpy(), (1, 42, 13)).copy()
-    flags, episode, progress = np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int64)
-    oa = _ta_obs_atol() + 2e-6
-    log = ExclusionLog(f"gpu 27-dof chain-wave step with domain randomisation vs oracle [n={n}]", bound=0.005)
-    resets, moved = 0, 0.0
-    act = None
+    e.root_states.copy_(torch.from_numpy(root)); e.dof_states.copy_(torch.from_numpy(dof))
+    e.state.flags.copy_(torch.from_numpy(flags.view(np.int32))); e.state.episode.copy_(torch.from_numpy(episode.view(np.int32)))
+    e.state.progress_buf.copy_(torch.from_numpy(progress))
 
-    def load(e):
-        e.root_states.copy_(torch.from_numpy(root)); e.dof_states.copy_(torch.from_numpy(dof))
-        e.state.flags.copy_(torch.from_numpy(flags.view(np.int32))); e.state.episode.copy_(torch.from_numpy(episode.view(np.int32)))
-        e.state.progress_buf.copy_(torch.from_numpy(progress))
-    for t in range(70):
+
+def run_chain_dr_step_parity(oracle_lib, env, cfg, m, tabs, kw, label, steps, state, rng, after_step=None):
+    """A TAEnv on the table-reading chain-wave kernel against the oracle with the tables `tabs` and the noise amplitudes `kw` (every env its
+    own scaled copy of the model), restarted from the oracle's tensors every step.  state = [root, dof, flags, episode, progress] (numpy): where
+    the comparison starts; the arrays are advanced in place along the oracle's trajectory.  after_step(t, act): called between the kernel's
+    step t and the oracle's, while `state` still holds the step's start.  -> (resets, the last actions).  Used by
+    tests/test_dr_reset_tasks_gpu.py with the tables a task drew on the device."""
+    import torch
+    n, p = env.num_envs, env.params
+    root, dof, flags, episode, progress = state
+    irb = np.broadcast_to(env.initial_rb_states.cpu().numpy(), (1, 42, 13)).copy()
+    oa = _ta_obs_atol() + 2e-6
+    log = ExclusionLog(label, bound=0.005)
+    resets = 0
+    act = None
+    for t in range(steps):
         if t % 4 == 0:
             act = rng.uniform(-1.2, 1.2, (n, 27)).astype(np.float32)
             act[: n // 3] *= 0.1
-        load(env)
+        load_chain_state(env, root, dof, flags, episode, progress)
         env.step(torch.from_numpy(act).cuda())
-        if t == 10:                                                   # the plain kernel from the same state: the tables do something
-            load(ref)
-            ref.step(torch.from_numpy(act).cuda())
-            moved = float((ref.dof_states - env.dof_states).abs().max())
+        if after_step is not None:
+            after_step(t, act)
         root0, dof0, ep0, prog0 = root.copy(), dof.copy(), episode.copy(), progress.copy()
         rb, frc, pvx = oracle_lib.ta_simulate_dr(cfg, m, act, root, dof, ep0, prog0, seed=p.seed, env_id_offset=p.env_id_offset, threads=8,
                                                  action_noise_sigma=kw["action_noise_sigma"], **tabs)
@@ -656,10 +647,39 @@ def test_ta_chain_kernel_with_randomisation_matches_oracle(oracle_lib, monkeypat
         resets += int(reset.sum())
         flags[~keep] = g_flags[~keep]          # the kernel's flags of the excluded envs matched a sample above
     log.close()
-    assert resets >= n and moved > 1e-2
+    return resets, act
+
+
+@pytest.mark.gpu
+def test_ta_chain_kernel_with_randomisation_matches_oracle(oracle_lib, monkeypatch):
+    """The table-reading instantiation of the chain-wave kernel (per-env drive gains, link masses, materials, action and observation noise)
+    against the oracle with the same tables (every env its own scaled copy of the model), restarted from the oracle's tensors every step; with
+    the randomisation cleared the plain kernel runs again, bit for bit."""
+    import torch
+    from isaacgym_amd.tensor_api import TAEnv
+    monkeypatch.setenv("PPENV_TA_KERNEL", "chain")
+    n = 640
+    cfg, m = scene.build_ta_scene(n), scene.build_ta_model()
+    env = TAEnv(n, device="cuda:0", seed=11, env={"episodeLength": 40}, materialize_rb=True)
+    ref = TAEnv(n, device="cuda:0", seed=11, env={"episodeLength": 40}, materialize_rb=True)
+    rng = np.random.default_rng(21)
+    tabs = _ta_dr_tables(n, rng)
+    kw = dict(action_noise_sigma=0.02, observation_noise_sigma=0.002)
+    env.set_randomization(**tabs, **kw)
+    state = [env.root_states.cpu().numpy().copy(), env.dof_states.cpu().numpy().copy(), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros(n, np.int64)]
+    moved = [0.0]
+
+    def plain_step(t, act):
+        if t == 10:                                                   # the plain kernel from the same state: the tables do something
+            load_chain_state(ref, *state)
+            ref.step(torch.from_numpy(act).cuda())
+            moved[0] = float((ref.dof_states - env.dof_states).abs().max())
+    resets, act = run_chain_dr_step_parity(oracle_lib, env, cfg, m, tabs, kw, f"gpu 27-dof chain-wave step with domain randomisation vs oracle [n={n}]", 70, state,
+                                           rng, after_step=plain_step)
+    assert resets >= n and moved[0] > 1e-2
     # cleared: the plain kernel again, bit for bit
     env.clear_randomization()
-    load(env); load(ref)
+    load_chain_state(env, *state); load_chain_state(ref, *state)
     a = torch.from_numpy(act).cuda()
     env.step(a); ref.step(a)
     for name in ("root_states", "dof_states", "dof_force_tensor", "obs_buf", "rew_buf"):
