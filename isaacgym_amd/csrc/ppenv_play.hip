@@ -1,0 +1,130 @@
+// ppenv_play.hip — episode accounting for playing a checkpoint, on the device (include/ppenv_play.h).
+//
+// Bound by launch latency, not bytes: a control step moves 12-20 B per row.  Two launches per step, the shape of ppo_loss_grad_kernel /
+// ppo_loss_reduce_kernel:
+//   play_rows_kernel     lane e owns env e (256 envs per workgroup, ragged tail guarded): the per-env step of ppenv_play_device.h, then
+//                        the workgroup's finished games summed in a fixed order (xor butterfly within a wave, the four waves in order through
+//                        LDS) into ONE ppenv_play_partial.  Reads totals.games for the freeze; writes no word of the totals.
+//   play_totals_kernel   one wave: lane l sums partials l, l + 64, ... in order, a butterfly, lane 0 adds the result to the totals.
+// The totals are written by the second launch only, which has one workgroup: nothing a workgroup reads is written by another one in
+// the same launch, without atomics, tickets or device-scope fences (such a hand-off costs more than the launch boundary).
+//
+// -ffinite-math-only is NOT in this unit's flags (isaacgym_amd/_lib.py): the minima / maxima start at +-inf.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "ppenv_play_device.h"
+
+void ppenv_set_error(const char* msg);   // ppenv.hip
+
+namespace {
+
+constexpr int kBlock = PPENV_PLAY_BLOCK;
+constexpr int kWaves = kBlock / 64;
+
+inline int32_t blocks_of(int32_t n) { return (n + kBlock - 1) / kBlock; }
+
+// Every lane ends with the same partial: at each stage both partners form a + b and b + a, which are the same bits.
+__device__ __forceinline__ void wave_merge(ppenv_play_partial& p) {
+    #pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        ppenv_play_partial o;
+        o.games = __shfl_xor((long long)p.games, off, 64);
+        o.steps = __shfl_xor((long long)p.steps, off, 64);
+        #pragma unroll
+        for (int a = 0; a < PPENV_PLAY_MAX_AGENTS; ++a) {
+            o.reward[a] = __shfl_xor(p.reward[a], off, 64);
+            o.reward_sq[a] = __shfl_xor(p.reward_sq[a], off, 64);
+            o.reward_min[a] = __shfl_xor(p.reward_min[a], off, 64);
+            o.reward_max[a] = __shfl_xor(p.reward_max[a], off, 64);
+        }
+        pp::play_merge(p, o);
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void play_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t num_envs,
+                                                           int32_t num_agents, int64_t games_num, float* __restrict__ cur_reward,
+                                                           int32_t* __restrict__ cur_steps, const ppenv_play_totals* __restrict__ totals,
+                                                           ppenv_play_partial* __restrict__ partial) {
+    __shared__ ppenv_play_partial wave_part[kWaves];
+    if (pp::play_frozen(totals->games, games_num)) return;       // uniform: the whole grid leaves
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t e = (int32_t)(blockIdx.x * kBlock + tid);
+    ppenv_play_partial acc;
+    pp::play_clear(acc);
+    if (e < num_envs) pp::play_env(e, num_agents, rew, done, cur_reward, cur_steps, acc);
+    wave_merge(acc);
+    if (lane == 0) wave_part[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        ppenv_play_partial s = wave_part[0];
+        for (int w = 1; w < kWaves; ++w) pp::play_merge(s, wave_part[w]);
+        partial[blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void play_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
+                                                         ppenv_play_totals* __restrict__ totals) {
+    if (pp::play_frozen(totals->games, games_num)) return;       // the same word play_rows_kernel tested: nothing wrote it in between
+    ppenv_play_partial acc;
+    pp::play_clear(acc);
+    for (int32_t b = (int32_t)threadIdx.x; b < parts; b += 64) pp::play_merge(acc, partial[b]);
+    wave_merge(acc);
+    if (threadIdx.x == 0) {
+        ppenv_play_totals t = *totals;
+        pp::play_totals_add(t, acc);
+        *totals = t;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void play_reset_kernel(int32_t num_envs, int32_t rows, float* __restrict__ cur_reward, int32_t* __restrict__ cur_steps,
+                                                            ppenv_play_totals* __restrict__ totals) {
+    const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (i < rows) cur_reward[i] = 0.0f;
+    if (i < num_envs) cur_steps[i] = 0;
+    if (i == 0) {
+        ppenv_play_totals t;
+        pp::play_totals_clear(t);
+        *totals = t;
+    }
+}
+
+bool launched(const char* what) {
+    if (hipGetLastError() != hipSuccess) { ppenv_set_error(what); return false; }
+    return true;
+}
+
+bool sizes_ok(int32_t num_envs, int32_t num_agents) {
+    return num_envs > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS && (int64_t)num_envs * num_agents <= INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" size_t ppenv_play_partial_bytes(int32_t num_envs) {
+    return num_envs > 0 ? (size_t)blocks_of(num_envs) * sizeof(ppenv_play_partial) : 0;
+}
+
+extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
+    if (!sizes_ok(num_envs, num_agents) || !cur_reward || !cur_steps || !totals) {
+        ppenv_set_error("ppenv_play_reset: NULL pointer, num_envs <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
+        return PPENV_EINVAL;
+    }
+    const int32_t rows = num_envs * num_agents;
+    hipLaunchKernelGGL(play_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, cur_reward, cur_steps, totals);
+    return launched("launching play_reset_kernel failed") ? PPENV_OK : PPENV_EHIP;
+}
+
+extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int32_t num_envs, int32_t num_agents, int64_t games_num, float* cur_reward,
+                                     int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
+    if (!sizes_ok(num_envs, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+        ppenv_set_error("ppenv_play_accumulate: NULL pointer, num_envs <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, or games_num < 1");
+        return PPENV_EINVAL;
+    }
+    const int32_t parts = blocks_of(num_envs);
+    hipLaunchKernelGGL(play_rows_kernel, dim3(parts), dim3(kBlock), 0, (hipStream_t)stream, rew, done, num_envs, num_agents, games_num, cur_reward,
+                       cur_steps, totals, partial);
+    if (!launched("launching play_rows_kernel failed")) return PPENV_EHIP;
+    hipLaunchKernelGGL(play_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
+    return launched("launching play_totals_kernel failed") ? PPENV_OK : PPENV_EHIP;
+}

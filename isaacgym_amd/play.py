@@ -1,0 +1,256 @@
+"""Play a checkpoint: the reference's `test=true` (train.py:210-215: `runner.run({'train': not cfg.test, 'play': cfg.test, 'checkpoint': ...,
+'sigma': ...})`), on the native env and network, with the episode accounting on the device (C ABI: include/ppenv_play.h).
+
+    Player(task, policy, games_num=2000).run()      games_num episodes of `task` under `policy` -> rl_games' numbers (average return,
+                                                    average episode length) plus spread
+    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth
+
+Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
+per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
+(`all_done_indices[::num_agents]`: an env of the two-agent task counts once, on agent 0's row), their returns and lengths go into the
+sums and the running values restart at zero; the loop ends after the step in which games_played >= games_num, every env that finished
+in that step counted.  `av_reward` is agent 0's, as in rl_games.
+
+rl_games reads `done.nonzero()` on the host every step.  Here `EpisodeStats.accumulate` does the accounting in two small launches per
+control step and the host reads one 72-byte struct every `poll_every` steps, only to decide when to stop.  The result does not depend
+on `poll_every`: once games_num games are counted the kernel changes nothing (the freeze, include/ppenv_play.h), so the totals are
+those of the step at which the host-synchronised loop would have stopped.
+
+The player drives `task.step(actions)` — the VecTask surface rl_games' player drives — so action clamping, clipObservations,
+controlFrequencyInv and both domain-randomisation modes behave as for any caller; a task with `randomize: True` plays under its
+randomisation (evaluation; PPOTrainer's refusal of such a task is about training below that surface and is untouched).
+
+Out of scope: capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
+`Runner` / `player_factory` shim (rl_games itself is absent); video capture; the observer, PBT and W&B hooks.
+"""
+import argparse
+import ctypes as C
+import math
+import time
+
+import torch
+
+from . import _lib
+
+MAX_AGENTS = 2                             # PPENV_PLAY_MAX_AGENTS
+
+
+class PlayTotals(C.Structure):
+    """ctypes mirror of ppenv_play_totals (include/ppenv_play.h)."""
+    _fields_ = [("games", C.c_int64), ("steps", C.c_int64), ("launches", C.c_int64),
+                ("reward", C.c_double * MAX_AGENTS), ("reward_sq", C.c_double * MAX_AGENTS),
+                ("reward_min", C.c_float * MAX_AGENTS), ("reward_max", C.c_float * MAX_AGENTS)]
+
+
+def totals_dict(t, num_agents=MAX_AGENTS):
+    """PlayTotals -> a Python dict (the per-agent fields as lists of num_agents)."""
+    return dict(games=int(t.games), steps=int(t.steps), launches=int(t.launches), reward=list(t.reward)[:num_agents],
+                reward_sq=list(t.reward_sq)[:num_agents], reward_min=list(t.reward_min)[:num_agents], reward_max=list(t.reward_max)[:num_agents])
+
+
+def _lib_play():
+    L = _lib.lib()
+    if getattr(L, "_play_bound", False):
+        return L
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.ppenv_play_partial_bytes.restype = C.c_size_t
+    L.ppenv_play_partial_bytes.argtypes = [i32]
+    L.ppenv_play_reset.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.ppenv_play_accumulate.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    L._play_bound = True
+    return L
+
+
+def summarize(totals, num_agents=1):
+    """The result-dict arithmetic from a totals dict (EpisodeStats.read()): rl_games' av reward = sum_rewards / games_played (agent 0's)
+    and av steps = sum_steps / games_played, plus the population standard deviation sqrt(max(E[x^2] - E[x]^2, 0)), minimum and maximum of
+    the games' returns; `per_agent`: the four reward figures for each agent.  With no game counted the averages are nan."""
+    g = int(totals["games"])
+    per_agent = []
+    for a in range(num_agents):
+        if g > 0:
+            mean = totals["reward"][a] / g
+            std = math.sqrt(max(totals["reward_sq"][a] / g - mean * mean, 0.0))
+        else:
+            mean = std = float("nan")
+        per_agent.append(dict(av_reward=mean, reward_std=std, reward_min=float(totals["reward_min"][a]), reward_max=float(totals["reward_max"][a])))
+    out = dict(games=g, av_steps=totals["steps"] / g if g > 0 else float("nan"))
+    out.update(per_agent[0])
+    out["per_agent"] = per_agent
+    return out
+
+
+class EpisodeStats:
+    """ppenv_play_accumulate / ppenv_play_reset on torch tensors: `cur_reward` [num_envs * num_agents] f32, `cur_steps` [num_envs] i32 and
+    the totals struct, all on `device`.  Nothing here synchronises except read()."""
+
+    def __init__(self, num_envs, num_agents, games_num, device):
+        self.num_envs, self.num_agents, self.games_num = int(num_envs), int(num_agents), int(games_num)
+        if self.num_envs < 1 or self.num_agents not in (1, 2) or self.games_num < 1:
+            raise ValueError(f"EpisodeStats: num_envs {num_envs} (>= 1), num_agents {num_agents} (1 or 2), games_num {games_num} (>= 1)")
+        self.device = torch.device(device)
+        self.rows = self.num_envs * self.num_agents
+        L = self.L = _lib_play()
+        dev = self.device
+        self.cur_reward = torch.zeros(self.rows, dtype=torch.float32, device=dev)
+        self.cur_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self._totals = torch.zeros(C.sizeof(PlayTotals), dtype=torch.uint8, device=dev)
+        self._partial = torch.zeros(int(L.ppenv_play_partial_bytes(self.num_envs)), dtype=torch.uint8, device=dev)
+        o = PlayTotals
+        self._counts = self._totals[:o.reward.offset].view(torch.int64)                           # games, steps, launches
+        self._sums = self._totals[o.reward.offset:o.reward_min.offset].view(torch.float64)        # reward[2], reward_sq[2]
+        self._ext = self._totals[o.reward_min.offset:].view(torch.float32)                        # reward_min[2], reward_max[2]
+        self.reset()
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def reset(self):
+        _lib.check(self.L.ppenv_play_reset(self.num_envs, self.num_agents, self.cur_reward.data_ptr(), self.cur_steps.data_ptr(),
+                                           self._totals.data_ptr(), self._stream()), self.L)
+
+    def accumulate(self, rew, done):
+        """One control step, after the env step: rew [rows] f32, done [rows] int64 (VecTask.step's rew_buf / reset_buf, or a [rows] slice
+        of larger buffers), contiguous, on this device.  Two launches, no synchronisation."""
+        if rew.dtype != torch.float32 or done.dtype != torch.int64 or rew.numel() != self.rows or done.numel() != self.rows or \
+                not rew.is_contiguous() or not done.is_contiguous() or rew.device != self.device or done.device != self.device:
+            raise ValueError(f"EpisodeStats.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
+        _lib.check(self.L.ppenv_play_accumulate(rew.data_ptr(), done.data_ptr(), self.num_envs, self.num_agents, self.games_num,
+                                                self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self._totals.data_ptr(),
+                                                self._partial.data_ptr(), self._stream()), self.L)
+
+    def totals(self):
+        """The totals as 0-dim device tensors (views: they change in place with every accumulate): games, steps, launches, agent 0's
+        reward / reward_sq / reward_min / reward_max, and the same four per agent under `per_agent`."""
+        A = MAX_AGENTS
+        agents = [dict(reward=self._sums[a], reward_sq=self._sums[A + a], reward_min=self._ext[a], reward_max=self._ext[A + a])
+                  for a in range(self.num_agents)]
+        return dict(games=self._counts[0], steps=self._counts[1], launches=self._counts[2], per_agent=agents, **agents[0])
+
+    def read(self):
+        """One host copy of the struct (the stream is waited for) -> totals_dict."""
+        raw = self._totals.cpu().numpy().tobytes()
+        return totals_dict(PlayTotals.from_buffer_copy(raw), self.num_agents)
+
+    def state_bytes(self):
+        """cur_reward, cur_steps and the totals as host bytes (the tests compare them)."""
+        return self.cur_reward.cpu().numpy().tobytes(), self.cur_steps.cpu().numpy().tobytes(), self._totals.cpu().numpy().tobytes()
+
+
+class Player:
+    """rl_games' BasePlayer.run on a task from isaacgym_amd.make(...) (any of the five registry names; the 4-actor task has two rows per
+    env) under an RLGamesPolicy.  The defaults are rl_games' player defaults.
+    sigma: train.py:214's override — the policy's log-std is filled with it, so sigma = exp(x) (rl_games' _override_sigma for a fixed
+    sigma); it matters only with deterministic=False."""
+
+    def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None):
+        for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
+            if int(v) != v or int(v) < 1:
+                raise ValueError(f"{name}: {v!r} is not a positive integer")
+        rl, sim = torch.device(task.rl_device), torch.device(task.device)
+        if rl != sim or sim.type != "cuda":
+            raise ValueError(f"Player needs rl_device == sim_device on a GPU (no per-step copies): rl_device is {rl}, sim_device is {sim}")
+        if torch.device(policy.device) != sim:
+            raise ValueError(f"the policy lives on {policy.device}, the task on {sim}")
+        if policy.net.num_obs != task.num_obs or policy.net.num_actions != task.num_actions:
+            raise ValueError(f"the policy maps {policy.net.num_obs} observations to {policy.net.num_actions} actions, the task has "
+                             f"{task.num_obs} and {task.num_actions}")
+        self.task, self.policy = task, policy
+        self.games_num, self.poll_every, self.max_steps = int(games_num), int(poll_every), int(max_steps)
+        self.deterministic, self.seed = bool(deterministic), int(seed)
+        self.num_agents = int(getattr(task, "num_agents", 1))
+        if sigma is not None:
+            policy.sigma.fill_(math.exp(float(sigma)))
+        self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
+        self.steps_played = 0
+        self.actions = None
+        self._obs = None
+
+    def start(self):
+        """Every env to the start of an episode, the accounting to zero, the action-draw counter to zero (a run is a function of the seed)."""
+        self.task.reset_idx()
+        self.stats.reset()
+        self.policy._counter = 0
+        self._obs = self.task.reset()["obs"]
+        self.steps_played = 0
+
+    def step(self):
+        """One control step: policy -> task.step -> accumulate.  No host read."""
+        if self._obs is None:
+            self.start()
+        self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
+        obs, rew, done, _ = self.task.step(self.actions)
+        self.stats.accumulate(rew, done)
+        self._obs = obs["obs"]
+        self.steps_played += 1
+
+    def run(self, on_poll=None):
+        """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
+        host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds)."""
+        self.start()
+        t0 = time.perf_counter()
+        tot = None
+        while self.steps_played < self.max_steps:
+            self.step()
+            tot = None
+            if self.steps_played % self.poll_every == 0:
+                tot = self.stats.read()
+                if on_poll is not None:
+                    on_poll(tot)
+                if tot["games"] >= self.games_num:
+                    break
+        if tot is None:
+            tot = self.stats.read()
+            if on_poll is not None:
+                on_poll(tot)
+        out = summarize(tot, self.num_agents)
+        out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
+        return out
+
+
+# ---- CLI --------------------------------------------------------------------------------------------------------------------------
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.play", description="play a checkpoint (rl_games' player) on the native env and network")
+    ap.add_argument("--task", default="HumanoidPingpongTiltNESSparse27DOFG1")
+    ap.add_argument("--checkpoint", required=True, help="nn/<task>.pth as python -m isaacgym_amd.ppo (or rl_games) writes it")
+    ap.add_argument("--num-envs", type=int, default=4096)
+    ap.add_argument("--games", type=int, default=2000, help="rl_games' games_num")
+    ap.add_argument("--stochastic", action="store_true", help="draw the actions from Normal(mu, sigma) instead of playing mu")
+    ap.add_argument("--sigma", type=float, default=None, help="override the log-std with this value (train.py:214); sigma = exp(value)")
+    ap.add_argument("--seed", type=int, default=42)
+    ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task yaml from")
+    ap.add_argument("--poll-every", type=int, default=64, help="control steps between two host reads of the totals")
+    ap.add_argument("--max-steps", type=int, default=108000)
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import isaacgym_amd
+    from .policy import RLGamesPolicy
+    task_cfg = None
+    if args.cfg_dir:
+        from . import cfgyaml
+        task_cfg = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})["task"]
+    task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
+    policy = RLGamesPolicy.load(args.checkpoint, task.device)
+    pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
+                max_steps=args.max_steps, sigma=args.sigma)
+    last = dict(games=0, steps=0, reward=[0.0])
+
+    def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
+        n = tot["games"] - last["games"]
+        if n > 0:
+            print(f"reward: {(tot['reward'][0] - last['reward'][0]) / n} steps: {(tot['steps'] - last['steps']) / n}", flush=True)
+        last.update(games=tot["games"], steps=tot["steps"], reward=list(tot["reward"]))
+
+    res = pl.run(on_poll=on_poll)
+    print(f"av reward: {res['av_reward']} av steps: {res['av_steps']}")
+    for a, p in enumerate(res["per_agent"]):
+        print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
+    print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
+    return res
+
+
+if __name__ == "__main__":
+    main()

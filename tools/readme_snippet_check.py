@@ -17,3 +17,15 @@ for _ in range(100):
     obs, rew, done, info = env.step(actions)
     tot += float(rew.mean())
 print("ok", obs["obs"].shape, float(values.mean()), tot, int(done.sum()))
+# ... and the Player snippet (a synthetic checkpoint for the 7-dof task; a short episode so that 200 games finish within tens of steps)
+from isaacgym_amd import scene
+from isaacgym_amd.play import Player
+sd = _rlgames_state_dict(torch, 80, (2048, 1536, 1024, 1024, 512, 512), 7, torch.Generator().manual_seed(0))
+import tempfile
+ckpt_tt = os.path.join(tempfile.mkdtemp(prefix="readme_snippet_"), "HumanoidPingpongTiltG1.pth")
+torch.save({"model": sd}, ckpt_tt)
+cfg = scene.default_task_cfg("TT")
+cfg["env"]["episodeLength"] = 12
+player = Player(isaacgym_amd.make(task="HumanoidPingpongTiltG1", num_envs=4096, cfg=cfg), RLGamesPolicy.load(ckpt_tt, "cuda:0"), games_num=200)
+result = player.run()
+print("ok", result["games"], result["av_reward"], result["av_steps"], result["steps_played"])
