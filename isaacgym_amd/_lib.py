@@ -1,4 +1,4 @@
-"""Loader of the HIP library `isaacgym_amd/lib/libppenv.so` (C ABI: include/ppenv.h).
+"""Loader of the HIP library `isaacgym_amd/lib/libppenv.so` and the one ctypes binding of its C ABI (include/*.h): `load()`.
 
 There is no CPU fallback: if the library is missing or does not load, importing the
 environment fails loudly.  `build()` compiles it with hipcc for gfx950 (cross-compiles
@@ -10,6 +10,8 @@ import shutil
 import subprocess
 import tempfile
 from concurrent.futures import ThreadPoolExecutor
+
+import torch
 
 from . import scene
 
@@ -32,6 +34,68 @@ _lib = None
 
 class PPEnvError(RuntimeError):
     pass
+
+
+# ---- ctypes mirrors of the structs load() binds (policy, ppo and play re-export theirs; include/ppenv.h's and ppenv_dr.h's live in scene)
+class MLPLayer(C.Structure):
+    """ctypes mirror of ppenv_mlp_layer (include/ppenv_policy.h)."""
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("batch", C.c_int32),
+                ("in_", C.c_void_p), ("in_stride", C.c_int64), ("lda", C.c_int32), ("in_f32", C.c_int32),
+                ("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float),
+                ("w", C.c_void_p), ("w_stride", C.c_int64), ("ldw", C.c_int32),
+                ("bias", C.c_void_p), ("bias_stride", C.c_int64), ("elu", C.c_int32),
+                ("out", C.c_void_p), ("out_stride", C.c_int64), ("ldo", C.c_int32), ("out_f32", C.c_int32)]
+
+
+class MLPDw(C.Structure):
+    """ctypes mirror of ppenv_mlp_dw (include/ppenv_policy.h)."""
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("batch", C.c_int32),
+                ("dz", C.c_void_p), ("dz_stride", C.c_int64), ("lddz", C.c_int32),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("ldx", C.c_int32),
+                ("dw", C.c_void_p), ("dw_stride", C.c_int64), ("lddw", C.c_int32),
+                ("accumulate", C.c_int32), ("splits", C.c_int32),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class MLPCast(C.Structure):
+    """ctypes mirror of ppenv_mlp_cast (include/ppenv_policy.h)."""
+    _fields_ = [("w32", C.c_void_p), ("n", C.c_int32), ("k", C.c_int32), ("ldw32", C.c_int32),
+                ("w16", C.c_void_p), ("ldw16", C.c_int32),
+                ("wt16", C.c_void_p), ("ldwt16", C.c_int32), ("wt_rows", C.c_int32)]
+
+
+class PPOLossArgs(C.Structure):
+    """ctypes mirror of ppenv_ppo_loss_args (include/ppenv_ppo.h)."""
+    _fields_ = [("m", C.c_int32), ("a", C.c_int32),
+                ("mu", C.c_void_p), ("ld_mu", C.c_int32), ("value", C.c_void_p), ("ld_value", C.c_int32),
+                ("actions", C.c_void_p), ("ld_actions", C.c_int32), ("old_mu", C.c_void_p), ("ld_old_mu", C.c_int32),
+                ("old_sigma", C.c_void_p), ("old_neglogp", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p),
+                ("returns", C.c_void_p), ("logstd", C.c_void_p),
+                ("e_clip", C.c_float), ("critic_coef", C.c_float), ("bounds_loss_coef", C.c_float), ("soft_bound", C.c_float),
+                ("entropy_coef", C.c_float), ("clip_value", C.c_int32), ("scale", C.c_void_p),
+                ("d_head", C.c_void_p), ("ld_d_head", C.c_int32), ("d_logstd", C.c_void_p), ("stats", C.c_void_p), ("partial", C.c_void_p)]
+
+
+class PPOTensor(C.Structure):
+    """ctypes mirror of ppenv_ppo_tensor."""
+    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("ld_p", C.c_int32), ("ld_g", C.c_int32)]
+
+
+class PPOAdam(C.Structure):
+    """ctypes mirror of ppenv_ppo_adam."""
+    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("max_norm", C.c_float), ("truncate", C.c_int32),
+                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32), ("world", C.c_int32)]
+
+
+MAX_AGENTS = 2                             # PPENV_PLAY_MAX_AGENTS
+
+
+class PlayTotals(C.Structure):
+    """ctypes mirror of ppenv_play_totals (include/ppenv_play.h)."""
+    _fields_ = [("games", C.c_int64), ("steps", C.c_int64), ("launches", C.c_int64),
+                ("reward", C.c_double * MAX_AGENTS), ("reward_sq", C.c_double * MAX_AGENTS),
+                ("reward_min", C.c_float * MAX_AGENTS), ("reward_max", C.c_float * MAX_AGENTS)]
 
 
 def is_stale():
@@ -125,16 +189,21 @@ def lib():
 
 
 def load(path):
-    """A libppenv build with its argtypes set (lib() for the default one; build_for_arm_model's output for another arm)."""
+    """A libppenv build with EVERY function of include/*.h bound (lib() for the default one; build_for_arm_model's or build_for_ta_model's
+    output for another model).  This is the only place that sets argtypes / restype: an unbound function would take a device pointer
+    as a C int and truncate it without an error."""
     try:
         L = C.CDLL(path)
     except OSError as e:
         raise PPEnvError(f"could not load {path}: {e}") from e
+    L.ppenv_abi_version.argtypes = []
     if L.ppenv_abi_version() != scene.ABI_VERSION:
         raise PPEnvError("libppenv.so ABI version does not match isaacgym_amd.scene; rebuild the library")
-    vp, sz = C.c_void_p, C.c_size_t
-    cfgp = C.POINTER(scene.Config)
+    vp, sz, i32, i64, u64, f32 = C.c_void_p, C.c_size_t, C.c_int32, C.c_int64, C.c_uint64, C.c_float
+    cfgp, layerp = C.POINTER(scene.Config), C.POINTER(MLPLayer)
+    # ---- include/ppenv.h
     L.ppenv_last_error.restype = C.c_char_p
+    L.ppenv_last_error.argtypes = []
     L.ppenv_arena_bytes.restype = sz
     L.ppenv_arena_bytes.argtypes = [cfgp]
     L.ppenv_create.argtypes = [cfgp, vp, sz, vp, C.POINTER(vp)]
@@ -144,28 +213,28 @@ def load(path):
     L.ppenv_config_of.argtypes = [vp, cfgp]
     L.ppenv_step.argtypes = [vp, vp, vp]
     L.ppenv_step_into.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.ppenv_step_sequence.argtypes = [vp, vp, C.c_int32, vp]
+    L.ppenv_step_sequence.argtypes = [vp, vp, i32, vp]
     L.ppenv_reset_all.argtypes = [vp, vp]
     L.ppenv_reduce_stats.argtypes = [vp, vp, vp]
-    L.ppenv_reset_idx.argtypes = [vp, vp, C.c_int32, C.c_int, vp]
+    L.ppenv_reset_idx.argtypes = [vp, vp, i32, C.c_int, vp]
     L.ppenv_pd_targets.argtypes = [vp, vp, vp, vp]
-    L.ppenv_serve_from_draws.argtypes = [vp, vp, C.c_int32, vp, vp]
+    L.ppenv_serve_from_draws.argtypes = [vp, vp, i32, vp, vp]
     L.ppenv_set_randomization.argtypes = [vp, C.POINTER(scene.Randomization)]
-    L.ppenv_set_gravity.argtypes = [vp, C.c_float]
+    L.ppenv_set_gravity.argtypes = [vp, f32]
     L.ppenv_status.restype = C.c_uint32
     L.ppenv_status.argtypes = [vp]
     L.ppenv_step_kernel_name.restype = C.c_char_p
     L.ppenv_step_kernel_name.argtypes = [vp]
-    L.ppenv_ta_sim_set_gravity.argtypes = [vp, C.c_float, vp]
+    L.ppenv_ta_sim_set_gravity.argtypes = [vp, f32, vp]
     L.ppenv_ta_sim_kernel_name.restype = C.c_char_p
     L.ppenv_ta_sim_kernel_name.argtypes = [vp]
-    L.ppenv_ta_pd_targets.argtypes = [vp, C.c_int32, vp, vp, vp]
-    L.ppenv_ta_serve_from_draws.argtypes = [vp, vp, C.c_int32, vp, vp]
+    L.ppenv_ta_pd_targets.argtypes = [vp, i32, vp, vp, vp]
+    L.ppenv_ta_serve_from_draws.argtypes = [vp, vp, i32, vp, vp]
     L.ppenv_ta_sim_device.argtypes = [vp]
     L.ppenv_ta_sim_status.restype = C.c_uint32
     L.ppenv_ta_sim_status.argtypes = [vp]
     L.ppenv_ta_sim_kernel.argtypes = [vp]
-    L.ppenv_ta_sim_set_policy_input.argtypes = [vp, vp, vp, C.c_float, vp, C.c_int32]
+    L.ppenv_ta_sim_set_policy_input.argtypes = [vp, vp, vp, f32, vp, i32]
     L.ppenv_ta_sim_set_randomization.argtypes = [vp, C.POINTER(scene.Randomization)]
     L.ppenv_ta_model_is_compiled.argtypes = [cfgp, C.POINTER(scene.TAModel)]
     L.ppenv_post_physics_step.argtypes = [vp, vp, vp, vp, vp, vp, vp]
@@ -178,19 +247,65 @@ def load(path):
     L.ppenv_ta_sim_create.argtypes = [cfgp, C.POINTER(scene.TAModel), vp, C.POINTER(vp)]
     L.ppenv_ta_sim_destroy.restype = None
     L.ppenv_ta_sim_destroy.argtypes = [vp]
-    L.ppenv_ta_simulate.argtypes = [vp, C.c_int32] + [vp] * 7
-    L.ppenv_ta_forward_kinematics.argtypes = [vp, C.c_int32] + [vp] * 4
+    L.ppenv_ta_simulate.argtypes = [vp, i32] + [vp] * 7
+    L.ppenv_ta_forward_kinematics.argtypes = [vp, i32] + [vp] * 4
     L.ppenv_ta_step.argtypes = [vp, C.POINTER(scene.TAParams)] + [vp] * 16
     L.ppenv_state_bytes.restype = sz
     L.ppenv_state_bytes.argtypes = [vp]
     L.ppenv_get_state.argtypes = [vp, vp, sz]
     L.ppenv_set_state.argtypes = [vp, vp, sz]
+    # ---- include/ppenv_dr.h
     L.ppenv_dr_state_bytes.restype = L.ppenv_dr_state_draws_offset.restype = sz
-    L.ppenv_dr_state_bytes.argtypes = L.ppenv_dr_state_draws_offset.argtypes = [C.c_int32]
+    L.ppenv_dr_state_bytes.argtypes = L.ppenv_dr_state_draws_offset.argtypes = [i32]
     L.ppenv_dr_plan_upload.argtypes = [C.POINTER(scene.DRPlan), vp, vp]
-    L.ppenv_dr_apply.argtypes = [vp, C.c_int32, vp, vp, vp, vp]
-    L.ppenv_dr_apply_ids.argtypes = [vp, C.c_int32, vp, C.c_int32, vp, vp, vp]
+    L.ppenv_dr_apply.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.ppenv_dr_apply_ids.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    # ---- include/ppenv_policy.h
+    L.ppenv_mlp_layer_forward.argtypes = [layerp, vp]
+    L.ppenv_mlp_layer_forward_share.argtypes = [layerp, i32, vp]
+    L.ppenv_mlp_chain_workspace_bytes.restype = sz
+    L.ppenv_mlp_chain_workspace_bytes.argtypes = [i32, i32, i32]
+    L.ppenv_mlp_chain_forward.argtypes = [layerp, i32, vp, vp]
+    L.ppenv_mlp_chain_status.argtypes = [vp]
+    L.ppenv_mlp_prepare_input.argtypes = [vp, i32, i32, i32, vp, vp, f32, vp, i32, vp]
+    L.ppenv_mlp_sample_actions.argtypes = [vp, i32, i32, i32, vp, u64, u64, f32, f32, vp, vp, vp]
+    L.ppenv_mlp_heads_sample.argtypes = [layerp, i32, vp, u64, u64, f32, f32, vp, vp, vp]
+    L.ppenv_gae.argtypes = [vp, vp, i32, i64, vp, i32, i32, f32, f32, f32, vp, vp, vp]
+    L.ppenv_mlp_layer_backward_input.argtypes = [layerp, vp, i64, i32, vp, i64, i32, vp]
+    L.ppenv_mlp_dw_workspace_bytes.restype = sz
+    L.ppenv_mlp_dw_workspace_bytes.argtypes = [C.POINTER(MLPDw)]
+    L.ppenv_mlp_layer_backward_weight.argtypes = [C.POINTER(MLPDw), vp]
+    L.ppenv_mlp_reduce_rows.argtypes = [vp, i32, i64, i64, vp, i32, vp]
+    L.ppenv_mlp_bias_grad_workspace_bytes.restype = sz
+    L.ppenv_mlp_bias_grad_workspace_bytes.argtypes = [i32, i32]
+    L.ppenv_mlp_bias_grad_f32.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp]
+    L.ppenv_mlp_cast_weights.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
+    L.ppenv_mlp_cast_weights_batch.argtypes = [C.POINTER(MLPCast), i32, vp]
+    L.ppenv_running_mean_std_workspace_bytes.restype = sz
+    L.ppenv_running_mean_std_workspace_bytes.argtypes = [i32, i32]
+    L.ppenv_running_mean_std_update.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, f32, vp, vp]
+    # ---- include/ppenv_ppo.h
+    L.ppenv_ppo_loss_partial_floats.restype = sz
+    L.ppenv_ppo_loss_partial_floats.argtypes = [i32]
+    L.ppenv_ppo_loss_grad.argtypes = [C.POINTER(PPOLossArgs), vp]
+    L.ppenv_ppo_grad_sumsq.argtypes = [vp, i32, vp, i32, vp]
+    L.ppenv_ppo_adam_step.argtypes = [vp, i32, vp, i32, PPOAdam, vp, vp, vp, vp]
+    # ---- include/ppenv_play.h
+    L.ppenv_play_partial_bytes.restype = sz
+    L.ppenv_play_partial_bytes.argtypes = [i32]
+    L.ppenv_play_reset.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.ppenv_play_accumulate.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     return L
+
+
+def stream(x):
+    """The raw handle of torch's current stream on the device of `x` (a tensor or a device): what every launch's `stream` argument gets."""
+    return torch.cuda.current_stream(getattr(x, "device", x)).cuda_stream
+
+
+def ptr(t):
+    """A tensor's device address, or None (a NULL pointer) for None."""
+    return t.data_ptr() if t is not None else None
 
 
 def check(rc, L=None):

@@ -19,7 +19,6 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .policy import _lib_policy
 
 
 def gae(rewards, values, dones, gamma=0.99, tau=0.95, reward_scale=1.0, advantages=None, returns=None):
@@ -29,8 +28,8 @@ def gae(rewards, values, dones, gamma=0.99, tau=0.95, reward_scale=1.0, advantag
     assert values.shape[0] == h + 1 and values.shape[1] == n and dones.dtype == torch.int64 and rewards.is_contiguous() and dones.is_contiguous()
     adv = torch.empty_like(rewards) if advantages is None else advantages
     ret = torch.empty_like(rewards) if returns is None else returns
-    _lib.check(_lib_policy().ppenv_gae(rewards.data_ptr(), values.data_ptr(), values.stride(1), values.stride(0), dones.data_ptr(), h, n, gamma, tau,
-                                       reward_scale, adv.data_ptr(), ret.data_ptr(), torch.cuda.current_stream(rewards.device).cuda_stream))
+    _lib.check(_lib.lib().ppenv_gae(rewards.data_ptr(), values.data_ptr(), values.stride(1), values.stride(0), dones.data_ptr(), h, n, gamma, tau,
+                                    reward_scale, adv.data_ptr(), ret.data_ptr(), _lib.stream(rewards)))
     return adv, ret
 
 

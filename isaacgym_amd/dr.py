@@ -1,5 +1,6 @@
-"""Reset-time, per-env domain randomisation drawn on the device (include/ppenv_dr.h): the tables, the uploaded plan and the state
-block of one environment handle, and the two launches.  The reference's rule — an env's actor parameters are redrawn when THAT env
+"""Per-env domain randomisation of an environment handle.  `Randomizable` is the surface PPEnv and TASim share: the tables a caller
+hands over, the noise amplitudes, and the reset-time plan.  `ResetRandomizer` is reset-time randomisation drawn on the device
+(include/ppenv_dr.h): the tables, the uploaded plan and the state block of one environment handle, and the two launches.  The reference's rule — an env's actor parameters are redrawn when THAT env
 resets (tasks/humanoid_pingpong_3_actor_tilt.py:849-850, 1025; upstream VecTask.apply_randomizations) — without a host round trip.
 torch owns the memory, as it owns the environments' arenas; the library rewrites table columns in place."""
 import ctypes as C
@@ -34,17 +35,14 @@ class ResetRandomizer:
         self.draws = self.state[off:].view(torch.int32)                               # [N] redraws each env has had
         self.randomize_buf = torch.zeros(n, dtype=torch.int64, device=self.device)    # the reference's attribute: control steps since the env's last redraw
         with torch.cuda.device(self.device):
-            _lib.check(L.ppenv_dr_plan_upload(C.byref(host), self.plan_dev.data_ptr(), self._stream()), L)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+            _lib.check(L.ppenv_dr_plan_upload(C.byref(host), self.plan_dev.data_ptr(), _lib.stream(self.device)), L)
 
     def apply(self, reset_buf):
         """One control step of the rule (ppenv_dr_apply), after the step that wrote reset_buf [reset_rows * N] int64.  One launch, no
         synchronisation."""
         assert reset_buf.dtype == torch.int64 and reset_buf.is_contiguous() and reset_buf.numel() == self.reset_rows * self.num_envs
         _lib.check(self.L.ppenv_dr_apply(self.plan_dev.data_ptr(), self.num_envs, reset_buf.data_ptr(), self.randomize_buf.data_ptr(),
-                                         self.state.data_ptr(), self._stream()), self.L)
+                                         self.state.data_ptr(), _lib.stream(self.device)), self.L)
 
     def apply_ids(self, env_ids):
         """The rule for the envs reset_idx(env_ids) lists (ppenv_dr_apply_ids); duplicates are dropped here (the kernel wants distinct ids)."""
@@ -52,5 +50,60 @@ class ResetRandomizer:
         if ids.numel() == 0:
             return
         _lib.check(self.L.ppenv_dr_apply_ids(self.plan_dev.data_ptr(), self.num_envs, ids.data_ptr(), ids.numel(), self.randomize_buf.data_ptr(),
-                                             self.state.data_ptr(), self._stream()), self.L)
+                                             self.state.data_ptr(), _lib.stream(self.device)), self.L)
         ids.record_stream(torch.cuda.current_stream(self.device))
+
+
+class Randomizable:
+    """The randomisation surface of an environment handle (PPEnv, TASim), which has `L`, `h`, `device` and `num_envs`.  The host class
+    supplies what differs: DR_TABLE_ROWS, DR_SETTER, the seed / env-id offset / reset_rows its set_reset_randomization passes on, and
+    the `reset_buf` apply_reset_randomization reads."""
+    DR_TABLE_ROWS = None      # {set_randomization name: rows of that table, 0 for a per-env scalar [N]}, in the order of scene.Randomization's pointers
+    DR_SETTER = None          # the C setter: "ppenv_set_randomization" / "ppenv_ta_sim_set_randomization"
+
+    def set_randomization(self, dof_stiffness_scale=None, dof_damping_scale=None, link_mass_scale=None, restitution_scale=None,
+                          friction_scale=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """Per-env domain-randomisation tables as float32 device tensors, [DR_TABLE_ROWS[name], N] or [N] (None = not randomised), and
+        the two noise amplitudes.  The tensors are kept alive here and read by every following step; rewriting them in place changes
+        the randomisation."""
+        def tab(t, rows):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous()
+            assert tuple(t.shape) == ((rows, self.num_envs) if rows else (self.num_envs,)), tuple(t.shape)
+            return t
+        given = (dof_stiffness_scale, dof_damping_scale, link_mass_scale, restitution_scale, friction_scale)
+        self._dr = [tab(t, rows) for t, rows in zip(given, self.DR_TABLE_ROWS.values())]
+        r = scene.Randomization()      # ppenv_ta_randomization has the fields of ppenv_randomization
+        for name, t in zip(self.DR_TABLE_ROWS, self._dr):
+            setattr(r, name, _lib.ptr(t))
+        r.action_noise_sigma, r.observation_noise_sigma = float(action_noise_sigma), float(observation_noise_sigma)
+        _lib.check(getattr(self.L, self.DR_SETTER)(self.h, C.byref(r)), self.L)
+
+    def _set_reset_randomization(self, plan, seed, env_id_offset, reset_rows, action_noise_sigma, observation_noise_sigma):
+        """What the host's set_reset_randomization does once it has filled in its defaults: the plan's tables are allocated — 1 for a
+        scaling, 0 for an additive term until an env's first redraw — and handed to set_randomization with the two noise amplitudes.
+        -> the ResetRandomizer (tables, randomize_buf, draws), also kept as `reset_randomization`."""
+        rr = ResetRandomizer(self.L, self.device, self.num_envs, plan, self.DR_TABLE_ROWS, seed=seed, env_id_offset=env_id_offset, reset_rows=reset_rows)
+        self.set_randomization(**rr.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+        self.reset_randomization = rr
+        return rr
+
+    def set_noise_sigmas(self, action_noise_sigma=0.0, observation_noise_sigma=0.0):
+        """The two noise amplitudes alone, over the tables of set_reset_randomization (they stay the same tensors)."""
+        self.set_randomization(**self.reset_randomization.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+
+    def apply_reset_randomization(self, env_ids=None):
+        """The per-step launch (ppenv_dr_apply on the host's reset_buf); env_ids: the id variant, for reset_idx(env_ids)."""
+        rr = getattr(self, "reset_randomization", None)
+        if rr is None:
+            raise _lib.PPEnvError("apply_reset_randomization: no plan is set (set_reset_randomization)")
+        if env_ids is None:
+            rr.apply(self.reset_buf)
+        else:
+            rr.apply_ids(env_ids)
+
+    def clear_randomization(self):
+        _lib.check(getattr(self.L, self.DR_SETTER)(self.h, None), self.L)
+        self._dr = None
+        self.reset_randomization = None

@@ -11,9 +11,10 @@ import numpy as np
 import torch
 
 from . import _lib, scene
+from .dr import Randomizable
 
 
-class PPEnv:
+class PPEnv(Randomizable):
     def __init__(self, config, device=None, library=None):
         """library: a libppenv build other than the default one (_lib.load of _lib.build_for_arm_model's output: another arm
         model compiled in); the handle then only ever talks to that build."""
@@ -31,7 +32,7 @@ class PPEnv:
         self.arena = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
         self.h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self.L.ppenv_create(C.byref(config), self.arena.data_ptr(), nbytes, self._stream(), C.byref(self.h)), self.L)
+            _lib.check(self.L.ppenv_create(C.byref(config), self.arena.data_ptr(), nbytes, _lib.stream(self.device), C.byref(self.h)), self.L)
         b = scene.Buffers()
         _lib.check(self.L.ppenv_buffers_of(self.h, C.byref(b)), self.L)
         base = self.arena.data_ptr()
@@ -56,9 +57,6 @@ class PPEnv:
         self.flags = view(b.flags, A * n, torch.int32, (n,) if A == 1 else (A, n))
         self.episode = view(b.episode, n, torch.int32, (n,))
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
             torch.cuda.synchronize(self.device)
@@ -80,12 +78,12 @@ class PPEnv:
                 or tuple(actions.shape) != (self.num_rows, scene.NUM_DOF):
             actions = actions.to(device=self.device, dtype=torch.float32).reshape(self.num_rows, scene.NUM_DOF).contiguous()
         if obs is None and rew is None and reset is None:
-            _lib.check(self.L.ppenv_step(self.h, actions.data_ptr(), self._stream()), self.L)
+            _lib.check(self.L.ppenv_step(self.h, actions.data_ptr(), _lib.stream(self.device)), self.L)
             return
         for t, dt, numel in ((obs, torch.float32, self.num_rows * scene.NUM_OBS), (rew, torch.float32, self.num_rows), (reset, torch.int64, self.num_rows)):
             assert t is None or (t.dtype == dt and t.is_contiguous() and t.device == self.device and t.numel() == numel)
-        p = lambda t: t.data_ptr() if t is not None else None
-        _lib.check(self.L.ppenv_step_into(self.h, actions.data_ptr(), p(obs), p(rew), p(reset), self._stream()), self.L)
+        p = _lib.ptr
+        _lib.check(self.L.ppenv_step_into(self.h, actions.data_ptr(), p(obs), p(rew), p(reset), _lib.stream(self.device)), self.L)
 
     def step_sequence(self, actions_list):
         """ppenv_step_sequence: one fused step per tensor of `actions_list` (float32 [A*N, 7], contiguous, on this device), launched back to back by one
@@ -94,10 +92,10 @@ class PPEnv:
         for a in actions_list:
             assert a.dtype == torch.float32 and a.device == self.device and a.is_contiguous() and tuple(a.shape) == (self.num_rows, scene.NUM_DOF)
         arr = (C.c_void_p * len(actions_list))(*[a.data_ptr() for a in actions_list])
-        _lib.check(self.L.ppenv_step_sequence(self.h, arr, len(actions_list), self._stream()), self.L)
+        _lib.check(self.L.ppenv_step_sequence(self.h, arr, len(actions_list), _lib.stream(self.device)), self.L)
 
     def reset_all(self):
-        _lib.check(self.L.ppenv_reset_all(self.h, self._stream()), self.L)
+        _lib.check(self.L.ppenv_reset_all(self.h, _lib.stream(self.device)), self.L)
 
     def reset_idx(self, env_ids, refresh_obs=True):
         """reset_idx(env_ids) -> _reset_idx (TT:809-812, 847-906) for the listed local env ids only (int64 tensor / sequence)."""
@@ -108,40 +106,25 @@ class PPEnv:
             if int(ids.min()) < 0 or int(ids.max()) >= self.num_envs:
                 raise IndexError(f"env id outside [0, {self.num_envs})")
         ids = ids.to(self.device).contiguous()
-        _lib.check(self.L.ppenv_reset_idx(self.h, ids.data_ptr(), ids.numel(), int(bool(refresh_obs)), self._stream()), self.L)
+        _lib.check(self.L.ppenv_reset_idx(self.h, ids.data_ptr(), ids.numel(), int(bool(refresh_obs)), _lib.stream(self.device)), self.L)
         ids.record_stream(torch.cuda.current_stream(self.device))   # the kernel reads `ids` after this frame is gone
 
     def pd_targets(self, actions):
         """pre_physics_step's PD targets (TT:1008-1014) for actions [A*N, 7]: what set_dof_position_target_tensor receives."""
         a = actions.to(device=self.device, dtype=torch.float32).reshape(self.num_rows, scene.NUM_DOF).contiguous()
         out = torch.empty_like(a)
-        _lib.check(self.L.ppenv_pd_targets(self.h, a.data_ptr(), out.data_ptr(), self._stream()), self.L)
+        _lib.check(self.L.ppenv_pd_targets(self.h, a.data_ptr(), out.data_ptr(), _lib.stream(self.device)), self.L)
         return out
 
     def serve_from_draws(self, draws):
         """generate_random_speed_for_ball of this variant on [M,3] draws (speed, tilt deg, tilt_z deg) -> [M,3] velocities."""
         d = torch.as_tensor(draws, dtype=torch.float32).to(self.device).reshape(-1, 3).contiguous()
         out = torch.empty_like(d)
-        _lib.check(self.L.ppenv_serve_from_draws(self.h, d.data_ptr(), d.shape[0], out.data_ptr(), self._stream()), self.L)
+        _lib.check(self.L.ppenv_serve_from_draws(self.h, d.data_ptr(), d.shape[0], out.data_ptr(), _lib.stream(self.device)), self.L)
         return out
 
-    def set_randomization(self, dof_stiffness_scale=None, dof_damping_scale=None, link_mass_scale=None, restitution_scale=None,
-                          friction_scale=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
-        """Per-env domain-randomisation tables (ppenv_set_randomization): float32 device tensors [7, N] / [N] (None = not randomised).
-        The tensors are kept alive here and read by every following step; rewriting them in place changes the randomisation."""
-        def tab(t, rows):
-            if t is None:
-                return None
-            t = torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous()
-            assert tuple(t.shape) == ((rows, self.num_envs) if rows else (self.num_envs,)), tuple(t.shape)
-            return t
-        self._dr = [tab(dof_stiffness_scale, 7), tab(dof_damping_scale, 7), tab(link_mass_scale, 7), tab(restitution_scale, 0), tab(friction_scale, 0)]
-        r = scene.Randomization()
-        (r.dof_stiffness_scale, r.dof_damping_scale, r.link_mass_scale, r.restitution_scale, r.friction_scale) = [t.data_ptr() if t is not None else None for t in self._dr]
-        r.action_noise_sigma, r.observation_noise_sigma = float(action_noise_sigma), float(observation_noise_sigma)
-        _lib.check(self.L.ppenv_set_randomization(self.h, C.byref(r)), self.L)
-
     DR_TABLE_ROWS = {"dof_stiffness_scale": 7, "dof_damping_scale": 7, "link_mass_scale": 7, "restitution_scale": 0, "friction_scale": 0}
+    DR_SETTER = "ppenv_set_randomization"
 
     def set_reset_randomization(self, plan, seed=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
         """Reset-time randomisation, the reference's rule (TT:849-850, 1025; include/ppenv_dr.h): `plan` (scene.reset_randomization_plan
@@ -149,31 +132,8 @@ class PPEnv:
         until an env's first redraw — and handed to set_randomization together with the two noise amplitudes; from then on
         apply_reset_randomization(), once after every step, redraws the columns of the envs that reset.  seed: default the handle's.
         -> the ResetRandomizer (tables, randomize_buf, draws)."""
-        from .dr import ResetRandomizer
-        rr = ResetRandomizer(self.L, self.device, self.num_envs, plan, self.DR_TABLE_ROWS, seed=self.config.seed if seed is None else seed,
-                             env_id_offset=self.config.env_id_offset, reset_rows=self.num_agents)
-        self.set_randomization(**rr.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
-        self.reset_randomization = rr
-        return rr
-
-    def set_noise_sigmas(self, action_noise_sigma=0.0, observation_noise_sigma=0.0):
-        """The two noise amplitudes alone, over the tables of set_reset_randomization (they stay the same tensors)."""
-        self.set_randomization(**self.reset_randomization.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
-
-    def apply_reset_randomization(self, env_ids=None):
-        """The per-step launch (ppenv_dr_apply on this handle's reset_buf); env_ids: the id variant, for reset_idx(env_ids)."""
-        rr = getattr(self, "reset_randomization", None)
-        if rr is None:
-            raise _lib.PPEnvError("apply_reset_randomization: no plan is set (set_reset_randomization)")
-        if env_ids is None:
-            rr.apply(self.reset_buf)
-        else:
-            rr.apply_ids(env_ids)
-
-    def clear_randomization(self):
-        _lib.check(self.L.ppenv_set_randomization(self.h, None), self.L)
-        self._dr = None
-        self.reset_randomization = None
+        return self._set_reset_randomization(plan, self.config.seed if seed is None else seed, self.config.env_id_offset, self.num_agents,
+                                             action_noise_sigma, observation_noise_sigma)
 
     def set_gravity(self, gravity_z):
         _lib.check(self.L.ppenv_set_gravity(self.h, float(gravity_z)), self.L)
@@ -195,7 +155,7 @@ class PPEnv:
                 self._stats = torch.zeros(4, dtype=torch.float64, device=self.device)
             out = self._stats
         assert out.dtype == torch.float64 and out.numel() == 4 and out.device == self.device and out.is_contiguous()
-        _lib.check(self.L.ppenv_reduce_stats(self.h, out.data_ptr(), self._stream()), self.L)
+        _lib.check(self.L.ppenv_reduce_stats(self.h, out.data_ptr(), _lib.stream(self.device)), self.L)
         return out
 
     # ---- Isaac-Gym tensor-API mode
@@ -206,11 +166,11 @@ class PPEnv:
         assert rigid_body_states.numel() == n * scene.NUM_BODIES * 13 and root_states.numel() == n * scene.NUM_ACTORS * 13
         assert dof_states.numel() == n * scene.NUM_DOF * 2 and dof_force.numel() == n * scene.NUM_DOF and pre_ball_vx.numel() == n
         _lib.check(self.L.ppenv_post_physics_step(self.h, rigid_body_states.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(),
-                                                  dof_force.data_ptr(), pre_ball_vx.data_ptr(), self._stream()), self.L)
+                                                  dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.stream(self.device)), self.L)
 
     def _refresh(self, fn, shape):
         out = torch.empty(shape, dtype=torch.float32, device=self.device)
-        _lib.check(fn(self.h, out.data_ptr(), self._stream()), self.L)
+        _lib.check(fn(self.h, out.data_ptr(), _lib.stream(self.device)), self.L)
         return out
 
     def refresh_root_states(self):
@@ -229,10 +189,10 @@ class PPEnv:
     def set_serve_override(self, serve, on=True):
         """serve: [N,3] tensor/array of serve velocities used at the next resets instead of the RNG."""
         if serve is None or not on:
-            _lib.check(self.L.ppenv_set_serve_override(self.h, None, int(bool(on)), self._stream()), self.L)
+            _lib.check(self.L.ppenv_set_serve_override(self.h, None, int(bool(on)), _lib.stream(self.device)), self.L)
             return
         s = torch.as_tensor(serve, dtype=torch.float32).to(self.device).reshape(self.num_envs, 3).contiguous()
-        _lib.check(self.L.ppenv_set_serve_override(self.h, s.data_ptr(), 1, self._stream()), self.L)
+        _lib.check(self.L.ppenv_set_serve_override(self.h, s.data_ptr(), 1, _lib.stream(self.device)), self.L)
         torch.cuda.current_stream(self.device).synchronize()   # `s` must outlive the transpose kernel
 
     def get_state(self):

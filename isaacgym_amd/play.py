@@ -31,34 +31,13 @@ import time
 import torch
 
 from . import _lib
-
-MAX_AGENTS = 2                             # PPENV_PLAY_MAX_AGENTS
-
-
-class PlayTotals(C.Structure):
-    """ctypes mirror of ppenv_play_totals (include/ppenv_play.h)."""
-    _fields_ = [("games", C.c_int64), ("steps", C.c_int64), ("launches", C.c_int64),
-                ("reward", C.c_double * MAX_AGENTS), ("reward_sq", C.c_double * MAX_AGENTS),
-                ("reward_min", C.c_float * MAX_AGENTS), ("reward_max", C.c_float * MAX_AGENTS)]
+from ._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ctypes mirror of ppenv_play_totals (bound in _lib.load)
 
 
 def totals_dict(t, num_agents=MAX_AGENTS):
     """PlayTotals -> a Python dict (the per-agent fields as lists of num_agents)."""
     return dict(games=int(t.games), steps=int(t.steps), launches=int(t.launches), reward=list(t.reward)[:num_agents],
                 reward_sq=list(t.reward_sq)[:num_agents], reward_min=list(t.reward_min)[:num_agents], reward_max=list(t.reward_max)[:num_agents])
-
-
-def _lib_play():
-    L = _lib.lib()
-    if getattr(L, "_play_bound", False):
-        return L
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    L.ppenv_play_partial_bytes.restype = C.c_size_t
-    L.ppenv_play_partial_bytes.argtypes = [i32]
-    L.ppenv_play_reset.argtypes = [i32, i32, vp, vp, vp, vp]
-    L.ppenv_play_accumulate.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
-    L._play_bound = True
-    return L
 
 
 def summarize(totals, num_agents=1):
@@ -90,7 +69,7 @@ class EpisodeStats:
             raise ValueError(f"EpisodeStats: num_envs {num_envs} (>= 1), num_agents {num_agents} (1 or 2), games_num {games_num} (>= 1)")
         self.device = torch.device(device)
         self.rows = self.num_envs * self.num_agents
-        L = self.L = _lib_play()
+        L = self.L = _lib.lib()
         dev = self.device
         self.cur_reward = torch.zeros(self.rows, dtype=torch.float32, device=dev)
         self.cur_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
@@ -102,12 +81,9 @@ class EpisodeStats:
         self._ext = self._totals[o.reward_min.offset:].view(torch.float32)                        # reward_min[2], reward_max[2]
         self.reset()
 
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
     def reset(self):
         _lib.check(self.L.ppenv_play_reset(self.num_envs, self.num_agents, self.cur_reward.data_ptr(), self.cur_steps.data_ptr(),
-                                           self._totals.data_ptr(), self._stream()), self.L)
+                                           self._totals.data_ptr(), _lib.stream(self.device)), self.L)
 
     def accumulate(self, rew, done):
         """One control step, after the env step: rew [rows] f32, done [rows] int64 (VecTask.step's rew_buf / reset_buf, or a [rows] slice
@@ -117,7 +93,7 @@ class EpisodeStats:
             raise ValueError(f"EpisodeStats.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
         _lib.check(self.L.ppenv_play_accumulate(rew.data_ptr(), done.data_ptr(), self.num_envs, self.num_agents, self.games_num,
                                                 self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self._totals.data_ptr(),
-                                                self._partial.data_ptr(), self._stream()), self.L)
+                                                self._partial.data_ptr(), _lib.stream(self.device)), self.L)
 
     def totals(self):
         """The totals as 0-dim device tensors (views: they change in place with every accumulate): games, steps, launches, agent 0's

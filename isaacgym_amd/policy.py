@@ -19,86 +19,25 @@ import os
 import torch
 
 from . import _lib
+from ._lib import MLPCast, MLPDw, MLPLayer     # the ctypes mirrors of include/ppenv_policy.h (bound in _lib.load)
 
 UNITS = [2048, 1536, 1024, 1024, 512, 512]     # cfg/train/HumanoidPingpongTiltG1PPO.yaml:29
-
-
-class MLPLayer(C.Structure):
-    """ctypes mirror of ppenv_mlp_layer (include/ppenv_policy.h)."""
-    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("batch", C.c_int32),
-                ("in_", C.c_void_p), ("in_stride", C.c_int64), ("lda", C.c_int32), ("in_f32", C.c_int32),
-                ("mean", C.c_void_p), ("inv_std", C.c_void_p), ("clip", C.c_float),
-                ("w", C.c_void_p), ("w_stride", C.c_int64), ("ldw", C.c_int32),
-                ("bias", C.c_void_p), ("bias_stride", C.c_int64), ("elu", C.c_int32),
-                ("out", C.c_void_p), ("out_stride", C.c_int64), ("ldo", C.c_int32), ("out_f32", C.c_int32)]
-
-
-class MLPDw(C.Structure):
-    """ctypes mirror of ppenv_mlp_dw (include/ppenv_policy.h)."""
-    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("k", C.c_int32), ("batch", C.c_int32),
-                ("dz", C.c_void_p), ("dz_stride", C.c_int64), ("lddz", C.c_int32),
-                ("x", C.c_void_p), ("x_stride", C.c_int64), ("ldx", C.c_int32),
-                ("dw", C.c_void_p), ("dw_stride", C.c_int64), ("lddw", C.c_int32),
-                ("accumulate", C.c_int32), ("splits", C.c_int32),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
-
-
-class MLPCast(C.Structure):
-    """ctypes mirror of ppenv_mlp_cast (include/ppenv_policy.h)."""
-    _fields_ = [("w32", C.c_void_p), ("n", C.c_int32), ("k", C.c_int32), ("ldw32", C.c_int32),
-                ("w16", C.c_void_p), ("ldw16", C.c_int32),
-                ("wt16", C.c_void_p), ("ldwt16", C.c_int32), ("wt_rows", C.c_int32)]
-
-
-def _lib_policy():
-    L = _lib.lib()
-    if getattr(L, "_policy_bound", False):
-        return L
-    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
-    L.ppenv_mlp_layer_backward_input.argtypes = [C.POINTER(MLPLayer), vp, i64, i32, vp, i64, i32, vp]
-    L.ppenv_mlp_dw_workspace_bytes.restype = C.c_size_t
-    L.ppenv_mlp_dw_workspace_bytes.argtypes = [C.POINTER(MLPDw)]
-    L.ppenv_mlp_layer_backward_weight.argtypes = [C.POINTER(MLPDw), vp]
-    L.ppenv_mlp_reduce_rows.argtypes = [vp, i32, i64, i64, vp, i32, vp]
-    L.ppenv_mlp_bias_grad_workspace_bytes.restype = C.c_size_t
-    L.ppenv_mlp_bias_grad_workspace_bytes.argtypes = [i32, i32]
-    L.ppenv_mlp_bias_grad_f32.argtypes = [vp, i32, i32, i32, vp, vp, i32, vp]
-    L.ppenv_mlp_cast_weights.argtypes = [vp, i32, i32, i32, vp, i32, vp, i32, i32, vp]
-    L.ppenv_mlp_cast_weights_batch.argtypes = [C.POINTER(MLPCast), i32, vp]
-    L.ppenv_running_mean_std_workspace_bytes.restype = C.c_size_t
-    L.ppenv_running_mean_std_workspace_bytes.argtypes = [i32, i32]
-    L.ppenv_running_mean_std_update.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, C.c_float, vp, vp]
-    L._policy_bound = True
-    L.ppenv_mlp_layer_forward.argtypes = [C.POINTER(MLPLayer), C.c_void_p]
-    L.ppenv_mlp_layer_forward_share.argtypes = [C.POINTER(MLPLayer), C.c_int32, C.c_void_p]
-    L.ppenv_mlp_chain_workspace_bytes.restype = C.c_size_t
-    L.ppenv_mlp_chain_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    L.ppenv_mlp_chain_forward.argtypes = [C.POINTER(MLPLayer), C.c_int32, C.c_void_p, C.c_void_p]
-    L.ppenv_mlp_chain_status.argtypes = [C.c_void_p]
-    L.ppenv_mlp_prepare_input.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int32, C.c_void_p]
-    L.ppenv_gae.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ppenv_mlp_heads_sample.argtypes = [C.POINTER(MLPLayer), C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.ppenv_mlp_sample_actions.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_float,
-                                           C.c_void_p, C.c_void_p, C.c_void_p]
-    return L
 
 
 def sample_actions(actions, mu, sigma, seed, counter, lo=-1.0, hi=1.0, neglogp=None):
     """ppenv_mlp_sample_actions on torch tensors: actions [M, A] = clamp(mu + sigma * N(0, 1), lo, hi), neglogp [M] of the unclamped
     draw (rl_games a2c_continuous with fixed sigma); deterministic in (seed, counter)."""
-    L = _lib_policy()
+    L = _lib.lib()
     assert actions.is_contiguous() and mu.stride(1) == 1 and sigma.is_contiguous()
     _lib.check(L.ppenv_mlp_sample_actions(mu.data_ptr(), mu.shape[0], mu.shape[1], mu.stride(0), sigma.data_ptr(), seed, counter, lo, hi,
-                                          actions.data_ptr(), neglogp.data_ptr() if neglogp is not None else None,
-                                          torch.cuda.current_stream(mu.device).cuda_stream))
+                                          actions.data_ptr(), _lib.ptr(neglogp), _lib.stream(mu)))
 
 
 def prepare_input(out, obs, mean=None, inv_std=None, clip=5.0):
     """ppenv_mlp_prepare_input on torch tensors: obs fp32 [M, K] -> out fp16 [M, Kpad] normalised, clamped, zero-padded."""
-    L = _lib_policy()
-    _lib.check(L.ppenv_mlp_prepare_input(obs.data_ptr(), obs.shape[0], obs.shape[1], obs.stride(0), mean.data_ptr() if mean is not None else None,
-                                         inv_std.data_ptr() if inv_std is not None else None, clip, out.data_ptr(), out.stride(0),
-                                         torch.cuda.current_stream(obs.device).cuda_stream))
+    L = _lib.lib()
+    _lib.check(L.ppenv_mlp_prepare_input(obs.data_ptr(), obs.shape[0], obs.shape[1], obs.stride(0), _lib.ptr(mean), _lib.ptr(inv_std), clip,
+                                         out.data_ptr(), out.stride(0), _lib.stream(obs)))
 
 
 def _descriptor(out, x, w, bias, elu, batch=1, in_stride=0, w_stride=0, bias_stride=0, out_stride=0, mean=None, inv_std=None, clip=5.0,
@@ -109,11 +48,10 @@ def _descriptor(out, x, w, bias, elu, batch=1, in_stride=0, w_stride=0, bias_str
     d.k = (w.shape[-1] if k is None else k)
     d.batch = batch
     d.in_, d.in_stride, d.lda, d.in_f32 = x.data_ptr(), in_stride, x.stride(0), int(x.dtype == torch.float32)
-    d.mean = mean.data_ptr() if mean is not None else None
-    d.inv_std = inv_std.data_ptr() if inv_std is not None else None
+    d.mean, d.inv_std = _lib.ptr(mean), _lib.ptr(inv_std)
     d.clip = clip
     d.w, d.w_stride, d.ldw = w.data_ptr(), w_stride, w.stride(-2)
-    d.bias, d.bias_stride = (bias.data_ptr() if bias is not None else None), bias_stride
+    d.bias, d.bias_stride = _lib.ptr(bias), bias_stride
     d.elu = int(elu)
     d.out, d.out_stride, d.ldo, d.out_f32 = out.data_ptr(), out_stride, out.stride(0), int(out.dtype == torch.float32)
     return d
@@ -124,14 +62,14 @@ def layer_forward(out, x, w, bias, elu, cus=0, **kw):
     cus: size the grid for that many of the 256 CUs (ppenv_mlp_layer_forward_share; 0 = the whole chip)."""
     d = _descriptor(out, x, w, bias, elu, **kw)
     if cus:
-        _lib.check(_lib_policy().ppenv_mlp_layer_forward_share(C.byref(d), cus, torch.cuda.current_stream(x.device).cuda_stream))
+        _lib.check(_lib.lib().ppenv_mlp_layer_forward_share(C.byref(d), cus, _lib.stream(x)))
     else:
-        _lib.check(_lib_policy().ppenv_mlp_layer_forward(C.byref(d), torch.cuda.current_stream(x.device).cuda_stream))
+        _lib.check(_lib.lib().ppenv_mlp_layer_forward(C.byref(d), _lib.stream(x)))
 
 
 def chain_workspace(m, batch, count, device):
     """The zeroed workspace of ppenv_mlp_chain_forward for `count` chained layers of m rows x batch problems."""
-    n = _lib_policy().ppenv_mlp_chain_workspace_bytes(m, batch, count)
+    n = _lib.lib().ppenv_mlp_chain_workspace_bytes(m, batch, count)
     assert n > 0
     return torch.zeros((n + 3) // 4, dtype=torch.int32, device=device)
 
@@ -139,11 +77,11 @@ def chain_workspace(m, batch, count, device):
 def chain_forward(descriptors, workspace):
     """ppenv_mlp_chain_forward on a list of layer descriptors (_descriptor): consecutive hidden layers in one launch."""
     arr = (MLPLayer * len(descriptors))(*descriptors)
-    _lib.check(_lib_policy().ppenv_mlp_chain_forward(arr, len(descriptors), workspace.data_ptr(), torch.cuda.current_stream(workspace.device).cuda_stream))
+    _lib.check(_lib.lib().ppenv_mlp_chain_forward(arr, len(descriptors), workspace.data_ptr(), _lib.stream(workspace)))
 
 
 def chain_status(workspace):
-    return _lib_policy().ppenv_mlp_chain_status(workspace.data_ptr())
+    return _lib.lib().ppenv_mlp_chain_status(workspace.data_ptr())
 
 
 def heads_sample(out, x, w, bias, num_actions, actions, sigma, seed, counter, lo=-1.0, hi=1.0, neglogp=None):
@@ -151,17 +89,8 @@ def heads_sample(out, x, w, bias, num_actions, actions, sigma, seed, counter, lo
     sample_actions(actions, out[:, :num_actions], sigma, seed, counter, lo, hi, neglogp) would produce."""
     d = _descriptor(out, x, w, bias, False)
     assert actions.is_contiguous() and actions.shape[1] == num_actions and sigma.is_contiguous()
-    _lib.check(_lib_policy().ppenv_mlp_heads_sample(C.byref(d), num_actions, sigma.data_ptr(), seed, counter, lo, hi, actions.data_ptr(),
-                                                    neglogp.data_ptr() if neglogp is not None else None,
-                                                    torch.cuda.current_stream(x.device).cuda_stream))
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _ptr(t):
-    return t.data_ptr() if t is not None else None
+    _lib.check(_lib.lib().ppenv_mlp_heads_sample(C.byref(d), num_actions, sigma.data_ptr(), seed, counter, lo, hi, actions.data_ptr(),
+                                                 _lib.ptr(neglogp), _lib.stream(x)))
 
 
 def layer_backward_input(dx, dz, wt, elu_out=None, colsum_partial=None, batch=1, dz_stride=0, wt_stride=0, dx_stride=0, elu_out_stride=0,
@@ -170,9 +99,9 @@ def layer_backward_input(dx, dz, wt, elu_out=None, colsum_partial=None, batch=1,
     layer's input width, k = its output width, wt = its weights transposed; colsum_partial [ceil(M / 64), >= n] fp32 receives the
     per-64-row column sums of dx (the bias gradient of the layer below, once reduce_rows has summed them)."""
     d = _descriptor(dx, dz, wt, None, False, batch=batch, in_stride=dz_stride, w_stride=wt_stride, out_stride=dx_stride, m=m, n=n, k=k)
-    _lib.check(_lib_policy().ppenv_mlp_layer_backward_input(
-        C.byref(d), _ptr(elu_out), elu_out_stride, elu_out.stride(0) if elu_out is not None else 0,
-        _ptr(colsum_partial), colsum_stride, colsum_partial.stride(0) if colsum_partial is not None else 0, _stream(dz)))
+    _lib.check(_lib.lib().ppenv_mlp_layer_backward_input(
+        C.byref(d), _lib.ptr(elu_out), elu_out_stride, elu_out.stride(0) if elu_out is not None else 0,
+        _lib.ptr(colsum_partial), colsum_stride, colsum_partial.stride(0) if colsum_partial is not None else 0, _lib.stream(dz)))
 
 
 def _dw_descriptor(dw, dz, x, batch, dz_stride, x_stride, dw_stride, m, n, k, accumulate, splits, workspace):
@@ -182,14 +111,14 @@ def _dw_descriptor(dw, dz, x, batch, dz_stride, x_stride, dw_stride, m, n, k, ac
     d.x, d.x_stride, d.ldx = x.data_ptr(), x_stride, x.stride(0)
     d.dw, d.dw_stride, d.lddw = dw.data_ptr(), dw_stride, dw.stride(-2)
     d.accumulate, d.splits = int(accumulate), int(splits)
-    d.workspace, d.workspace_bytes = _ptr(workspace), (workspace.numel() * workspace.element_size() if workspace is not None else 0)
+    d.workspace, d.workspace_bytes = _lib.ptr(workspace), (workspace.numel() * workspace.element_size() if workspace is not None else 0)
     return d
 
 
 def dw_workspace_bytes(m, n, k, batch=1, splits=0):
     d = MLPDw()
     d.m, d.n, d.k, d.batch, d.splits = m, n, k, batch, splits
-    return int(_lib_policy().ppenv_mlp_dw_workspace_bytes(C.byref(d)))
+    return int(_lib.lib().ppenv_mlp_dw_workspace_bytes(C.byref(d)))
 
 
 def layer_backward_weight(dw, dz, x, batch=1, dz_stride=0, x_stride=0, dw_stride=0, m=None, n=None, k=None, accumulate=False, splits=0, workspace=None):
@@ -199,45 +128,45 @@ def layer_backward_weight(dw, dz, x, batch=1, dz_stride=0, x_stride=0, dw_stride
         need = dw_workspace_bytes(dz.shape[0] if m is None else m, dw.shape[-2] if n is None else n, dw.shape[-1] if k is None else k, batch, splits)
         workspace = torch.empty(max(need, 16), dtype=torch.uint8, device=dz.device)
     d = _dw_descriptor(dw, dz, x, batch, dz_stride, x_stride, dw_stride, m, n, k, accumulate, splits, workspace)
-    _lib.check(_lib_policy().ppenv_mlp_layer_backward_weight(C.byref(d), _stream(dz)))
+    _lib.check(_lib.lib().ppenv_mlp_layer_backward_weight(C.byref(d), _lib.stream(dz)))
 
 
 def reduce_rows(out, partial, rows=None, n=None, accumulate=False):
     """out [n] (+)= the sum of partial's first `rows` rows (fp32, in row order)."""
     rows = partial.shape[0] if rows is None else rows
     n = out.numel() if n is None else n
-    _lib.check(_lib_policy().ppenv_mlp_reduce_rows(partial.data_ptr(), rows, partial.stride(0), n, out.data_ptr(), int(accumulate), _stream(out)))
+    _lib.check(_lib.lib().ppenv_mlp_reduce_rows(partial.data_ptr(), rows, partial.stride(0), n, out.data_ptr(), int(accumulate), _lib.stream(out)))
 
 
 def bias_grad_f32(out, dz, accumulate=False, workspace=None):
     """out [n] fp32 (+)= column sums of dz [M, n] fp32 (the heads' bias gradient)."""
-    L = _lib_policy()
+    L = _lib.lib()
     m, n = dz.shape
     if workspace is None:
         workspace = torch.empty(int(L.ppenv_mlp_bias_grad_workspace_bytes(m, n)), dtype=torch.uint8, device=dz.device)
-    _lib.check(L.ppenv_mlp_bias_grad_f32(dz.data_ptr(), m, n, dz.stride(0), workspace.data_ptr(), out.data_ptr(), int(accumulate), _stream(dz)))
+    _lib.check(L.ppenv_mlp_bias_grad_f32(dz.data_ptr(), m, n, dz.stride(0), workspace.data_ptr(), out.data_ptr(), int(accumulate), _lib.stream(dz)))
 
 
 def cast_weights(w32, w16=None, wt16=None):
     """fp32 master weights [n, k] -> w16 [n, >= k] (zero-padded rows) and / or wt16 [>= k, >= n] = the transpose (zero-padded), fp16."""
     n, k = w32.shape
-    _lib.check(_lib_policy().ppenv_mlp_cast_weights(w32.data_ptr(), n, k, w32.stride(0), _ptr(w16), w16.stride(0) if w16 is not None else 0,
-                                                    _ptr(wt16), wt16.stride(0) if wt16 is not None else 0, wt16.shape[0] if wt16 is not None else 0, _stream(w32)))
+    _lib.check(_lib.lib().ppenv_mlp_cast_weights(w32.data_ptr(), n, k, w32.stride(0), _lib.ptr(w16), w16.stride(0) if w16 is not None else 0,
+                                                 _lib.ptr(wt16), wt16.stride(0) if wt16 is not None else 0, wt16.shape[0] if wt16 is not None else 0, _lib.stream(w32)))
 
 
 def cast_item(w32, w16=None, wt16=None):
     """One entry of a cast_weights_batch list (the tensors must stay alive and in place: the entry holds their addresses)."""
     it = MLPCast()
     it.w32, it.n, it.k, it.ldw32 = w32.data_ptr(), w32.shape[0], w32.shape[1], w32.stride(0)
-    it.w16, it.ldw16 = _ptr(w16), (w16.stride(0) if w16 is not None else 0)
-    it.wt16, it.ldwt16, it.wt_rows = _ptr(wt16), (wt16.stride(0) if wt16 is not None else 0), (wt16.shape[0] if wt16 is not None else 0)
+    it.w16, it.ldw16 = _lib.ptr(w16), (w16.stride(0) if w16 is not None else 0)
+    it.wt16, it.ldwt16, it.wt_rows = _lib.ptr(wt16), (wt16.stride(0) if wt16 is not None else 0), (wt16.shape[0] if wt16 is not None else 0)
     return it
 
 
 def cast_weights_batch(items, stream_of):
     """ppenv_mlp_cast_weights_batch: every matrix in `items` (cast_item entries, at most 32) in one launch."""
     arr = (MLPCast * len(items))(*items)
-    _lib.check(_lib_policy().ppenv_mlp_cast_weights_batch(arr, len(items), _stream(stream_of)))
+    _lib.check(_lib.lib().ppenv_mlp_cast_weights_batch(arr, len(items), _lib.stream(stream_of)))
 
 
 class RunningMeanStd(torch.nn.Module):
@@ -270,14 +199,14 @@ class RunningMeanStd(torch.nn.Module):
     def update(self, obs):
         """obs [M, num_obs] fp32 on the device: one pass; mean / inv_std are refreshed in place (a NativeMLP given these tensors by
         set_normalization_tensors sees the new statistics at its next forward)."""
-        L = _lib_policy()
+        L = _lib.lib()
         m, k = obs.shape
         assert obs.dtype == torch.float32 and obs.device == self.device and obs.stride(1) == 1 and k == self.num_obs
         if self._ws is None or self._ws_rows < m:
             self._ws = torch.zeros(int(L.ppenv_running_mean_std_workspace_bytes(m, k)) // 8 + 1, dtype=torch.float64, device=self.device)   # zeroed: the ticket
             self._ws_rows = m
         _lib.check(L.ppenv_running_mean_std_update(obs.data_ptr(), m, k, obs.stride(0), self.running_mean.data_ptr(), self.running_var.data_ptr(),
-                                                   self.count.data_ptr(), self.mean.data_ptr(), self.inv_std.data_ptr(), self.eps, self._ws.data_ptr(), _stream(obs)))
+                                                   self.count.data_ptr(), self.mean.data_ptr(), self.inv_std.data_ptr(), self.eps, self._ws.data_ptr(), _lib.stream(obs)))
 
 
 class NativeMLP:
@@ -286,7 +215,7 @@ class NativeMLP:
 
     def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, max_rows=None, fuse_input=False, cus=0):
         """cus: the share of the chip's 256 CUs each layer launch is sized for (0 = all): 128 when two env groups' forwards run side by
-        side on two streams (collector.PipelinedRollout); results do not depend on it.
+        side on two streams (tools/gpu_rollout_pipeline.py); results do not depend on it.
         fuse_input: layer 1 reads the fp32 observations in place and normalises while staging (one launch fewer, but the
         register-staged kernel); default: a small normalise-and-pad launch first, then layer 1 on the LDS-DMA kernel like the rest
         (M = 4096, 313 observations: 54 us fused, see DESIGN.md §5a for the split path)."""
@@ -308,7 +237,7 @@ class NativeMLP:
 
     def sibling(self, max_rows=None):
         """Another forward context on the SAME operand images and statistics (no copy: one set of weights in HBM / L2) with its own
-        activation buffers — one per env group when groups of envs are stepped on separate streams (collector.PipelinedRollout)."""
+        activation buffers — one per env group when groups of envs are stepped on separate streams (tools/gpu_rollout_pipeline.py)."""
         other = object.__new__(NativeMLP)
         other.__dict__.update({k: v for k, v in self.__dict__.items() if k not in ("h", "head_out", "mu", "value", "x16", "_rows", "_chain_ws")})
         other._rows, other._chain_ws = 0, None        # (the chain workspace belongs to one launch sequence: groups on separate streams each get their own)
@@ -531,7 +460,7 @@ class NativeMLPLearner:
         need = max([dw_workspace_bytes(m, 2 * u[0], self.net.w[0].shape[-1])] + [dw_workspace_bytes(m, u[i], u[i - 1], batch=2) for i in range(1, len(u))] +
                    [dw_workspace_bytes(m, self.nh, 2 * u[-1]), 16])
         self.ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        self.ws_b = torch.empty(int(_lib_policy().ppenv_mlp_bias_grad_workspace_bytes(m, self.net.num_actions + 1)) + 16, dtype=torch.uint8, device=dev)
+        self.ws_b = torch.empty(int(_lib.lib().ppenv_mlp_bias_grad_workspace_bytes(m, self.net.num_actions + 1)) + 16, dtype=torch.uint8, device=dev)
         self._rows = m
 
     def attach_running_mean_std(self, rms):

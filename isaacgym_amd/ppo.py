@@ -52,6 +52,7 @@ import torch
 
 from . import _lib
 from . import distributed as D
+from ._lib import PPOAdam, PPOLossArgs, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
 from .policy import UNITS, NativeActorCritic, RunningMeanStd
 
@@ -59,48 +60,6 @@ HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 STATS = ("loss", "a_loss", "c_loss", "b_loss", "entropy", "kl", "clip_frac")     # ppenv_ppo_loss_grad's stats[] (include/ppenv_ppo.h)
 SOFT_BOUND = 1.1                          # rl_games a2c_continuous.bound_loss
 OPT_PARTS = 512                           # workgroups of the optimizer launches: two per CU
-
-
-class PPOLossArgs(C.Structure):
-    """ctypes mirror of ppenv_ppo_loss_args (include/ppenv_ppo.h)."""
-    _fields_ = [("m", C.c_int32), ("a", C.c_int32),
-                ("mu", C.c_void_p), ("ld_mu", C.c_int32), ("value", C.c_void_p), ("ld_value", C.c_int32),
-                ("actions", C.c_void_p), ("ld_actions", C.c_int32), ("old_mu", C.c_void_p), ("ld_old_mu", C.c_int32),
-                ("old_sigma", C.c_void_p), ("old_neglogp", C.c_void_p), ("advantages", C.c_void_p), ("old_values", C.c_void_p),
-                ("returns", C.c_void_p), ("logstd", C.c_void_p),
-                ("e_clip", C.c_float), ("critic_coef", C.c_float), ("bounds_loss_coef", C.c_float), ("soft_bound", C.c_float),
-                ("entropy_coef", C.c_float), ("clip_value", C.c_int32), ("scale", C.c_void_p),
-                ("d_head", C.c_void_p), ("ld_d_head", C.c_int32), ("d_logstd", C.c_void_p), ("stats", C.c_void_p), ("partial", C.c_void_p)]
-
-
-class PPOTensor(C.Structure):
-    """ctypes mirror of ppenv_ppo_tensor."""
-    _fields_ = [("p", C.c_void_p), ("g", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
-                ("rows", C.c_int32), ("cols", C.c_int32), ("ld_p", C.c_int32), ("ld_g", C.c_int32)]
-
-
-class PPOAdam(C.Structure):
-    """ctypes mirror of ppenv_ppo_adam."""
-    _fields_ = [("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_float), ("max_norm", C.c_float), ("truncate", C.c_int32),
-                ("growth_factor", C.c_float), ("backoff_factor", C.c_float), ("growth_interval", C.c_int32), ("world", C.c_int32)]
-
-
-def _lib_ppo():
-    L = _lib.lib()
-    if getattr(L, "_ppo_bound", False):
-        return L
-    vp, i32 = C.c_void_p, C.c_int32
-    L.ppenv_ppo_loss_partial_floats.restype = C.c_size_t
-    L.ppenv_ppo_loss_partial_floats.argtypes = [i32]
-    L.ppenv_ppo_loss_grad.argtypes = [C.POINTER(PPOLossArgs), vp]
-    L.ppenv_ppo_grad_sumsq.argtypes = [vp, i32, vp, i32, vp]
-    L.ppenv_ppo_adam_step.argtypes = [vp, i32, vp, i32, PPOAdam, vp, vp, vp, vp]
-    L._ppo_bound = True
-    return L
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 # ---- configuration ----------------------------------------------------------------------------------------------------------------
@@ -246,7 +205,7 @@ class LossGrad:
         dev = torch.device(device)
         self.d_head = torch.zeros((max_rows, self.a + 1), dtype=torch.float32, device=dev)
         self.d_logstd = torch.zeros(self.a, dtype=torch.float32, device=dev) if d_logstd is None else d_logstd     # the optimizer's gradient buffer
-        self.partial = torch.zeros(int(_lib_ppo().ppenv_ppo_loss_partial_floats(max_rows)), dtype=torch.float32, device=dev)
+        self.partial = torch.zeros(int(_lib.lib().ppenv_ppo_loss_partial_floats(max_rows)), dtype=torch.float32, device=dev)
 
     def __call__(self, mu, value, actions, old_mu, old_sigma, old_neglogp, advantages, old_values, returns, logstd, scale, stats):
         """mu / actions / old_mu [M, >= A] fp32 with unit column stride (any row stride); value [M, 1] (any row stride); old_sigma / logstd [A];
@@ -262,7 +221,7 @@ class LossGrad:
                         old_values.data_ptr(), returns.data_ptr(), logstd.data_ptr(), c.e_clip, c.critic_coef, c.bounds_loss_coef, SOFT_BOUND,
                         c.entropy_coef, int(c.clip_value), scale.data_ptr(), self.d_head.data_ptr(), self.d_head.stride(0),
                         self.d_logstd.data_ptr(), stats.data_ptr(), self.partial.data_ptr())
-        _lib.check(_lib_ppo().ppenv_ppo_loss_grad(C.byref(p), _stream(mu)))
+        _lib.check(_lib.lib().ppenv_ppo_loss_grad(C.byref(p), _lib.stream(mu)))
         return self.d_head[:m]
 
 
@@ -322,8 +281,8 @@ class DeviceAdam:
         return dict(scale=s[0:1].view(torch.float32)[0], growth_tracker=s[1], step=s[2], skipped=s[3], grad_norm=s[4:5].view(torch.float32)[0])
 
     def step(self):
-        L = _lib_ppo()
-        st = _stream(self.slab)
+        L = _lib.lib()
+        st = _lib.stream(self.slab)
         _lib.check(L.ppenv_ppo_grad_sumsq(self.table.data_ptr(), self.count, self.slab.data_ptr(), self.parts, st))
         _lib.check(L.ppenv_ppo_adam_step(self.table.data_ptr(), self.count, self.slab.data_ptr(), self.parts, self.hp, self.lr.data_ptr(),
                                          self.state[self.cur].data_ptr(), self.state[1 - self.cur].data_ptr(), st))

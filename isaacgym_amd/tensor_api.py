@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib, scene
+from .dr import Randomizable
 
 
 class TAState:
@@ -42,18 +43,17 @@ class TAState:
         ov = None
         if reset_override is not None:
             ov = reset_override.to(self.device, torch.float32).reshape(n, 5).contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
         # (the library launches on the device that owns obs_buf, whatever the caller's current device is)
         self._ck(self.L.ppenv_ta_post_physics_step(
             C.byref(self.params), rb_states.data_ptr(), initial_rb_states.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(),
-            dof_force.data_ptr(), pre_ball_vx.data_ptr(), ov.data_ptr() if ov is not None else None, self.flags.data_ptr(),
+            dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.ptr(ov), self.flags.data_ptr(),
             self.episode.data_ptr(), self.progress_buf.data_ptr(), self.obs_buf.data_ptr(), self.rew_buf.data_ptr(),
-            self.reset_buf.data_ptr(), self._any_reset.data_ptr(), stream))
+            self.reset_buf.data_ptr(), self._any_reset.data_ptr(), _lib.stream(self.device)))
         if ov is not None:
             torch.cuda.current_stream(self.device).synchronize()   # keep `ov` alive until the kernel has read it
 
 
-class TASim:
+class TASim(Randomizable):
     """pre_physics_step + gym.simulate + refresh for the 27-DoF task (TA:1124-1143, 1150) on Isaac-Gym-layout tensors."""
 
     def __init__(self, num_envs, device="cuda:0", scene_cfg=None, model=None, library=None):
@@ -66,14 +66,11 @@ class TASim:
         self.model = model if model is not None else scene.build_ta_model()
         self.h = C.c_void_p()
         with torch.cuda.device(self.device):
-            self._ck(self.L.ppenv_ta_sim_create(C.byref(self.scene), C.byref(self.model), self._stream(), C.byref(self.h)))
+            self._ck(self.L.ppenv_ta_sim_create(C.byref(self.scene), C.byref(self.model), _lib.stream(self.device), C.byref(self.h)))
             torch.cuda.current_stream(self.device).synchronize()
 
     def _ck(self, rc):
         _lib.check(rc, self.L)
-
-    def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
 
     def close(self):
         if getattr(self, "h", None):
@@ -95,7 +92,7 @@ class TASim:
         for t, k in ((actions, n * 27), (root_states, n * 39), (dof_states, n * 54), (rb_states, n * 42 * 13), (dof_force, n * 27), (pre_ball_vx, n)):
             self._check(t, k)
         self._ck(self.L.ppenv_ta_simulate(self.h, n, actions.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(), rb_states.data_ptr(),
-                                            dof_force.data_ptr(), pre_ball_vx.data_ptr(), self._stream()))
+                                            dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.stream(self.device)))
 
     @property
     def kernel(self):
@@ -104,7 +101,7 @@ class TASim:
 
     def set_gravity(self, gravity_z):
         """sim_params.gravity (ppenv_ta_sim_set_gravity): every later step of this simulation runs under gravity_z (<= 0)."""
-        self._ck(self.L.ppenv_ta_sim_set_gravity(self.h, float(gravity_z), self._stream()))
+        self._ck(self.L.ppenv_ta_sim_set_gravity(self.h, float(gravity_z), _lib.stream(self.device)))
         self.scene.gravity_z = float(gravity_z)
 
     @property
@@ -137,9 +134,9 @@ class TASim:
             ov = reset_override.to(self.device, torch.float32).reshape(n, 5).contiguous()
         self._ck(self.L.ppenv_ta_step(
             self.h, C.byref(state.params), actions.data_ptr(), initial_rb_states.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(),
-            rb_states.data_ptr() if rb_states is not None else None, dof_force.data_ptr(), pre_ball_vx.data_ptr(), ov.data_ptr() if ov is not None else None, state.flags.data_ptr(),
+            _lib.ptr(rb_states), dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.ptr(ov), state.flags.data_ptr(),
             state.episode.data_ptr(), state.progress_buf.data_ptr(), obs.data_ptr(), rew.data_ptr(), reset.data_ptr(),
-            state._any_reset.data_ptr(), self._stream()))
+            state._any_reset.data_ptr(), _lib.stream(self.device)))
         if ov is not None:
             torch.cuda.current_stream(self.device).synchronize()
 
@@ -155,61 +152,36 @@ class TASim:
         self._pin = (out, mean, inv_std)
         self._ck(self.L.ppenv_ta_sim_set_policy_input(self.h, mean.data_ptr(), inv_std.data_ptr(), float(clip), out.data_ptr(), out.stride(0)))
 
-    def set_randomization(self, dof_stiffness_scale=None, dof_damping_scale=None, link_mass_scale=None, restitution_scale=None, friction_scale=None,
-                          action_noise_sigma=0.0, observation_noise_sigma=0.0):
-        """ppenv_ta_sim_set_randomization: per-env tables as float32 device tensors — drive stiffness / damping scales [27, N], link mass scales
-        [28, N] (link 0 = pelvis), restitution / friction scales [N]; None = not randomised — and the two noise amplitudes.  Read by every later
-        `step` (kept alive here); chain-wave kernel only."""
-        n = self.num_envs
-
-        def tab(t, rows):
-            if t is None:
-                return None
-            t = torch.as_tensor(t, dtype=torch.float32).to(self.device).contiguous()
-            assert tuple(t.shape) == ((rows, n) if rows else (n,)), tuple(t.shape)
-            return t
-        self._dr = [tab(dof_stiffness_scale, 27), tab(dof_damping_scale, 27), tab(link_mass_scale, 28), tab(restitution_scale, 0), tab(friction_scale, 0)]
-        r = scene.Randomization()      # ppenv_ta_randomization has the fields of ppenv_randomization
-        (r.dof_stiffness_scale, r.dof_damping_scale, r.link_mass_scale, r.restitution_scale, r.friction_scale) = [t.data_ptr() if t is not None else None for t in self._dr]
-        r.action_noise_sigma, r.observation_noise_sigma = float(action_noise_sigma), float(observation_noise_sigma)
-        self._ck(self.L.ppenv_ta_sim_set_randomization(self.h, C.byref(r)))
-
+    # drive stiffness / damping scales [27, N], link mass scales [28, N] (link 0 = pelvis), restitution / friction scales [N]; chain-wave kernel only
     DR_TABLE_ROWS = {"dof_stiffness_scale": 27, "dof_damping_scale": 27, "link_mass_scale": 28, "restitution_scale": 0, "friction_scale": 0}
+    DR_SETTER = "ppenv_ta_sim_set_randomization"
+    reset_buf = None          # what apply_reset_randomization reads: the owner of the task state sets it (TAEnv: its TAState's)
 
     def set_reset_randomization(self, plan, seed=0, env_id_offset=0, action_noise_sigma=0.0, observation_noise_sigma=0.0):
         """Reset-time randomisation (include/ppenv_dr.h) of this simulation's tables: allocates the ones `plan` names
         (scene.reset_randomization_plan with dof_rows 27, mass_rows 28), hands them to set_randomization and builds the device plan.
         -> the ResetRandomizer; its apply(reset_buf) is the per-step launch."""
-        from .dr import ResetRandomizer
-        rr = ResetRandomizer(self.L, self.device, self.num_envs, plan, self.DR_TABLE_ROWS, seed=seed, env_id_offset=env_id_offset)
-        self.set_randomization(**rr.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
-        self.reset_randomization = rr
-        return rr
-
-    def clear_randomization(self):
-        self._ck(self.L.ppenv_ta_sim_set_randomization(self.h, None))
-        self._dr = None
-        self.reset_randomization = None
+        return self._set_reset_randomization(plan, seed, env_id_offset, 1, action_noise_sigma, observation_noise_sigma)
 
     def pd_targets(self, actions):
         """pre_physics_step's PD targets (TA:1131) for actions [N,27]."""
         a = actions.to(device=self.device, dtype=torch.float32).reshape(self.num_envs, 27).contiguous()
         out = torch.empty_like(a)
-        self._ck(self.L.ppenv_ta_pd_targets(self.h, self.num_envs, a.data_ptr(), out.data_ptr(), self._stream()))
+        self._ck(self.L.ppenv_ta_pd_targets(self.h, self.num_envs, a.data_ptr(), out.data_ptr(), _lib.stream(self.device)))
         return out
 
     def serve_from_draws(self, draws):
         """TA's generate_random_speed_for_ball (TA:346-377) on [M,3] draws (speed, tilt deg, tilt_z deg)."""
         d = torch.as_tensor(draws, dtype=torch.float32).to(self.device).reshape(-1, 3).contiguous()
         out = torch.empty_like(d)
-        self._ck(self.L.ppenv_ta_serve_from_draws(self.h, d.data_ptr(), d.shape[0], out.data_ptr(), self._stream()))
+        self._ck(self.L.ppenv_ta_serve_from_draws(self.h, d.data_ptr(), d.shape[0], out.data_ptr(), _lib.stream(self.device)))
         return out
 
     def forward_kinematics(self, root_states, dof_states, rb_states):
         n = self.num_envs
         for t, k in ((root_states, n * 39), (dof_states, n * 54), (rb_states, n * 42 * 13)):
             self._check(t, k)
-        self._ck(self.L.ppenv_ta_forward_kinematics(self.h, n, root_states.data_ptr(), dof_states.data_ptr(), rb_states.data_ptr(), self._stream()))
+        self._ck(self.L.ppenv_ta_forward_kinematics(self.h, n, root_states.data_ptr(), dof_states.data_ptr(), rb_states.data_ptr(), _lib.stream(self.device)))
 
 
 class TAEnv:
@@ -252,6 +224,7 @@ class TAEnv:
             self.params.initial_rb_shared = 1
         self.obs_buf, self.rew_buf, self.reset_buf, self.progress_buf = self.state.obs_buf, self.state.rew_buf, self.state.reset_buf, self.state.progress_buf
         self.reset_buf.fill_(1)   # upstream VecTask.allocate_buffers
+        self.sim.reset_buf = self.reset_buf       # what sim.apply_reset_randomization reads
 
     def step(self, actions, obs=None, rew=None, reset=None):
         """obs / rew / reset (fused mode only): tensors that receive this step's observations, rewards and reset flags instead of
@@ -299,17 +272,11 @@ class TAEnv:
         return getattr(self.sim, "reset_randomization", None)
 
     def set_noise_sigmas(self, action_noise_sigma=0.0, observation_noise_sigma=0.0):
-        self.sim.set_randomization(**self.reset_randomization.tables, action_noise_sigma=action_noise_sigma, observation_noise_sigma=observation_noise_sigma)
+        self.sim.set_noise_sigmas(action_noise_sigma, observation_noise_sigma)
 
     def apply_reset_randomization(self, env_ids=None):
         """The per-step launch (ppenv_dr_apply on reset_buf); env_ids: the id variant, for reset_idx(env_ids)."""
-        rr = self.reset_randomization
-        if rr is None:
-            raise _lib.PPEnvError("apply_reset_randomization: no plan is set (set_reset_randomization)")
-        if env_ids is None:
-            rr.apply(self.reset_buf)
-        else:
-            rr.apply_ids(env_ids)
+        self.sim.apply_reset_randomization(env_ids)
 
     def clear_randomization(self):
         self.sim.clear_randomization()

@@ -4,10 +4,10 @@ TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 
+from helpers import build_shim
 from isaacgym_amd import scene
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -21,12 +21,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < max(os.path.getmtime(p) for p in [_SRC] + _HDRS):
-            tmp = f"{_LIB}.{os.getpid()}.tmp"
-            subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-fno-signed-zeros", "-ffinite-math-only",
-                            "-Wno-unknown-pragmas", "-o", tmp, _SRC], check=True, capture_output=True)
-            os.replace(tmp, _LIB)
-        L = C.CDLL(_LIB)
+        L = build_shim(_SRC, _LIB, _HDRS, ["-ffp-contract=off", "-fno-signed-zeros", "-ffinite-math-only"])
         u32, u64, i32, i64, vp = C.c_uint32, C.c_uint64, C.c_int32, C.c_int64, C.c_void_p
         L.dr_shim_uniform.restype = L.dr_shim_base.restype = L.dr_shim_weight.restype = L.dr_shim_value.restype = C.c_float
         L.dr_shim_uniform.argtypes = [u64, u32, u32, u32]

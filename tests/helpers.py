@@ -1,5 +1,7 @@
 """Shared helpers for the parity tests."""
+import ctypes
 import os
+import subprocess
 
 import numpy as np
 
@@ -11,6 +13,18 @@ BODY_IDS = [0, 31, 32, 33, 34, 35, 36, 37, 38, 39]
 # fp32 tolerances of the parity bar (BASELINE.json north_star: "fp32, rtol 1e-4")
 RTOL = 1e-4
 ATOL = 1e-5
+
+
+def build_shim(src, out, deps, flags):
+    """A host shim (tests/csrc/*.cpp: kernel arithmetic compiled for the CPU) as a CDLL: g++ of `src` -> `out` with `flags` (the shim's
+    own floating-point switches; the parity tolerances were set against them) when `out` is missing or older than `src` / `deps`.
+    Built aside and renamed: another test process never loads half a file."""
+    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in [src] + list(deps)):
+        tmp = f"{out}.{os.getpid()}.tmp"
+        subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17"] + list(flags) + ["-Wno-unknown-pragmas", "-o", tmp, src],
+                       check=True, capture_output=True)
+        os.replace(tmp, out)
+    return ctypes.CDLL(out)
 
 
 def load_golden(variant):

@@ -3,10 +3,10 @@
 TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from helpers import build_shim
 from isaacgym_amd.play import PlayTotals, totals_dict
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -20,12 +20,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        if (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < max(os.path.getmtime(p) for p in [_SRC] + _HDRS):
-            tmp = f"{_LIB}.{os.getpid()}.tmp"
-            subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off", "-Wno-unknown-pragmas", "-o", tmp, _SRC],
-                           check=True, capture_output=True)
-            os.replace(tmp, _LIB)
-        L = C.CDLL(_LIB)
+        L = build_shim(_SRC, _LIB, _HDRS, ["-ffp-contract=off"])
         i32, i64, vp = C.c_int32, C.c_int64, C.c_void_p
         L.play_shim_sizeof_totals.restype = L.play_shim_sizeof_partial.restype = C.c_size_t
         L.play_shim_reset.restype = L.play_shim_accumulate.restype = None

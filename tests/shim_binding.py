@@ -2,35 +2,30 @@
 TEST INFRASTRUCTURE ONLY."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from helpers import build_shim
 from isaacgym_amd import scene
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "host_shim.cpp")
-_HDR = os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h")
-_HDR2 = os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_ta_device.h")
+_HDRS = [os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_ta_device.h")]
 _LIB = os.path.join(_HERE, "csrc", "libppenv_hostshim.so")
+_FLAGS = ["-ffp-contract=fast", "-fno-signed-zeros", "-ffinite-math-only"]
 _lib = None
 
 
 def lib_for_model(header, out):
     """The host shim with ANOTHER arm model compiled in (-DPPENV_MODEL_HEADER, as isaacgym_amd._lib.build_for_arm_model does for
     the HIP library): `header` = modelgen.generate(config) written to a file; -> a CDLL."""
-    subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=fast", "-fno-signed-zeros", "-ffinite-math-only", "-Wno-unknown-pragmas",
-                    f'-DPPENV_MODEL_HEADER="{header}"', "-o", out, _SRC], check=True, capture_output=True)
-    return C.CDLL(out)
+    return build_shim(_SRC, out, _HDRS + [header], _FLAGS + [f'-DPPENV_MODEL_HEADER="{header}"'])
 
 
 def lib():
     global _lib
     if _lib is None:
-        if (not os.path.exists(_LIB)) or os.path.getmtime(_LIB) < max(os.path.getmtime(_SRC), os.path.getmtime(_HDR), os.path.getmtime(_HDR2)):
-            subprocess.run(["g++", "-O2", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=fast", "-fno-signed-zeros", "-ffinite-math-only", "-Wno-unknown-pragmas",
-                            "-o", _LIB, _SRC], check=True, capture_output=True)
-        _lib = C.CDLL(_LIB)
+        _lib = build_shim(_SRC, _LIB, _HDRS, _FLAGS)
     return _lib
 
 

@@ -254,8 +254,8 @@ def test_policy_entry_points_reject_bad_arguments_without_a_gpu():
     rows, unaligned or odd output strides — and reports PPENV_EINVAL with a message (no compute happens here: there is no GPU)."""
     import ctypes as C
     from isaacgym_amd import _lib
-    from isaacgym_amd.policy import MLPLayer, _lib_policy
-    L = _lib_policy()
+    from isaacgym_amd.policy import MLPLayer
+    L = _lib.lib()
     EINVAL = -1
     d = MLPLayer()
     assert L.ppenv_mlp_layer_forward(C.byref(d), None) == EINVAL                       # all NULL

@@ -21,7 +21,7 @@ def _ints(torch, gen, shape, lo=-2, hi=3):
 # ------------------------------------------------------------------------------------------------ CPU: argument checks only
 def test_backward_entry_points_reject_bad_arguments_before_any_device_call():
     from isaacgym_amd import _lib, policy
-    L = policy._lib_policy()
+    L = _lib.lib()
     d = policy.MLPDw()
     assert L.ppenv_mlp_layer_backward_weight(C.byref(d), None) == -1 and b"NULL pointer" in L.ppenv_last_error()
     d.m, d.n, d.k, d.batch, d.lddz, d.ldx, d.lddw = 100, 64, 64, 1, 64, 64, 64            # m not a multiple of 64

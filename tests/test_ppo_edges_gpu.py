@@ -292,7 +292,7 @@ def test_loss_kernel_wide_row_strides(torch_cuda, m, a):
     ld_mu, ld_value, ld_act, ld_old, ld_dh = a + 5, 3, a + 3, a + 2, a + 1 + 6
     mu, value, act, old_mu = wide(b["mu"], ld_mu), wide(b["value"], ld_value), wide(b["actions"], ld_act), wide(b["old_mu"], ld_old)
     vec = {k: d(b[k]) for k in ("old_sigma", "old_neglogp", "advantages", "old_values", "returns", "logstd")}
-    L = ppo._lib_ppo()
+    L = _lib.lib()
     partial = torch.zeros(int(L.ppenv_ppo_loss_partial_floats(m)), device="cuda")
     sc = torch.full((1,), scale, device="cuda")
     outs = []
@@ -444,7 +444,7 @@ def test_adam_launch_shapes(torch_cuda, truncate):
 
 def test_adam_table_of_64_tensors_and_the_refusal_of_65(torch_cuda):
     torch = torch_cuda
-    from isaacgym_amd import ppo
+    from isaacgym_amd import _lib, ppo
     gen = torch.Generator().manual_seed(13)
     scale, lr = 1024.0, 1e-3
     items = [_layout(torch, LAYOUTS[i % len(LAYOUTS)], torch.randn(N_ELEMS, generator=gen).cuda()) for i in range(64)]
@@ -470,7 +470,7 @@ def test_adam_table_of_64_tensors_and_the_refusal_of_65(torch_cuda):
     # 65: refused by the class, and by both entry points before any device call (the table pointer is the valid one of 64)
     with pytest.raises(AssertionError):
         ppo.DeviceAdam(params + [torch.zeros(4, device="cuda")], gbufs + [torch.zeros(4, device="cuda")], lr)
-    L, st = ppo._lib_ppo(), torch.cuda.current_stream().cuda_stream
+    L, st = _lib.lib(), torch.cuda.current_stream().cuda_stream
     before = [p.clone() for p in params] + [opt.state.clone()]
     assert L.ppenv_ppo_grad_sumsq(opt.table.data_ptr(), 65, opt.slab.data_ptr(), opt.parts, st) == PPENV_EINVAL
     assert b"64 tensors" in L.ppenv_last_error()
