@@ -25,6 +25,7 @@ using std::max;
 __device__ unsigned long long pp_stamp_buf[4096 * 32];
 #endif
 #include "ppenv_device.h"
+#include "ppenv_host.h"
 
 using namespace pp;
 
@@ -268,7 +269,7 @@ __device__ __forceinline__ bool await(int* flag, int value) {
     }
     return false;
 }
-// the status word lives in pinned host memory (ppenv::status_host): the host reads it at its next call without a synchronisation
+// the status word lives in pinned host memory (PPStatusWord, ppenv_host.h): the host reads it at its next call without a synchronisation
 __device__ __forceinline__ void report_fault(uint32_t* status, uint32_t bit) {
     if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_or(status, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -912,19 +913,9 @@ __global__ void serve_transpose_kernel(int n, const float* in, float* out) {
 
 // ------------------------------------------------------------------------- host side
 thread_local char g_err[512] = "";
-void set_err(const char* fmt, const char* a = "", const char* b = "") { snprintf(g_err, sizeof g_err, fmt, a, b); }
 }  // namespace
-void ppenv_set_error(const char* msg) { set_err("%s", msg); }   // for the other translation units of the library
+void ppenv_set_error(const char* msg) { snprintf(g_err, sizeof g_err, "%s", msg); }   // declared in ppenv_host.h, for every translation unit of the library
 namespace {
-
-#define PP_HIP(call)                                                   \
-    do {                                                               \
-        hipError_t e_ = (call);                                        \
-        if (e_ != hipSuccess) {                                        \
-            set_err("%s failed: %s", #call, hipGetErrorString(e_));    \
-            return PPENV_EHIP;                                         \
-        }                                                              \
-    } while (0)
 
 size_t align_up(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -952,29 +943,29 @@ Layout layout_for(int n, int A) {
 }
 
 bool validate(const ppenv_config* c) {
-    if (!c) { set_err("config is NULL"); return false; }
-    if (c->abi_version != PPENV_ABI_VERSION) { set_err("config.abi_version does not match this library"); return false; }
-    if (c->num_envs <= 0) { set_err("num_envs must be positive"); return false; }
-    if (c->variant < PPENV_VARIANT_T3 || c->variant > PPENV_VARIANT_T4) { set_err("unknown task variant"); return false; }
-    if (c->num_humanoids != agents_of(c)) { set_err("num_humanoids must be 2 for PPENV_VARIANT_T4 and 1 otherwise"); return false; }
-    if (agents_of(c) == 2 && c->substeps > kMaxSplitSubsteps) { set_err("the 4-actor variant supports at most 4 substeps"); return false; }
-    if (c->substeps < 1 || c->substeps > 16 || c->ball_substeps < 1 || c->ball_substeps > 64) { set_err("substeps / ball_substeps out of range"); return false; }
-    if (!(c->dt > 0.f)) { set_err("dt must be positive"); return false; }
+    if (!c) { ppenv_set_error("config is NULL"); return false; }
+    if (c->abi_version != PPENV_ABI_VERSION) { ppenv_set_error("config.abi_version does not match this library"); return false; }
+    if (c->num_envs <= 0) { ppenv_set_error("num_envs must be positive"); return false; }
+    if (c->variant < PPENV_VARIANT_T3 || c->variant > PPENV_VARIANT_T4) { ppenv_set_error("unknown task variant"); return false; }
+    if (c->num_humanoids != agents_of(c)) { ppenv_set_error("num_humanoids must be 2 for PPENV_VARIANT_T4 and 1 otherwise"); return false; }
+    if (agents_of(c) == 2 && c->substeps > kMaxSplitSubsteps) { ppenv_set_error("the 4-actor variant supports at most 4 substeps"); return false; }
+    if (c->substeps < 1 || c->substeps > 16 || c->ball_substeps < 1 || c->ball_substeps > 64) { ppenv_set_error("substeps / ball_substeps out of range"); return false; }
+    if (!(c->dt > 0.f)) { ppenv_set_error("dt must be positive"); return false; }
     {   // the serve's sines and cosines are a degree-9 / degree-8 series (sincos_small): fp32-exact up to ~1 rad, not beyond
         const float lim = 57.0f;
         if (fabsf(c->serve_tilt_lo_deg) > lim || fabsf(c->serve_tilt_hi_deg) > lim || fabsf(c->serve_tilt_z_lo_deg) > lim || fabsf(c->serve_tilt_z_hi_deg) > lim) {
-            set_err("serve tilt angles must lie within +-57 degrees (the kernel's small-angle sine / cosine series)");
+            ppenv_set_error("serve tilt angles must lie within +-57 degrees (the kernel's small-angle sine / cosine series)");
             return false;
         }
     }
     if (!model_matches<ModelG1>(*c)) {
-        set_err("the config's arm model (joint frames / inertials / gains / limits / link shapes / paddle / observed-body frames) differs from "
+        ppenv_set_error("the config's arm model (joint frames / inertials / gains / limits / link shapes / paddle / observed-body frames) differs from "
                 "the one compiled into this library (csrc/ppenv_model_g1.h); generate its header with isaacgym_amd.modelgen and rebuild "
                 "(isaacgym_amd._lib.build_for_arm_model)");
         return false;
     }
     for (int d = 0; d < ND; d++)
-        if (!(c->joint[d].mass > 0.f) || !(c->joint[d].lower <= c->joint[d].upper)) { set_err("joint table: mass must be > 0 and lower <= upper"); return false; }
+        if (!(c->joint[d].mass > 0.f) || !(c->joint[d].lower <= c->joint[d].upper)) { ppenv_set_error("joint table: mass must be > 0 and lower <= upper"); return false; }
     return true;
 }
 
@@ -992,29 +983,44 @@ struct ppenv {
     int serve_on;
     bool one_wave;           // step_kernel (PPENV_STEP_KERNEL=fused, or more substeps than step_kernel_split has LDS slots for); ignored by the 4-actor variant
     int agents;              // 1, or 2 for PPENV_VARIANT_T4
-    uint32_t* status_host;   // PPENV_STATUS_* bits, pinned host memory mapped into the device: kernels write it through, the host reads it without a sync
-    uint32_t* status_dev;
+    PPStatusWord status;     // PPENV_STATUS_* bits: kernels write them through, the host reads them without a sync
     int dbg_drop_handoff;    // PPENV_DEBUG_DROP_HANDOFF=1 at create (tests): the arm wave withholds its last hand-off, so the partner waves time out
     int dr_on;               // a randomisation is set: ppenv_step launches step_kernel<ModelG1, true> with these tables
     DRTables dr;
 };
 
 namespace {
-int use_device(const ppenv* e) {
-    int cur = -1;
-    PP_HIP(hipGetDevice(&cur));
-    if (cur != e->cfg.device_id) PP_HIP(hipSetDevice(e->cfg.device_id));
-    return PPENV_OK;
-}
 // every entry point that reads or advances the state: refuse to go on once a kernel has reported a fault
-int check_status(const ppenv* e) {
-    const uint32_t st = *(volatile uint32_t*)e->status_host;
-    if (st == 0) return PPENV_OK;
-    char msg[200];
-    snprintf(msg, sizeof msg, "device status 0x%x: %s; the environment state is no longer valid (destroy the handle)", st,
-             (st & PPENV_STATUS_HANDOFF_TIMEOUT) ? "a step-kernel wave timed out waiting for its partner wave's LDS hand-off and did not store its envs" : "unknown fault");
-    set_err("%s", msg);
-    return PPENV_EDEVICE;
+int check_status(const ppenv* e) { return e->status.refuse_if_set("device status 0x%x: %s; the environment state is no longer valid (destroy the handle)"); }
+
+// create (mode 0) / reset_all (mode 1): init_kernel for the handle's number of humanoids
+void launch_init(const ppenv* e, int mode, int serve_on, hipStream_t s) {
+    const dim3 grid(grid_for(e->cfg.num_envs)), block(kBlock);
+    if (e->agents == 2) hipLaunchKernelGGL((init_kernel<ModelG1, 2>), grid, block, 0, s, e->K, e->buf, mode, serve_on);
+    else hipLaunchKernelGGL((init_kernel<ModelG1, 1>), grid, block, 0, s, e->K, e->buf, mode, serve_on);
+}
+
+// What ppenv_create does on the device.  On any failure the caller destroys the handle, which frees whatever exists by then.
+int create_on_device(ppenv* e, void* arena_dev, size_t arena_bytes, hipStream_t s) {
+    PP_HIP(hipSetDevice(e->cfg.device_id));
+    if (!e->status.alloc()) { ppenv_set_error("allocating the device status word failed"); return PPENV_ENOMEM; }
+    if (arena_dev) {
+        if (arena_bytes < e->lay.total || ((uintptr_t)arena_dev & 255u)) { ppenv_set_error("arena too small or not 256-byte aligned"); return PPENV_EINVAL; }
+        e->arena = arena_dev;
+    } else {
+        if (hipMalloc(&e->arena, e->lay.total) != hipSuccess) { ppenv_set_error("hipMalloc of the env arena failed"); return PPENV_ENOMEM; }
+        e->owns_arena = true;
+    }
+    char* a = (char*)e->arena;
+    const Layout& l = e->lay;
+    e->buf = DevBuffers{(float*)(a + l.obs), (float*)(a + l.rew), (long long*)(a + l.reset), (long long*)(a + l.progress),
+                        (float*)(a + l.dof_pos), (float*)(a + l.dof_vel), (float*)(a + l.dof_force), (float*)(a + l.ball),
+                        (uint32_t*)(a + l.flags), (uint32_t*)(a + l.episode), (float*)(a + l.serve)};
+    e->K = make_step_consts(e->cfg);
+    PP_HIP(hipMemsetAsync(e->arena, 0, l.total, s));
+    launch_init(e, 0, 0, s);
+    PP_HIP(hipGetLastError());
+    return PPENV_OK;
 }
 }  // namespace
 
@@ -1029,76 +1035,33 @@ size_t ppenv_arena_bytes(const ppenv_config* cfg) {
 }
 
 int ppenv_create(const ppenv_config* cfg, void* arena_dev, size_t arena_bytes, void* stream, ppenv** out) {
-    if (!out) { set_err("out is NULL"); return PPENV_EINVAL; }
+    if (!out) { ppenv_set_error("out is NULL"); return PPENV_EINVAL; }
     *out = nullptr;
     if (!validate(cfg)) return PPENV_EINVAL;
     int ndev = 0;
     PP_HIP(hipGetDeviceCount(&ndev));
-    if (cfg->device_id < 0 || cfg->device_id >= ndev) { set_err("device_id out of range"); return PPENV_EINVAL; }
+    if (cfg->device_id < 0 || cfg->device_id >= ndev) { ppenv_set_error("device_id out of range"); return PPENV_EINVAL; }
     // PPENV_STEP_KERNEL=split|fused forces a schedule (same arithmetic either way).  The two-wave schedule wins at every size measured
     // (us per step, split vs one-wave: N = 16384 13.1 / 20.5, 65536 19.6 / 22.8, 131072 35.3 / 41.5): it needs 187 VGPRs (two waves
     // per SIMD) against 256 + 79 AGPRs.
     const char* kernel = getenv("PPENV_STEP_KERNEL");
     if (kernel && strcmp(kernel, "split") != 0 && strcmp(kernel, "fused") != 0) {
-        set_err("PPENV_STEP_KERNEL=%s: the accepted values are split and fused (or leave it unset)", kernel);
+        pp_set_errorf("PPENV_STEP_KERNEL=%s: the accepted values are split and fused (or leave it unset)", kernel);
         return PPENV_EINVAL;
     }
-    ppenv* e = new (std::nothrow) ppenv;
-    if (!e) { set_err("out of host memory"); return PPENV_ENOMEM; }
+    ppenv* e = new (std::nothrow) ppenv{};   // every member zero / NULL: ppenv_destroy takes the handle at any stage of what follows
+    if (!e) { ppenv_set_error("out of host memory"); return PPENV_ENOMEM; }
     e->cfg = *cfg;
     e->agents = agents_of(cfg);
     e->lay = layout_for(cfg->num_envs, e->agents);
-    e->serve_on = 0;
     e->one_wave = (kernel && strcmp(kernel, "fused") == 0) || cfg->substeps > kMaxSplitSubsteps;   // one LDS hand-off slot per substep boundary
-    e->arena = nullptr;
-    e->owns_arena = false;
-    e->status_host = e->status_dev = nullptr;
-    e->dr_on = 0;
-    e->dr = DRTables{};
     {
         const char* d = getenv("PPENV_DEBUG_DROP_HANDOFF");
         e->dbg_drop_handoff = (d && d[0] == '1') ? 1 : 0;
     }
-    if (hipSetDevice(cfg->device_id) != hipSuccess) { delete e; set_err("hipSetDevice failed"); return PPENV_EHIP; }
-    if (hipHostMalloc((void**)&e->status_host, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&e->status_dev, e->status_host, 0) != hipSuccess) {
-        if (e->status_host) (void)hipHostFree(e->status_host);
-        delete e;
-        set_err("allocating the device status word failed");
-        return PPENV_ENOMEM;
-    }
-    *e->status_host = 0u;
-    if (arena_dev) {
-        if (arena_bytes < e->lay.total || ((uintptr_t)arena_dev & 255u)) {
-            (void)hipHostFree(e->status_host);
-            delete e;
-            set_err("arena too small or not 256-byte aligned");
-            return PPENV_EINVAL;
-        }
-        e->arena = arena_dev;
-    } else {
-        if (hipMalloc(&e->arena, e->lay.total) != hipSuccess) { (void)hipHostFree(e->status_host); delete e; set_err("hipMalloc of the env arena failed"); return PPENV_ENOMEM; }
-        e->owns_arena = true;
-    }
-    char* a = (char*)e->arena;
-    const Layout& l = e->lay;
-    e->buf = DevBuffers{(float*)(a + l.obs), (float*)(a + l.rew), (long long*)(a + l.reset), (long long*)(a + l.progress),
-                        (float*)(a + l.dof_pos), (float*)(a + l.dof_vel), (float*)(a + l.dof_force), (float*)(a + l.ball),
-                        (uint32_t*)(a + l.flags), (uint32_t*)(a + l.episode), (float*)(a + l.serve)};
-    e->K = make_step_consts(e->cfg);
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t err = hipMemsetAsync(e->arena, 0, l.total, s);
-    if (err == hipSuccess) {
-        if (e->agents == 2) hipLaunchKernelGGL((init_kernel<ModelG1, 2>), dim3(grid_for(cfg->num_envs)), dim3(kBlock), 0, s, e->K, e->buf, 0, 0);
-        else hipLaunchKernelGGL((init_kernel<ModelG1, 1>), dim3(grid_for(cfg->num_envs)), dim3(kBlock), 0, s, e->K, e->buf, 0, 0);
-        err = hipGetLastError();
-    }
-    if (err != hipSuccess) {
-        set_err("initialising the env state failed: %s", hipGetErrorString(err));
-        if (e->owns_arena) (void)hipFree(e->arena);
-        (void)hipHostFree(e->status_host);
-        delete e;
-        return PPENV_EHIP;
+    if (int rc = create_on_device(e, arena_dev, arena_bytes, (hipStream_t)stream)) {
+        ppenv_destroy(e);
+        return rc;
     }
     *out = e;
     return PPENV_OK;
@@ -1108,12 +1071,12 @@ void ppenv_destroy(ppenv* e) {
     if (!e) return;
     (void)hipSetDevice(e->cfg.device_id);
     if (e->owns_arena && e->arena) (void)hipFree(e->arena);
-    if (e->status_host) (void)hipHostFree(e->status_host);
+    e->status.release();
     delete e;
 }
 
 int ppenv_buffers_of(ppenv* e, ppenv_buffers* out) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e || !out) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     out->num_envs = e->cfg.num_envs;
     out->num_agents = e->agents;
     out->obs_buf = e->buf.obs; out->rew_buf = e->buf.rew;
@@ -1124,7 +1087,7 @@ int ppenv_buffers_of(ppenv* e, ppenv_buffers* out) {
 }
 
 int ppenv_config_of(ppenv* e, ppenv_config* out) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e || !out) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     *out = e->cfg;
     return PPENV_OK;
 }
@@ -1145,26 +1108,26 @@ static StepSchedule schedule_of(const ppenv* e) {
 }
 
 static int launch_step(ppenv* e, const DevBuffers& buf, const float* actions_dev, void* stream) {
-    if (!e || !actions_dev) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e || !actions_dev) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     if (int rc = check_status(e)) return rc;
-    if (int rc = use_device(e)) return rc;
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     const dim3 grid(grid_for(e->cfg.num_envs));
     hipStream_t st = (hipStream_t)stream;
     switch (schedule_of(e)) {
     case SCH_DR_T4:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 1, 1, true>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff, e->dr);
+        hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 1, 1, true>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status.dev, e->dbg_drop_handoff, e->dr);
         break;
     case SCH_DR_SPLIT:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0, 1, true>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff, e->dr);
+        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0, 1, true>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status.dev, e->dbg_drop_handoff, e->dr);
         break;
     case SCH_DR_FUSED:
         hipLaunchKernelGGL((step_kernel<ModelG1, true>), grid, dim3(kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->dr);
         break;
     case SCH_T4:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 1>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
+        hipLaunchKernelGGL((step_kernel_split<ModelG1, 2, 1>), grid, dim3(3 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status.dev, e->dbg_drop_handoff);
         break;
     case SCH_SPLIT:
-        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status_dev, e->dbg_drop_handoff);
+        hipLaunchKernelGGL((step_kernel_split<ModelG1, 1, 0>), grid, dim3(2 * kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, e->status.dev, e->dbg_drop_handoff);
         break;
     case SCH_FUSED:
         hipLaunchKernelGGL((step_kernel<ModelG1, false>), grid, dim3(kBlock), 0, st, e->K, buf, actions_dev, e->serve_on, DRTables{});
@@ -1182,7 +1145,7 @@ int ppenv_step(ppenv* e, const float* actions_dev, void* stream) { return launch
  * 16 384 envs (profiles/r04_d_smallk.txt): 1.03 G env-steps/s, the same as one replay of a 20-step graph (so the ~85 us such a short run loses are not
  * the graph launch but the first launch after an idle GPU and the final synchronisation), against 0.8-0.9 G for twenty Python calls. */
 int ppenv_step_sequence(ppenv* e, const float* const* actions_dev, int32_t count, void* stream) {
-    if (!e || !actions_dev || count < 0) { set_err("NULL argument or negative count"); return PPENV_EINVAL; }
+    if (!e || !actions_dev || count < 0) { ppenv_set_error("NULL argument or negative count"); return PPENV_EINVAL; }
     for (int32_t i = 0; i < count; i++)
         if (int rc = launch_step(e, e->buf, actions_dev[i], stream)) return rc;
     return PPENV_OK;
@@ -1190,8 +1153,8 @@ int ppenv_step_sequence(ppenv* e, const float* const* actions_dev, int32_t count
 
 /* the same launch with this step's observations / rewards / reset flags going to the caller's tensors (NULL: the handle's own) */
 int ppenv_step_into(ppenv* e, const float* actions_dev, float* obs_dev, float* rew_dev, int64_t* reset_dev, void* stream) {
-    if (!e) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (obs_dev && (reinterpret_cast<uintptr_t>(obs_dev) & 15)) { set_err("ppenv_step_into: obs must be 16-byte aligned"); return PPENV_EINVAL; }
+    if (!e) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (obs_dev && (reinterpret_cast<uintptr_t>(obs_dev) & 15)) { ppenv_set_error("ppenv_step_into: obs must be 16-byte aligned"); return PPENV_EINVAL; }
     DevBuffers b = e->buf;
     if (obs_dev) b.obs = obs_dev;
     if (rew_dev) b.rew = rew_dev;
@@ -1200,21 +1163,20 @@ int ppenv_step_into(ppenv* e, const float* actions_dev, float* obs_dev, float* r
 }
 
 int ppenv_reset_all(ppenv* e, void* stream) {
-    if (!e) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     if (int rc = check_status(e)) return rc;
-    if (int rc = use_device(e)) return rc;
-    if (e->agents == 2) hipLaunchKernelGGL((init_kernel<ModelG1, 2>), dim3(grid_for(e->cfg.num_envs)), dim3(kBlock), 0, (hipStream_t)stream, e->K, e->buf, 1, e->serve_on);
-    else hipLaunchKernelGGL((init_kernel<ModelG1, 1>), dim3(grid_for(e->cfg.num_envs)), dim3(kBlock), 0, (hipStream_t)stream, e->K, e->buf, 1, e->serve_on);
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
+    launch_init(e, 1, e->serve_on, (hipStream_t)stream);
     PP_HIP(hipGetLastError());
     return PPENV_OK;
 }
 
-uint32_t ppenv_status(ppenv* e) { return e ? *(volatile uint32_t*)e->status_host : 0u; }
+uint32_t ppenv_status(ppenv* e) { return e ? e->status.read() : 0u; }
 
 int ppenv_set_randomization(ppenv* e, const ppenv_randomization* dr) {
-    if (!e) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     if (!dr) { e->dr_on = 0; e->dr = DRTables{}; return PPENV_OK; }
-    if (!(dr->action_noise_sigma >= 0.f) || !(dr->observation_noise_sigma >= 0.f)) { set_err("noise amplitudes must be >= 0"); return PPENV_EINVAL; }
+    if (!(dr->action_noise_sigma >= 0.f) || !(dr->observation_noise_sigma >= 0.f)) { ppenv_set_error("noise amplitudes must be >= 0"); return PPENV_EINVAL; }
     e->dr = DRTables{dr->dof_stiffness_scale, dr->dof_damping_scale, dr->link_mass_scale, dr->restitution_scale, dr->friction_scale,
                      dr->action_noise_sigma, dr->observation_noise_sigma};
     e->dr_on = 1;
@@ -1222,30 +1184,30 @@ int ppenv_set_randomization(ppenv* e, const ppenv_randomization* dr) {
 }
 
 int ppenv_set_gravity(ppenv* e, float gravity_z) {
-    if (!e) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (!(gravity_z <= 0.f)) { set_err("gravity_z must be <= 0 (the world's up axis is z)"); return PPENV_EINVAL; }
+    if (!e) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (!(gravity_z <= 0.f)) { ppenv_set_error("gravity_z must be <= 0 (the world's up axis is z)"); return PPENV_EINVAL; }
     e->cfg.gravity_z = gravity_z;
     e->K = make_step_consts(e->cfg);   // host-side: the next launch carries the new constants in its kernel argument
     return PPENV_OK;
 }
 
 int ppenv_reset_idx(ppenv* e, const int64_t* env_ids_dev, int32_t count, int refresh_obs, void* stream) {
-    if (!e || (count > 0 && !env_ids_dev) || count < 0) { set_err("ppenv_reset_idx: NULL ids or negative count"); return PPENV_EINVAL; }
+    if (!e || (count > 0 && !env_ids_dev) || count < 0) { ppenv_set_error("ppenv_reset_idx: NULL ids or negative count"); return PPENV_EINVAL; }
     if (count == 0) return PPENV_OK;
     if (int rc = check_status(e)) return rc;
-    if (int rc = use_device(e)) return rc;
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     const dim3 grid((count + kBlock - 1) / kBlock), block(kBlock);
     if (e->agents == 2)
-        hipLaunchKernelGGL((reset_idx_kernel<ModelG1, 2>), grid, block, 0, (hipStream_t)stream, e->K, e->buf, (const long long*)env_ids_dev, count, refresh_obs, e->serve_on, e->status_dev);
+        hipLaunchKernelGGL((reset_idx_kernel<ModelG1, 2>), grid, block, 0, (hipStream_t)stream, e->K, e->buf, (const long long*)env_ids_dev, count, refresh_obs, e->serve_on, e->status.dev);
     else
-        hipLaunchKernelGGL((reset_idx_kernel<ModelG1, 1>), grid, block, 0, (hipStream_t)stream, e->K, e->buf, (const long long*)env_ids_dev, count, refresh_obs, e->serve_on, e->status_dev);
+        hipLaunchKernelGGL((reset_idx_kernel<ModelG1, 1>), grid, block, 0, (hipStream_t)stream, e->K, e->buf, (const long long*)env_ids_dev, count, refresh_obs, e->serve_on, e->status.dev);
     PP_HIP(hipGetLastError());
     return PPENV_OK;
 }
 
 int ppenv_pd_targets(ppenv* e, const float* actions_dev, float* pd_tar_dev, void* stream) {
-    if (!e || !actions_dev || !pd_tar_dev) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
+    if (!e || !actions_dev || !pd_tar_dev) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     const int rows = e->cfg.num_envs * e->agents;
     hipLaunchKernelGGL(pd_targets_kernel<ModelG1>, dim3((rows * ND + 255) / 256), dim3(256), 0, (hipStream_t)stream, rows, e->K.clip_actions, actions_dev, pd_tar_dev);
     PP_HIP(hipGetLastError());
@@ -1253,17 +1215,17 @@ int ppenv_pd_targets(ppenv* e, const float* actions_dev, float* pd_tar_dev, void
 }
 
 int ppenv_serve_from_draws(ppenv* e, const float* draws_dev, int32_t m, float* vel_dev, void* stream) {
-    if (!e || !draws_dev || !vel_dev || m <= 0) { set_err("NULL argument or m <= 0"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
+    if (!e || !draws_dev || !vel_dev || m <= 0) { ppenv_set_error("NULL argument or m <= 0"); return PPENV_EINVAL; }
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     hipLaunchKernelGGL(serve_from_draws_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->cfg.variant, m, draws_dev, vel_dev);
     PP_HIP(hipGetLastError());
     return PPENV_OK;
 }
 
 int ppenv_reduce_stats(ppenv* e, double* out_dev, void* stream) {
-    if (!e || !out_dev) { set_err("NULL argument"); return PPENV_EINVAL; }
+    if (!e || !out_dev) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
     if (int rc = check_status(e)) return rc;
-    if (int rc = use_device(e)) return rc;
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     const int rows = e->cfg.num_envs * e->agents;   // one row per agent: out[3] counts agents
     if (rows <= 32768) {
         hipLaunchKernelGGL(stats_kernel_single, dim3(1), dim3(1024), 0, (hipStream_t)stream, rows, e->agents, e->buf.rew, e->buf.progress,
@@ -1281,50 +1243,34 @@ int ppenv_reduce_stats(ppenv* e, double* out_dev, void* stream) {
 int ppenv_post_physics_step(ppenv* e, const float* rigid_body_states_dev, float* root_states_dev, float* dof_states_dev,
                             const float* dof_force_dev, const float* pre_ball_vx_dev, void* stream) {
     if (!e || !rigid_body_states_dev || !root_states_dev || !dof_states_dev || !dof_force_dev || !pre_ball_vx_dev) {
-        set_err("NULL argument");
+        ppenv_set_error("NULL argument");
         return PPENV_EINVAL;
     }
-    if (e->agents != 1) { set_err("ppenv_post_physics_step serves the 3-actor variants; the 4-actor entry is ppenv_t4_rewards"); return PPENV_EINVAL; }
+    if (e->agents != 1) { ppenv_set_error("ppenv_post_physics_step serves the 3-actor variants; the 4-actor entry is ppenv_t4_rewards"); return PPENV_EINVAL; }
     if (int rc = check_status(e)) return rc;
-    if (int rc = use_device(e)) return rc;
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     hipLaunchKernelGGL(post_physics_kernel, dim3(grid_for(e->cfg.num_envs)), dim3(kBlock), 0, (hipStream_t)stream, e->K, e->buf,
                        rigid_body_states_dev, root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev, e->serve_on);
     PP_HIP(hipGetLastError());
     return PPENV_OK;
 }
 
-int ppenv_refresh_root_states(ppenv* e, float* out, void* stream) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
-    hipLaunchKernelGGL(refresh_root_kernel, dim3((e->cfg.num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->K, e->buf, out);
+// the gym.refresh_* entries: one lane per env, `block` of them per workgroup
+static int refresh(ppenv* e, float* out, void* stream, void (*kernel)(const StepConsts, DevBuffers, float*), int block) {
+    if (!e || !out) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
+    hipLaunchKernelGGL(kernel, dim3((e->cfg.num_envs + block - 1) / block), dim3(block), 0, (hipStream_t)stream, e->K, e->buf, out);
     PP_HIP(hipGetLastError());
     return PPENV_OK;
 }
-int ppenv_refresh_dof_states(ppenv* e, float* out, void* stream) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
-    hipLaunchKernelGGL(refresh_dof_kernel, dim3((e->cfg.num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->K, e->buf, out);
-    PP_HIP(hipGetLastError());
-    return PPENV_OK;
-}
-int ppenv_refresh_dof_force(ppenv* e, float* out, void* stream) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
-    hipLaunchKernelGGL(refresh_dof_force_kernel, dim3((e->cfg.num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->K, e->buf, out);
-    PP_HIP(hipGetLastError());
-    return PPENV_OK;
-}
-int ppenv_refresh_rigid_body_states(ppenv* e, float* out, void* stream) {
-    if (!e || !out) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
-    hipLaunchKernelGGL(refresh_rb_kernel<ModelG1>, dim3(grid_for(e->cfg.num_envs)), dim3(kBlock), 0, (hipStream_t)stream, e->K, e->buf, out);
-    PP_HIP(hipGetLastError());
-    return PPENV_OK;
-}
+int ppenv_refresh_root_states(ppenv* e, float* out, void* stream) { return refresh(e, out, stream, refresh_root_kernel, 256); }
+int ppenv_refresh_dof_states(ppenv* e, float* out, void* stream) { return refresh(e, out, stream, refresh_dof_kernel, 256); }
+int ppenv_refresh_dof_force(ppenv* e, float* out, void* stream) { return refresh(e, out, stream, refresh_dof_force_kernel, 256); }
+int ppenv_refresh_rigid_body_states(ppenv* e, float* out, void* stream) { return refresh(e, out, stream, refresh_rb_kernel<ModelG1>, kBlock); }
 
 int ppenv_set_serve_override(ppenv* e, const float* serve_dev, int on, void* stream) {
-    if (!e) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (int rc = use_device(e)) return rc;
+    if (!e) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     if (on && serve_dev) {
         hipLaunchKernelGGL(serve_transpose_kernel, dim3((e->cfg.num_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->cfg.num_envs,
                            serve_dev, e->buf.serve);
@@ -1349,9 +1295,9 @@ size_t ppenv_state_bytes(ppenv* e) {
 }
 
 static int state_io(ppenv* e, char* blob, size_t nbytes, bool to_host) {
-    if (!e || !blob) { set_err("NULL argument"); return PPENV_EINVAL; }
-    if (nbytes != ppenv_state_bytes(e)) { set_err("state blob size does not match this handle"); return PPENV_ESTATE; }
-    if (int rc = use_device(e)) return rc;
+    if (!e || !blob) { ppenv_set_error("NULL argument"); return PPENV_EINVAL; }
+    if (nbytes != ppenv_state_bytes(e)) { ppenv_set_error("state blob size does not match this handle"); return PPENV_ESTATE; }
+    if (int rc = pp_use_device(e->cfg.device_id)) return rc;
     PP_HIP(hipDeviceSynchronize());
     if (int rc = check_status(e)) return rc;       // after the synchronisation: a fault of the step still in flight is seen here
     const size_t n = (size_t)e->cfg.num_envs, A = (size_t)e->agents;

@@ -15,7 +15,7 @@
 
 #include "ppenv_dr_device.h"
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 
@@ -55,11 +55,6 @@ __global__ __launch_bounds__(kBlock) void dr_apply_ids_kernel(const ppenv_dr_pla
     const int32_t e = (int32_t)id;
     const int64_t count = steps[e / kBlock];                   // read-only in this launch
     pp::dr_ids_env(*plan, e, count, randomize_buf, draws);
-}
-
-bool launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error(what); return false; }
-    return true;
 }
 
 }  // namespace
@@ -106,7 +101,7 @@ extern "C" int ppenv_dr_apply(const ppenv_dr_plan* plan_dev, int32_t num_envs, c
     int64_t* steps = (int64_t*)state_dev;
     int32_t* draws = (int32_t*)((char*)state_dev + ppenv_dr_state_draws_offset(num_envs));
     hipLaunchKernelGGL(dr_apply_kernel, dim3(blocks_of(num_envs)), dim3(kBlock), 0, (hipStream_t)stream, plan_dev, reset_buf, randomize_buf, steps, draws, num_envs);
-    return launched("launching dr_apply_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching dr_apply_kernel failed");
 }
 
 extern "C" int ppenv_dr_apply_ids(const ppenv_dr_plan* plan_dev, int32_t num_envs, const int64_t* env_ids, int32_t count, int64_t* randomize_buf,
@@ -119,5 +114,5 @@ extern "C" int ppenv_dr_apply_ids(const ppenv_dr_plan* plan_dev, int32_t num_env
     const int64_t* steps = (const int64_t*)state_dev;
     int32_t* draws = (int32_t*)((char*)state_dev + ppenv_dr_state_draws_offset(num_envs));
     hipLaunchKernelGGL(dr_apply_ids_kernel, dim3(blocks_of(count)), dim3(kBlock), 0, (hipStream_t)stream, plan_dev, env_ids, count, randomize_buf, steps, draws, num_envs);
-    return launched("launching dr_apply_ids_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching dr_apply_ids_kernel failed");
 }

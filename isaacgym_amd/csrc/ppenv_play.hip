@@ -16,7 +16,7 @@
 
 #include "ppenv_play_device.h"
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 
@@ -90,11 +90,6 @@ __global__ __launch_bounds__(kBlock) void play_reset_kernel(int32_t num_envs, in
     }
 }
 
-bool launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error(what); return false; }
-    return true;
-}
-
 bool sizes_ok(int32_t num_envs, int32_t num_agents) {
     return num_envs > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS && (int64_t)num_envs * num_agents <= INT32_MAX;
 }
@@ -112,7 +107,7 @@ extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur
     }
     const int32_t rows = num_envs * num_agents;
     hipLaunchKernelGGL(play_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, cur_reward, cur_steps, totals);
-    return launched("launching play_reset_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching play_reset_kernel failed");
 }
 
 extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int32_t num_envs, int32_t num_agents, int64_t games_num, float* cur_reward,
@@ -124,7 +119,7 @@ extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int3
     const int32_t parts = blocks_of(num_envs);
     hipLaunchKernelGGL(play_rows_kernel, dim3(parts), dim3(kBlock), 0, (hipStream_t)stream, rew, done, num_envs, num_agents, games_num, cur_reward,
                        cur_steps, totals, partial);
-    if (!launched("launching play_rows_kernel failed")) return PPENV_EHIP;
+    if (int rc = pp_launched("launching play_rows_kernel failed")) return rc;
     hipLaunchKernelGGL(play_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
-    return launched("launching play_totals_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching play_totals_kernel failed");
 }

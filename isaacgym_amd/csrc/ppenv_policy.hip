@@ -23,7 +23,7 @@
 #include "../../include/ppenv_policy.h"
 #include "ppenv_device.h"   // dr_gauss: the counter RNG's standard normal
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 #ifndef PP_OUT_NT
 #define PP_OUT_NT 0       // 1: the activations leave by non-temporal stores (experiment, tools/gpu_mlp_exp1.py)
@@ -1234,8 +1234,7 @@ extern "C" int ppenv_mlp_prepare_input(const float* obs, int32_t m, int32_t k, i
     const long long chunks = (long long)m * (ld_out / 2);
     hipLaunchKernelGGL(prepare_input_kernel, dim3((unsigned)((chunks + 255) / 256)), dim3(256), 0, (hipStream_t)stream, obs, m, k, ld_obs, mean, inv_std, clip,
                        reinterpret_cast<_Float16*>(out), ld_out);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching prepare_input_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching prepare_input_kernel failed");
 }
 
 extern "C" int ppenv_mlp_sample_actions(const float* mu, int32_t m, int32_t a, int32_t ld_mu, const float* sigma, uint64_t seed, uint64_t counter,
@@ -1246,8 +1245,7 @@ extern "C" int ppenv_mlp_sample_actions(const float* mu, int32_t m, int32_t a, i
     }
     hipLaunchKernelGGL(sample_actions_kernel, dim3((m + 7) / 8), dim3(256), 0, (hipStream_t)stream, mu, m, a, ld_mu, sigma,
                        (unsigned long long)seed, (unsigned long long)counter, lo, hi, actions, neglogp);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching sample_actions_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching sample_actions_kernel failed");
 }
 
 extern "C" int ppenv_gae(const float* rewards, const float* values, int32_t ld_values, int64_t values_step, const int64_t* dones, int32_t horizon, int32_t n,
@@ -1258,8 +1256,7 @@ extern "C" int ppenv_gae(const float* rewards, const float* values, int32_t ld_v
     }
     hipLaunchKernelGGL(gae_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, rewards, values, ld_values, (long long)values_step,
                        reinterpret_cast<const long long*>(dones), horizon, n, gamma, tau, reward_scale, advantages, returns);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching gae_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching gae_kernel failed");
 }
 
 // the heads layer and the action draw in one launch
@@ -1278,8 +1275,7 @@ extern "C" int ppenv_mlp_heads_sample(const ppenv_mlp_layer* L, int32_t num_acti
            L->out, (long long)L->out_stride};
     hipLaunchKernelGGL(mlp_heads_kernel, dim3((L->m + 31) / 32), dim3(256), 0, (hipStream_t)stream, a,
                        SampleArgs{num_actions, sigma, (unsigned long long)seed, (unsigned long long)counter, lo, hi, actions, neglogp});
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching mlp_heads_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching mlp_heads_kernel failed");
 }
 
 namespace {
@@ -1386,8 +1382,7 @@ int launch_layer(const ppenv_mlp_layer* L, const BwdInput* bw, void* stream, int
     else if (cfg == 129) PP_LAUNCH(2, 2, 2, 2, 32);
     else PP_LAUNCH(2, 2, 2, 2, 64);
 #undef PP_LAUNCH
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching mlp_layer_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching mlp_layer_kernel failed");
 }
 }  // namespace
 
@@ -1437,8 +1432,7 @@ extern "C" int ppenv_mlp_chain_forward(const ppenv_mlp_layer* layers, int32_t co
     static int cus = 0;
     if (cus == 0) { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) { ppenv_set_error("hipGetDeviceProperties failed"); return PPENV_EHIP; } cus = prop.multiProcessorCount; }
     hipLaunchKernelGGL(mlp_chain_pp3_kernel, dim3(ticket < cus ? ticket : cus), dim3(512), 0, (hipStream_t)stream, c);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching mlp_chain_pp3_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching mlp_chain_pp3_kernel failed");
 }
 
 // The same layer with its grid sized for `cus` of the chip's 256 CUs (include/ppenv_policy.h): the tile choice above aims at one workgroup

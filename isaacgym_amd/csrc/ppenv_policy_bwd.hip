@@ -29,7 +29,7 @@
 #include "../../include/ppenv.h"
 #include "../../include/ppenv_policy.h"
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -473,7 +473,7 @@ extern "C" int ppenv_mlp_layer_backward_weight(const ppenv_mlp_dw* d, void* stre
              s > 1 ? (long long)d->batch * d->n * d->k : 0};
     const int per_xcd = s >= 8 ? (s / 8) * T : (T + (8 / s) - 1) / (8 / s);
     hipLaunchKernelGGL(mlp_dw_kernel, dim3(8 * per_xcd, d->batch), dim3(512), 0, (hipStream_t)stream, a, tn, tk);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching mlp_dw_kernel failed"); return PPENV_EHIP; }
+    if (int rc = pp_launched("launching mlp_dw_kernel failed")) return rc;
     if (s > 1) {
         // workspace [s][batch][n][k] -> dw [batch][n, lddw]: one reduce per batch entry and, when lddw != k, per row block — the common
         // case (lddw == k, dw_stride == n k) is ONE launch over batch * n * k elements
@@ -488,7 +488,7 @@ extern "C" int ppenv_mlp_layer_backward_weight(const ppenv_mlp_dw* d, void* stre
                                    reinterpret_cast<const float*>(d->workspace) + (size_t)b * nk, s, nk * d->batch, d->n, d->k,
                                    d->dw + (size_t)b * d->dw_stride, d->lddw, d->accumulate);
         }
-        if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching reduce_rows_kernel failed"); return PPENV_EHIP; }
+        if (int rc = pp_launched("launching reduce_rows_kernel failed")) return rc;
     }
     return PPENV_OK;
 }
@@ -500,8 +500,7 @@ extern "C" int ppenv_mlp_reduce_rows(const float* partial, int32_t rows, int64_t
     else
         hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, partial, rows, (long long)row_stride,
                            (long long)n, out, accumulate);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching reduce_rows_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching reduce_rows_kernel failed");
 }
 
 extern "C" size_t ppenv_mlp_bias_grad_workspace_bytes(int32_t m, int32_t n) { return (m <= 0 || n <= 0) ? 0 : (size_t)((m + 1023) / 1024) * n * sizeof(float); }
@@ -512,8 +511,7 @@ extern "C" int ppenv_mlp_bias_grad_f32(const float* dz, int32_t m, int32_t n, in
     hipLaunchKernelGGL(colsum_f32_kernel, dim3(blocks, (n + 31) / 32), dim3(256), 0, (hipStream_t)stream, dz, m, n, ld, reinterpret_cast<float*>(workspace));
     hipLaunchKernelGGL(reduce_rows_kernel, dim3((unsigned)((n / 4 + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float*>(workspace), blocks,
                        (long long)n, (long long)n, out, accumulate);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching the bias-gradient kernels failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching the bias-gradient kernels failed");
 }
 
 extern "C" int ppenv_mlp_cast_weights(const float* w32, int32_t n, int32_t k, int32_t ldw32, uint16_t* w16, int32_t ldw16, uint16_t* wt16, int32_t ldwt16,
@@ -525,8 +523,7 @@ extern "C" int ppenv_mlp_cast_weights(const float* w32, int32_t n, int32_t k, in
     const int cols = w16 ? (ldw16 > wt_rows ? ldw16 : wt_rows) : wt_rows, rows = wt16 ? (ldwt16 > n ? ldwt16 : n) : n;   // cover the zero padding of both images
     hipLaunchKernelGGL(cast_weights_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, (hipStream_t)stream, w32, n, k, ldw32,
                        reinterpret_cast<_Float16*>(w16), ldw16, reinterpret_cast<_Float16*>(wt16), ldwt16, wt_rows, ldwt16);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching cast_weights_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching cast_weights_kernel failed");
 }
 
 extern "C" int ppenv_mlp_cast_weights_batch(const ppenv_mlp_cast* items, int32_t count, void* stream) {
@@ -549,8 +546,7 @@ extern "C" int ppenv_mlp_cast_weights_batch(const ppenv_mlp_cast* items, int32_t
     }
     b.tile_off[count] = off;
     hipLaunchKernelGGL(cast_weights_batch_kernel, dim3(off), dim3(256), 0, (hipStream_t)stream, b);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching cast_weights_batch_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching cast_weights_batch_kernel failed");
 }
 
 extern "C" size_t ppenv_running_mean_std_workspace_bytes(int32_t m, int32_t k) {
@@ -568,6 +564,5 @@ extern "C" int ppenv_running_mean_std_update(const float* obs, int32_t m, int32_
     double* partial = reinterpret_cast<double*>(reinterpret_cast<char*>(workspace) + 1024);
     hipLaunchKernelGGL(rms_update_kernel, dim3((m + kRmsRows - 1) / kRmsRows, (k + 63) / 64), dim3(256), 0, (hipStream_t)stream, obs, m, k, ld, partial, tickets, mean, var,
                        count, mean_f32, inv_std_f32, eps);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching rms_update_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching rms_update_kernel failed");
 }

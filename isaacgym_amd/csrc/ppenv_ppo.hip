@@ -23,7 +23,7 @@
 #include "../../include/ppenv.h"
 #include "../../include/ppenv_ppo.h"
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 
@@ -304,11 +304,6 @@ __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_t
     }
 }
 
-bool launched(const char* what) {
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error(what); return false; }
-    return true;
-}
-
 }  // namespace
 
 extern "C" size_t ppenv_ppo_loss_partial_floats(int32_t m) {
@@ -325,10 +320,9 @@ extern "C" int ppenv_ppo_loss_grad(const ppenv_ppo_loss_args* a, void* stream) {
     }
     const int parts = (a->m + kLossThreads - 1) / kLossThreads;
     hipLaunchKernelGGL(ppo_loss_grad_kernel, dim3(parts), dim3(kLossThreads), 0, (hipStream_t)stream, *a);
-    if (!launched("launching ppo_loss_grad_kernel failed")) return PPENV_EHIP;
+    if (int rc = pp_launched("launching ppo_loss_grad_kernel failed")) return rc;
     hipLaunchKernelGGL(ppo_loss_reduce_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, *a, parts);
-    if (!launched("launching ppo_loss_reduce_kernel failed")) return PPENV_EHIP;
-    return PPENV_OK;
+    return pp_launched("launching ppo_loss_reduce_kernel failed");
 }
 
 extern "C" int ppenv_ppo_grad_sumsq(const ppenv_ppo_tensor* table, int32_t count, double* slab, int32_t parts, void* stream) {
@@ -337,7 +331,7 @@ extern "C" int ppenv_ppo_grad_sumsq(const ppenv_ppo_tensor* table, int32_t count
         return PPENV_EINVAL;
     }
     hipLaunchKernelGGL(ppo_grad_sumsq_kernel, dim3(parts), dim3(kOptThreads), 0, (hipStream_t)stream, table, count, slab);
-    return launched("launching ppo_grad_sumsq_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching ppo_grad_sumsq_kernel failed");
 }
 
 extern "C" int ppenv_ppo_adam_step(const ppenv_ppo_tensor* table, int32_t count, const double* slab, int32_t parts, ppenv_ppo_adam hp, const float* lr,
@@ -348,5 +342,5 @@ extern "C" int ppenv_ppo_adam_step(const ppenv_ppo_tensor* table, int32_t count,
         return PPENV_EINVAL;
     }
     hipLaunchKernelGGL(ppo_adam_kernel, dim3(parts), dim3(kOptThreads), 0, (hipStream_t)stream, table, count, slab, parts, hp, lr, state_in, state_out);
-    return launched("launching ppo_adam_kernel failed") ? PPENV_OK : PPENV_EHIP;
+    return pp_launched("launching ppo_adam_kernel failed");
 }

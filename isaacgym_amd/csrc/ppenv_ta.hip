@@ -85,7 +85,7 @@ __global__ __launch_bounds__(kTaBlock) void t4_rewards_kernel(const ppenv_t4_par
 
 }  // namespace
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 // The stateless entries have no handle to remember a device: they launch on the device that owns their output tensor, whatever the
@@ -106,8 +106,7 @@ int use_device_of(const void* dev_ptr) {
 // TA:1162-1166 as a launch of its own (also used by the fused step of ppenv_ta_sim.hip); not part of the public ABI
 int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, void* stream) {
     hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, flags_dev, any_reset_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching ta_clear_counts_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching ta_clear_counts_kernel failed");
 }
 
 extern "C" int ppenv_t4_rewards(const ppenv_t4_params* params, const float* rb_states_dev, const float* root_states_dev,
@@ -125,8 +124,7 @@ extern "C" int ppenv_t4_rewards(const ppenv_t4_params* params, const float* rb_s
     hipLaunchKernelGGL(t4_rewards_kernel, dim3((n + kTaBlock - 1) / kTaBlock), dim3(kTaBlock), 0, (hipStream_t)stream, *params, rb_states_dev,
                        root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev, (const long long*)progress_dev, flags1_in_dev, flags2_in_dev, flags1_dev, flags2_dev,
                        rew1_dev, rew2_dev, (long long*)reset1_dev, (long long*)reset2_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching t4_rewards_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching t4_rewards_kernel failed");
 }
 
 extern "C" int ppenv_ta_post_physics_step(const ppenv_ta_params* params, const float* rb_states_dev, const float* initial_rb_states_dev,
@@ -147,6 +145,5 @@ extern "C" int ppenv_ta_post_physics_step(const ppenv_ta_params* params, const f
                        initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev, reset_override_dev, flags_dev,
                        episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev, scratch_any_reset_dev);
     hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, s, n, flags_dev, scratch_any_reset_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching the TA post-physics kernels failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching the TA post-physics kernels failed");
 }

@@ -44,7 +44,7 @@
 using namespace pp;
 using namespace pp::ta;
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 
 namespace {
 using T = ModelG1Tree;
@@ -1151,8 +1151,7 @@ int ta_chain_launch(const TAScal& P, const TAChainArgs& a, void* stream) {
     const int n = a.p.num_envs;
     if (a.dr_on()) hipLaunchKernelGGL(ta_chain_kernel<true>, dim3((n + kE - 1) / kE), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
     else hipLaunchKernelGGL(ta_chain_kernel<false>, dim3((n + kE - 1) / kE), dim3(kWaves * 64), 0, (hipStream_t)stream, P, a);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching the chain-wave 27-dof step failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching the chain-wave 27-dof step failed");
 }
 
 }  // namespace ta

@@ -23,7 +23,7 @@ using namespace pp;
 using namespace pp::ta;
 using std::min;
 
-void ppenv_set_error(const char* msg);   // ppenv.hip
+#include "ppenv_host.h"
 int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, void* stream);   // ppenv_ta.hip
 
 namespace {
@@ -534,8 +534,7 @@ struct ppenv_ta_sim {
     int device;
     int quad;     // 1: ta_sim_quad_kernel (four lanes per env), 0: ta_sim_kernel (one lane per env; any tree)
     int chain;    // 1: ppenv_ta_step runs the chain-wave kernel (ppenv_ta_chain.hip: one lane per env, one wave per limb; the compiled G1 model only)
-    uint32_t* status_host;   // PPENV_STATUS_* bits, pinned host memory the kernels write through (cf. ppenv::status_host)
-    uint32_t* status_dev;
+    PPStatusWord status;     // PPENV_STATUS_* bits the kernels write through
     const float* pin_mean;   // ppenv_ta_sim_set_policy_input (chain-wave kernel only); pin_out NULL: off
     const float* pin_inv_std;
     float pin_clip;
@@ -545,21 +544,17 @@ struct ppenv_ta_sim {
 };
 
 namespace {
-// every entry point launches on the device the handle was created on, whatever the caller's current device is
-int ta_use_device(const ppenv_ta_sim* s) {
-    int cur = -1;
-    if (hipGetDevice(&cur) != hipSuccess || (cur != s->device && hipSetDevice(s->device) != hipSuccess)) {
-        ppenv_set_error("selecting the 27-dof handle's device failed");
-        return PPENV_EHIP;
-    }
-    return PPENV_OK;
+// is a randomisation set (ppenv_ta_sim_set_randomization)?  Its tables are read by the chain-wave kernel only.
+bool dr_set(const ppenv_ta_sim* s) {
+    return s->dr.dof_stiffness_scale || s->dr.dof_damping_scale || s->dr.link_mass_scale || s->dr.restitution_scale || s->dr.friction_scale ||
+           s->dr.action_noise_sigma > 0.f || s->dr.observation_noise_sigma > 0.f;
 }
 }  // namespace
 
 extern "C" {
 
 int ppenv_ta_sim_device(const ppenv_ta_sim* s) { return s ? s->device : -1; }
-uint32_t ppenv_ta_sim_status(const ppenv_ta_sim* s) { return s ? *(volatile uint32_t*)s->status_host : 0u; }
+uint32_t ppenv_ta_sim_status(const ppenv_ta_sim* s) { return s ? s->status.read() : 0u; }
 /* the policy's first-layer input written by ppenv_ta_step itself (chain-wave kernel): out NULL switches it off */
 int ppenv_ta_sim_set_policy_input(ppenv_ta_sim* s, const float* mean_dev, const float* inv_std_dev, float clip, void* out_f16_dev, int32_t ld_out) {
     if (!s) { ppenv_set_error("ppenv_ta_sim_set_policy_input: NULL handle"); return PPENV_EINVAL; }
@@ -605,61 +600,37 @@ int ppenv_ta_sim_create(const ppenv_config* scene, const ppenv_ta_model* model, 
     if (!scene || !model || !out) { ppenv_set_error("ppenv_ta_sim_create: NULL argument"); return PPENV_EINVAL; }
     *out = nullptr;
     if (scene->abi_version != PPENV_ABI_VERSION) { ppenv_set_error("scene.abi_version does not match this library"); return PPENV_EINVAL; }
-    ppenv_ta_sim* s = new (std::nothrow) ppenv_ta_sim;
+    ppenv_ta_sim* s = new (std::nothrow) ppenv_ta_sim{};   // every member zero / NULL
     if (!s) { ppenv_set_error("out of host memory"); return PPENV_ENOMEM; }
+    s->device = -1;
+    // the one way out on a failure from here on: ppenv_ta_sim_destroy frees whatever exists by then
+    auto fail = [&](int rc) { ppenv_ta_sim_destroy(s); return rc; };
     const char* why = "";
-    if (!make_ta_consts(*scene, *model, s->host, &why)) {
-        char msg[256];
-        snprintf(msg, sizeof msg, "ppenv_ta_sim_create: %s", why);
-        ppenv_set_error(msg);
-        delete s;
-        return PPENV_EINVAL;
-    }
+    if (!make_ta_consts(*scene, *model, s->host, &why)) { pp_set_errorf("ppenv_ta_sim_create: %s", why); return fail(PPENV_EINVAL); }
     s->K = make_step_consts(*scene);
-    s->dev = nullptr;
-    s->devK = nullptr;
     {   // PPENV_TA_KERNEL=lane|quad|chain forces a mapping (same arithmetic; quad needs the G1 tree, chain the compiled G1 model)
         const char* k = getenv("PPENV_TA_KERNEL");
         s->quad = quad_topology(s->host) && !(k && strcmp(k, "lane") == 0);
         s->chain = ta_chain_model_matches(s->host) && !(k && (strcmp(k, "lane") == 0 || strcmp(k, "quad") == 0));
         if (k && strcmp(k, "chain") == 0 && !s->chain) {
             ppenv_set_error("PPENV_TA_KERNEL=chain, but the model differs from the one compiled into the chain-wave kernel (run python -m isaacgym_amd.modelgen_ta and rebuild)");
-            delete s;
-            return PPENV_EINVAL;
+            return fail(PPENV_EINVAL);
         }
     }
-    s->status_host = s->status_dev = nullptr;
-    s->pin_mean = s->pin_inv_std = nullptr; s->pin_out = nullptr; s->pin_clip = 0.f; s->pin_ld = 0;
-    s->dr = ppenv_ta_randomization{};
     // the handle lives on scene->device_id when that names a visible GPU (the caller's current device otherwise)
     int ndev = 0;
-    s->device = -1;
     if (hipGetDeviceCount(&ndev) == hipSuccess && scene->device_id >= 0 && scene->device_id < ndev && hipSetDevice(scene->device_id) == hipSuccess) s->device = scene->device_id;
     if ((s->device < 0 && hipGetDevice(&s->device) != hipSuccess) || hipMalloc((void**)&s->dev, sizeof(TAConsts)) != hipSuccess ||
         hipMalloc((void**)&s->devK, sizeof(StepConsts)) != hipSuccess) {
         ppenv_set_error("ppenv_ta_sim_create: hipMalloc of the model constants failed");
-        if (s->dev) (void)hipFree(s->dev);
-        delete s;
-        return PPENV_EHIP;
+        return fail(PPENV_EHIP);
     }
-    if (hipHostMalloc((void**)&s->status_host, sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&s->status_dev, s->status_host, 0) != hipSuccess) {
-        ppenv_set_error("ppenv_ta_sim_create: allocating the device status word failed");
-        if (s->status_host) (void)hipHostFree(s->status_host);
-        (void)hipFree(s->dev); (void)hipFree(s->devK);
-        delete s;
-        return PPENV_ENOMEM;
-    }
-    *s->status_host = 0u;
+    if (!s->status.alloc()) { ppenv_set_error("ppenv_ta_sim_create: allocating the device status word failed"); return fail(PPENV_ENOMEM); }
     // pageable host source: the copy is staged before the call returns, the struct may be reused by the caller
     if (hipMemcpyAsync(s->dev, &s->host, sizeof(TAConsts), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess ||
         hipMemcpyAsync(s->devK, &s->K, sizeof(StepConsts), hipMemcpyHostToDevice, (hipStream_t)stream) != hipSuccess) {
-        (void)hipFree(s->dev);
-        (void)hipFree(s->devK);
-        (void)hipHostFree(s->status_host);
-        delete s;
         ppenv_set_error("ppenv_ta_sim_create: uploading the model constants failed");
-        return PPENV_EHIP;
+        return fail(PPENV_EHIP);
     }
     *out = s;
     return PPENV_OK;
@@ -667,10 +638,10 @@ int ppenv_ta_sim_create(const ppenv_config* scene, const ppenv_ta_model* model, 
 
 void ppenv_ta_sim_destroy(ppenv_ta_sim* s) {
     if (!s) return;
-    (void)ta_use_device(s);
+    if (s->device >= 0) (void)hipSetDevice(s->device);   // a handle whose create failed before it chose a device owns nothing there
     if (s->dev) (void)hipFree(s->dev);
     if (s->devK) (void)hipFree(s->devK);
-    if (s->status_host) (void)hipHostFree(s->status_host);
+    s->status.release();
     delete s;
 }
 
@@ -680,7 +651,7 @@ void ppenv_ta_sim_destroy(ppenv_ta_sim* s) {
 int ppenv_ta_sim_set_gravity(ppenv_ta_sim* s, float gravity_z, void* stream) {
     if (!s) { ppenv_set_error("ppenv_ta_sim_set_gravity: NULL handle"); return PPENV_EINVAL; }
     if (!(gravity_z <= 0.f)) { ppenv_set_error("gravity_z must be <= 0 (the world's up axis is z)"); return PPENV_EINVAL; }
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     s->host.sc.gravity_z = gravity_z;
     s->K.gdv = gravity_z * s->K.hb;
     // pageable host sources: staged before the calls return
@@ -695,9 +666,7 @@ int ppenv_ta_sim_set_gravity(ppenv_ta_sim* s, float gravity_z, void* stream) {
 // The kernel ppenv_ta_step launches for this handle now (demangled, as rocprofv3's kernel trace shows it).
 const char* ppenv_ta_sim_kernel_name(const ppenv_ta_sim* s) {
     if (!s) return "";
-    const bool dr = s->dr.dof_stiffness_scale || s->dr.dof_damping_scale || s->dr.link_mass_scale || s->dr.restitution_scale || s->dr.friction_scale ||
-                    s->dr.action_noise_sigma > 0.f || s->dr.observation_noise_sigma > 0.f;
-    if (s->chain) return dr ? "ta_chain_kernel<true>" : "ta_chain_kernel<false>";
+    if (s->chain) return dr_set(s) ? "ta_chain_kernel<true>" : "ta_chain_kernel<false>";
     return s->quad ? "ta_sim_quad_kernel<true, true>" : "ta_sim_kernel<true> + ta_post_physics_kernel";
 }
 
@@ -707,20 +676,18 @@ int ppenv_ta_simulate(ppenv_ta_sim* s, int32_t n, const float* actions_dev, floa
         ppenv_set_error("ppenv_ta_simulate: NULL argument or num_envs <= 0");
         return PPENV_EINVAL;
     }
-    if (s->dr.dof_stiffness_scale || s->dr.dof_damping_scale || s->dr.link_mass_scale || s->dr.restitution_scale || s->dr.friction_scale ||
-        s->dr.action_noise_sigma > 0.f || s->dr.observation_noise_sigma > 0.f) {
+    if (dr_set(s)) {
         ppenv_set_error("ppenv_ta_simulate: a randomisation is set; its tables are read by ppenv_ta_step (the chain-wave kernel) only");
         return PPENV_EINVAL;
     }
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     if (s->quad)
         hipLaunchKernelGGL((ta_sim_quad_kernel<true, false>), dim3((n + kQuadEnvs - 1) / kQuadEnvs), dim3(64), 0, (hipStream_t)stream, s->dev, s->host.sc, s->devK, n, actions_dev,
                            root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev, TaskArgs{});
     else
         hipLaunchKernelGGL(ta_sim_kernel<true>, dim3((n + kTaLanes - 1) / kTaLanes), dim3(kTaLanes), 0, (hipStream_t)stream, s->dev, s->K, n, actions_dev,
                            root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching ta_sim_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching ta_sim_kernel failed");
 }
 
 int ppenv_ta_step(ppenv_ta_sim* s, const ppenv_ta_params* params, const float* actions_dev, const float* initial_rb_states_dev, float* root_states_dev,
@@ -732,15 +699,12 @@ int ppenv_ta_step(ppenv_ta_sim* s, const ppenv_ta_params* params, const float* a
         ppenv_set_error("ppenv_ta_step: NULL argument or num_envs <= 0");
         return PPENV_EINVAL;
     }
-    if (*(volatile uint32_t*)s->status_host != 0u) {
-        ppenv_set_error("ppenv_ta_step: an earlier launch reported a hand-off time-out (status word set): the state tensors of that launch were not stored; destroy the handle");
-        return PPENV_EDEVICE;
-    }
+    if (int rc = s->status.refuse_if_set("ppenv_ta_step: an earlier launch reported a hand-off time-out (status word set): the state tensors of that launch were not stored; destroy the handle")) return rc;
     const int n = params->num_envs;
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     if (s->chain) {   // one lane per env, one wave per limb; rigid_body_states only on request
         TAChainArgs a{*params, s->devK, actions_dev, initial_rb_states_dev, root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev,
-                      reset_override_dev, flags_dev, episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev, scratch_any_reset_dev, s->status_dev,
+                      reset_override_dev, flags_dev, episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev, scratch_any_reset_dev, s->status.dev,
                       s->pin_mean, s->pin_inv_std, s->pin_clip, s->pin_out, s->pin_ld,
                       s->dr.dof_stiffness_scale, s->dr.dof_damping_scale, s->dr.link_mass_scale, s->dr.restitution_scale, s->dr.friction_scale,
                       s->dr.action_noise_sigma, s->dr.observation_noise_sigma};
@@ -758,24 +722,22 @@ int ppenv_ta_step(ppenv_ta_sim* s, const ppenv_ta_params* params, const float* a
                scratch_any_reset_dev};
     hipLaunchKernelGGL((ta_sim_quad_kernel<true, true>), dim3((n + kQuadEnvs - 1) / kQuadEnvs), dim3(64), 0, st, s->dev, s->host.sc, s->devK, n, actions_dev,
                        root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev, t);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching the fused 27-dof step failed"); return PPENV_EHIP; }
+    if (int rc = pp_launched("launching the fused 27-dof step failed")) return rc;
     return ppenv_ta_clear_counts(n, flags_dev, scratch_any_reset_dev, stream);
 }
 
 int ppenv_ta_pd_targets(ppenv_ta_sim* s, int32_t n, const float* actions_dev, float* pd_tar_dev, void* stream) {
     if (!s || n <= 0 || !actions_dev || !pd_tar_dev) { ppenv_set_error("ppenv_ta_pd_targets: NULL argument or num_envs <= 0"); return PPENV_EINVAL; }
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     hipLaunchKernelGGL(ta_pd_targets_kernel, dim3((n * NDOF + 255) / 256), dim3(256), 0, (hipStream_t)stream, s->dev, n, actions_dev, pd_tar_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching ta_pd_targets_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching ta_pd_targets_kernel failed");
 }
 
 int ppenv_ta_serve_from_draws(ppenv_ta_sim* s, const float* draws_dev, int32_t m, float* vel_dev, void* stream) {
     if (!s || m <= 0 || !draws_dev || !vel_dev) { ppenv_set_error("ppenv_ta_serve_from_draws: NULL argument or m <= 0"); return PPENV_EINVAL; }
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     hipLaunchKernelGGL(ta_serve_from_draws_kernel, dim3((m + 255) / 256), dim3(256), 0, (hipStream_t)stream, m, draws_dev, vel_dev);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching ta_serve_from_draws_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching ta_serve_from_draws_kernel failed");
 }
 
 int ppenv_ta_forward_kinematics(ppenv_ta_sim* s, int32_t n, const float* root_states_dev, const float* dof_states_dev, float* rb_states_dev,
@@ -784,7 +746,7 @@ int ppenv_ta_forward_kinematics(ppenv_ta_sim* s, int32_t n, const float* root_st
         ppenv_set_error("ppenv_ta_forward_kinematics: NULL argument or num_envs <= 0");
         return PPENV_EINVAL;
     }
-    if (int rc = ta_use_device(s)) return rc;
+    if (int rc = pp_use_device(s->device)) return rc;
     if (s->quad)
         hipLaunchKernelGGL((ta_sim_quad_kernel<false, false>), dim3((n + kQuadEnvs - 1) / kQuadEnvs), dim3(64), 0, (hipStream_t)stream, s->dev, s->host.sc, s->devK, n,
                            (const float*)nullptr, const_cast<float*>(root_states_dev), const_cast<float*>(dof_states_dev), rb_states_dev,
@@ -793,8 +755,7 @@ int ppenv_ta_forward_kinematics(ppenv_ta_sim* s, int32_t n, const float* root_st
         hipLaunchKernelGGL(ta_sim_kernel<false>, dim3((n + kTaLanes - 1) / kTaLanes), dim3(kTaLanes), 0, (hipStream_t)stream, s->dev, s->K, n,
                            (const float*)nullptr, const_cast<float*>(root_states_dev), const_cast<float*>(dof_states_dev), rb_states_dev,
                            (float*)nullptr, (float*)nullptr);
-    if (hipGetLastError() != hipSuccess) { ppenv_set_error("launching ta_sim_kernel failed"); return PPENV_EHIP; }
-    return PPENV_OK;
+    return pp_launched("launching ta_sim_kernel failed");
 }
 
 }  // extern "C"

@@ -532,6 +532,41 @@ def test_handoff_timeout_is_reported_not_stored(torch_cuda, monkeypatch, schedul
     ok.close()
 
 
+def test_refused_create_leaves_nothing_behind(torch_cuda):
+    """ppenv_create refuses a caller arena that is one byte short, or right in size but 128 bytes off the 256-byte alignment, after it
+    has allocated the handle and its status word: PPENV_EINVAL, the message, *out NULL.  A handle created on the same stream afterwards
+    steps bit for bit like one created before any refusal.  65 envs: one full wave and one lane of the next."""
+    import ctypes as C
+    torch = torch_cuda
+    from isaacgym_amd import _lib
+    n, L = 65, _lib.lib()
+    actions = torch.from_numpy(np.random.default_rng(5).uniform(-1, 1, (n, 7)).astype(np.float32)).cuda()
+
+    def one_step():
+        env = make_env(scene.build_config("TT", num_envs=n, seed=4))
+        env.step(actions)
+        torch.cuda.synchronize()
+        out = env.obs_buf.clone(), env.rew_buf.clone(), env.reset_buf.clone()
+        assert env.status == 0
+        env.close()
+        return out
+
+    want = one_step()
+    cfg = scene.build_config("TT", num_envs=n, seed=4)
+    cfg.device_id = 0
+    nbytes = L.ppenv_arena_bytes(C.byref(cfg))
+    arena = torch.zeros(nbytes + 256, dtype=torch.uint8, device="cuda:0")
+    assert arena.data_ptr() % 256 == 0
+    for ptr, size in ((arena.data_ptr(), nbytes - 1), (arena.data_ptr() + 128, nbytes)):
+        h = C.c_void_p(1)
+        assert L.ppenv_create(C.byref(cfg), ptr, size, _lib.stream(arena), C.byref(h)) == -1      # PPENV_EINVAL
+        assert L.ppenv_last_error().decode() == "arena too small or not 256-byte aligned"
+        assert h.value is None
+    got = one_step()
+    for w, g in zip(want, got):
+        assert torch.equal(w, g)
+
+
 @pytest.mark.parametrize("name", ["quad", "split_g1", "split3", "bogus"])
 def test_unknown_step_kernel_is_refused(torch_cuda, monkeypatch, name):
     """PPENV_STEP_KERNEL accepts split and fused only: a retired schedule or a typo fails at create instead of quietly
