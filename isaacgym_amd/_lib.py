@@ -20,15 +20,19 @@ ROOT = os.path.dirname(_PKG)
 LIB_PATH = os.environ.get("PPENV_LIB", os.path.join(_PKG, "lib", "libppenv.so"))   # PPENV_LIB: profiling builds only
 SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "ppenv_ta.hip"), os.path.join(_PKG, "csrc", "ppenv_ta_sim.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_device.h"), os.path.join(ROOT, "include", "ppenv_play.h"),
+           os.path.join(_PKG, "csrc", "ppenv_ppo_meter_device.h"), os.path.join(ROOT, "include", "ppenv_ppo_meter.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
-# per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf
-SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"]}
+# per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
+# the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one)
+SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"],
+                "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
 _lib = None
 
@@ -97,6 +101,12 @@ class PlayTotals(C.Structure):
     _fields_ = [("games", C.c_int64), ("steps", C.c_int64), ("launches", C.c_int64),
                 ("reward", C.c_double * MAX_AGENTS), ("reward_sq", C.c_double * MAX_AGENTS),
                 ("reward_min", C.c_float * MAX_AGENTS), ("reward_max", C.c_float * MAX_AGENTS)]
+
+
+class PPOMeter(C.Structure):
+    """ctypes mirror of ppenv_ppo_meter (include/ppenv_ppo_meter.h)."""
+    _fields_ = [("mean_reward", C.c_double), ("mean_length", C.c_double), ("current_size", C.c_int64), ("games_total", C.c_int64),
+                ("updates", C.c_int64)]
 
 
 def is_stale():
@@ -296,6 +306,10 @@ def load(path):
     L.ppenv_play_partial_bytes.argtypes = [i32]
     L.ppenv_play_reset.argtypes = [i32, i32, vp, vp, vp, vp]
     L.ppenv_play_accumulate.argtypes = [vp, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    # ---- include/ppenv_ppo_meter.h
+    L.ppo_meter_partial_bytes.restype = sz
+    L.ppo_meter_partial_bytes.argtypes = [i32, i32]
+    L.ppo_meter_update.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp]
     return L
 
 

@@ -25,6 +25,13 @@ Deviations from rl_games:
   - The minibatches are the contiguous row ranges of the horizon-major buffers, in order.
 
 Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
+They also carry "meter" (the score meter's struct) and "last_mean_rewards" (the best score so far); load() accepts files without them.
+
+The score (GameMeter; C ABI: include/ppenv_ppo_meter.h) is rl_games' game_rewards / game_lengths: AverageMeter(games_to_track) over the
+finished games' unscaled returns (agent 0's row of each env) and lengths, updated once per epoch over the collector's horizon by two
+launches.  `fit` is rl_games' loop around train_epoch(): the periodic save to nn/<name>.pth, the best checkpoint from save_best_after on,
+the stop on score_to_win (yaml:63-66).  Two deviations: the meter is fp64 with a fixed summation order (rl_games: fp32 torch), and the
+best checkpoint goes to nn/<name>_best.pth while nn/<name>.pth keeps meaning "latest" (rl_games: best in <name>.pth, latest in last_...).
 
 Data-parallel training (the reference's multi_gpu mode: `torchrun --nproc_per_node=N train.py multi_gpu=True`; rl_games' multi-GPU a2c).  Each
 rank owns an env shard (isaacgym_amd.make(multi_gpu=True)) and a learner; `PPOTrainer(..., group=...)` switches it on when the group has more
@@ -38,6 +45,8 @@ parity unpinned):
     normalisation, minibatch_size;
   - global: the epoch statistics of train_epoch() (loss terms, KL and clip fraction averaged over the ranks; episode sums and counts summed),
     in one all-reduce per epoch, and `frame` (horizon x rows x world).
+  - the score meter is per rank, as in rl_games; train_epoch() returns rank 0's (one 40-byte broadcast per epoch), so every rank takes fit's
+    decisions from the same numbers and all leave the loop in the same epoch.
 Only rank 0 writes checkpoints; load() on every rank reads the same file, so the ranks resume identical — all with rank 0's statistics.
 """
 import argparse
@@ -52,7 +61,7 @@ import torch
 
 from . import _lib
 from . import distributed as D
-from ._lib import PPOAdam, PPOLossArgs, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h (bound in _lib.load)
+from ._lib import PPOAdam, PPOLossArgs, PPOMeter, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h and ppenv_ppo_meter.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
 from .policy import UNITS, NativeActorCritic, RunningMeanStd
 
@@ -60,6 +69,7 @@ HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 STATS = ("loss", "a_loss", "c_loss", "b_loss", "entropy", "kl", "clip_frac")     # ppenv_ppo_loss_grad's stats[] (include/ppenv_ppo.h)
 SOFT_BOUND = 1.1                          # rl_games a2c_continuous.bound_loss
 OPT_PARTS = 512                           # workgroups of the optimizer launches: two per CU
+NO_SCORE = -100500.0                      # rl_games a2c_common: last_mean_rewards before any best checkpoint
 
 
 # ---- configuration ----------------------------------------------------------------------------------------------------------------
@@ -90,6 +100,9 @@ class PPOConfig:
     fixed_sigma: bool = True              # yaml:23
     max_epochs: int = 200000              # yaml:64
     save_frequency: int = 1500            # yaml:66
+    score_to_win: float = 20000.0         # yaml:63
+    save_best_after: int = 3000           # yaml:65
+    games_to_track: int = 100             # rl_games a2c_common default (the yaml does not set it): the score meter's window
     units: tuple = tuple(UNITS)           # yaml:29
     # GradScaler (torch.cuda.amp defaults; rl_games builds it with enabled=mixed_precision)
     init_scale: float = 65536.0
@@ -101,7 +114,8 @@ class PPOConfig:
         "grad_norm": "grad_norm", "truncate_grads": "truncate_grads", "normalize_advantage": "normalize_advantage",
         "normalize_input": "normalize_input", "normalize_value": "normalize_value", "mixed_precision": "mixed_precision",
         "horizon_length": "horizon_length", "mini_epochs": "mini_epochs", "minibatch_size": "minibatch_size", "max_epochs": "max_epochs",
-        "save_frequency": "save_frequency"}
+        "save_frequency": "save_frequency", "score_to_win": "score_to_win", "save_best_after": "save_best_after",
+        "games_to_track": "games_to_track"}
 
     @classmethod
     def from_train_cfg(cls, train, task_cfg=None, **overrides):
@@ -153,6 +167,8 @@ class PPOConfig:
             raise ValueError("fixed_sigma: False is not supported (the network has a learnable, observation-independent log-std)")
         if tuple(self.units) != tuple(UNITS):
             raise ValueError(f"units: {list(self.units)} — the native network is built for {UNITS}")
+        if self.games_to_track < 1:
+            raise ValueError(f"games_to_track: {self.games_to_track} is not a positive number of games (rl_games' default is 100)")
 
 
 # ---- the loss gradient in fp64: what ppenv_ppo_loss_grad computes ------------------------------------------------------------------
@@ -302,6 +318,68 @@ class DeviceAdam:
             self.lr.copy_(sd["lr"])
 
 
+class GameMeter:
+    """rl_games' game_rewards / game_lengths (AverageMeter(games_to_track)) on the device: ppo_meter_update (include/ppenv_ppo_meter.h) on
+    torch tensors.  `cur_reward` [num_envs] f32 and `cur_len` [num_envs] i32 are the envs' running games (agent 0's row of each env), the
+    meter struct holds the two running means, the games they stand for, and the counts.  Nothing here reads the device on the host."""
+
+    def __init__(self, num_envs, num_agents, games_to_track, device):
+        self.num_envs, self.num_agents, self.games_to_track = int(num_envs), int(num_agents), int(games_to_track)
+        if self.num_envs < 1 or self.num_agents not in (1, 2) or self.games_to_track < 1:
+            raise ValueError(f"GameMeter: num_envs {num_envs} (>= 1), num_agents {num_agents} (1 or 2), games_to_track {games_to_track} (>= 1)")
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:                       # tensors carry an index: compare like with like
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.rows = self.num_envs * self.num_agents
+        self.L = _lib.lib()
+        self.cur_reward = torch.zeros(self.num_envs, dtype=torch.float32, device=dev)
+        self.cur_len = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self._meter = torch.zeros(C.sizeof(PPOMeter), dtype=torch.uint8, device=dev)           # all zero: the empty meter
+        self._partial = torch.zeros(0, dtype=torch.uint8, device=dev)                          # grows to the longest horizon seen
+
+    def update(self, rewards, dones):
+        """One horizon: rewards [H, rows] f32 (unscaled), dones [H, rows] int64 — RolloutCollector's buffers or row-strided views of larger
+        ones (unit stride inside a row), on this device.  Two launches, no synchronisation."""
+        if rewards.dim() != 2 or rewards.shape != dones.shape or rewards.shape[0] < 1 or rewards.shape[1] != self.rows or \
+                rewards.dtype != torch.float32 or dones.dtype != torch.int64 or rewards.device != self.device or dones.device != self.device or \
+                (self.rows > 1 and (rewards.stride(1) != 1 or dones.stride(1) != 1)):
+            raise ValueError(f"GameMeter.update: rewards must be float32 and dones int64, [H, {self.rows}] with unit stride inside a row, on {self.device}")
+        h = rewards.shape[0]
+        ld_r, ld_d = (rewards.stride(0), dones.stride(0)) if h > 1 else (self.rows, self.rows)
+        need = int(self.L.ppo_meter_partial_bytes(h, self.num_envs))
+        if self._partial.numel() < need:
+            self._partial = torch.zeros(need, dtype=torch.uint8, device=self.device)
+        _lib.check(self.L.ppo_meter_update(rewards.data_ptr(), ld_r, dones.data_ptr(), ld_d, h, self.num_envs, self.num_agents, self.games_to_track,
+                                           self.cur_reward.data_ptr(), self.cur_len.data_ptr(), self._meter.data_ptr(), self._partial.data_ptr(),
+                                           _lib.stream(self.device)), self.L)
+
+    def snapshot(self):
+        """One copy of the meter struct as it stands at this point of the stream (uint8 [sizeof ppenv_ppo_meter]); fields(snapshot) names it."""
+        return self._meter.clone()
+
+    def fields(self, raw=None):
+        """The meter as 0-dim device tensors: mean_reward, mean_length (fp64), current_size, games_total, updates (int64).  Views of the
+        live struct, which change in place with every update — or of `raw`, a snapshot()."""
+        o, raw = PPOMeter, self._meter if raw is None else raw
+        means, counts = raw[:o.current_size.offset].view(torch.float64), raw[o.current_size.offset:].view(torch.int64)
+        return dict(mean_reward=means[0], mean_length=means[1], current_size=counts[0], games_total=counts[1], updates=counts[2])
+
+    def state_dict(self):
+        """The meter struct only: the envs' running games restart at zero on resume, as the envs themselves do."""
+        return {"meter": self._meter.detach().clone()}
+
+    def load_state_dict(self, sd):
+        with torch.no_grad():
+            self._meter.copy_(sd["meter"])
+            self.cur_reward.zero_()
+            self.cur_len.zero_()
+
+    def state_bytes(self):
+        """cur_reward, cur_len and the meter struct as host bytes (the tests compare them)."""
+        return self.cur_reward.cpu().numpy().tobytes(), self.cur_len.cpu().numpy().tobytes(), self._meter.cpu().numpy().tobytes()
+
+
 # ---- the trainer ------------------------------------------------------------------------------------------------------------------
 def _denorm_(x, rms):
     """rl_games RunningMeanStd(unnorm=True) in place: clamp(+-5), then x sqrt(var + eps) + mean."""
@@ -365,6 +443,8 @@ class PPOTrainer:
         self.steps_per_epoch = cfg.mini_epochs * (total // mb)
         self.stats = z(self.steps_per_epoch, 8)
         self.ep_ret, self.ep_len = z(n), z(n)                              # the running episode of every row (unscaled rewards)
+        self.meter = GameMeter(env.num_envs, n // env.num_envs, cfg.games_to_track, dev)     # rl_games' score: per rank, as in rl_games
+        self.last_mean_rewards = NO_SCORE                                  # the score of the best checkpoint so far (fit)
         self.epoch, self.frame = 0, 0
         if self.multi:
             self._broadcast_start()
@@ -479,11 +559,16 @@ class PPOTrainer:
 
     def train_epoch(self):
         """One epoch; no host synchronisation.  -> dict of 0-dim device tensors: the STATS averaged over the epoch's minibatch steps, the
-        loss scale, the steps skipped in this epoch, the last gradient norm, and the mean return / length of the episodes finished in the
-        horizon (unscaled rewards; 0 when none finished)."""
+        loss scale, the steps skipped in this epoch, the last gradient norm, the mean return / length of the episodes finished in the
+        horizon (unscaled rewards; 0 when none finished), and rl_games' score after this horizon: meter_return / meter_length, the running
+        means of the last meter_games <= games_to_track finished games (agent 0's unscaled return; 0 games: nothing to judge yet).
+        Data-parallel: every rank keeps its own meter, as in rl_games, and every rank returns RANK 0's — the rank that judges and writes
+        the checkpoints — so that the returned statistics are the same on all ranks (one 40-byte broadcast per epoch)."""
         skipped0 = self.opt.fields()["skipped"].clone()
         self.net.train()
         self.collect()
+        self.meter.update(self.col.rewards, self.col.dones)
+        score = self.meter.snapshot()
         ep = self._episodes()
         self.prepare()
         self.learn()
@@ -497,11 +582,15 @@ class PPOTrainer:
             g = torch.cat([mean[:len(STATS)], ep])
             torch.distributed.all_reduce(g, op=torch.distributed.ReduceOp.SUM, group=self.group)
             mean, ep = g[:len(STATS)] / self.world, g[len(STATS):]
+            src = torch.distributed.get_global_rank(self.group, 0) if self.group is not None else 0
+            torch.distributed.broadcast(score, src, group=self.group)
         f = self.opt.fields()
         out = {k: mean[i] for i, k in enumerate(STATS)}
         n = ep[2].clamp(min=1.0)
         out.update(scale=f["scale"], skipped=f["skipped"] - skipped0, grad_norm=f["grad_norm"], episodes=ep[2], mean_return=ep[0] / n,
                    mean_length=ep[1] / n)
+        score = self.meter.fields(score)
+        out.update(meter_return=score["mean_reward"], meter_length=score["mean_length"], meter_games=score["current_size"])
         return out
 
     # -- checkpoints --
@@ -514,7 +603,8 @@ class PPOTrainer:
         # statistics in torch and can differ in the last bit): a resumed run normalises exactly as the uninterrupted one
         stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms))
                  if rms is not None for k in ("mean", "inv_std")}
-        return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats}
+        return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
+                "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards)}
 
     def save(self, path):
         """Data-parallel: rank 0 writes, the other ranks return (their parameters and optimizer state are rank 0's)."""
@@ -550,6 +640,62 @@ class PPOTrainer:
         lr.sync_weights()
         self.opt.load_state_dict(ck["optimizer"])
         self.epoch, self.frame = int(ck["epoch"]), int(ck["frame"])
+        if "meter" in ck:                                                    # checkpoints from before the score meter have neither
+            self.meter.load_state_dict(ck["meter"])
+        self.last_mean_rewards = float(ck.get("last_mean_rewards", NO_SCORE))
+
+
+# ---- the run loop -----------------------------------------------------------------------------------------------------------------
+def fit(trainer, out_dir, name, print_every=10, max_epochs=None):
+    """rl_games' train loop around train_epoch(), restated from its published a2c_common.train (rl_games is absent offline: parity
+    unpinned).  Runs until trainer.epoch reaches max_epochs (default cfg.max_epochs: the TOTAL, so a resumed trainer continues its
+    numbering) or the score wins.  After every epoch, with ONE host read (here, not in train_epoch):
+      - every cfg.save_frequency epochs and at the end: <out_dir>/nn/<name>.pth — the LATEST weights, as before;
+      - when meter_games > 0, meter_return > trainer.last_mean_rewards and epoch >= cfg.save_best_after: last_mean_rewards = meter_return
+        and <out_dir>/nn/<name>_best.pth is written (rl_games writes its best to <name>.pth and its latest to last_<name>...: here the
+        existing file name keeps its meaning);
+      - if that new best also exceeds cfg.score_to_win: <out_dir>/nn/<name>_ep_<epoch>_rew_<meter_return>.pth, and the loop stops.
+    Data-parallel: train_epoch() returns rank 0's score on every rank, so all ranks take the same decisions and leave in the same epoch;
+    rank 0 alone writes (trainer.save).  print_every: rank 0 prints a line every so many epochs and at the end (0: never).
+    -> dict(epochs: run by this call, epoch: the trainer's, stopped, reason: "max_epochs" | "score_to_win", best_score: last_mean_rewards
+    (NO_SCORE while there is no best), paths: dict(latest, best, won: None where not written by this call), written: every path in order)."""
+    cfg = trainer.cfg
+    total = int(cfg.max_epochs if max_epochs is None else max_epochs)
+    nn_dir = os.path.join(out_dir, "nn")
+    paths = dict(latest=None, best=None, won=None)
+    written, ran, stopped = [], 0, False
+    frame0, t0 = trainer.frame, time.perf_counter()
+
+    def save(kind, path):
+        trainer.save(path)                                                   # rank 0 only
+        paths[kind] = path
+        written.append(path)
+
+    while trainer.epoch < total and not stopped:
+        res = trainer.train_epoch()
+        ran += 1
+        epoch = trainer.epoch
+        keys = list(res)
+        vals = dict(zip(keys, torch.stack([res[k].detach().double() for k in keys]).tolist()))     # the epoch's only host read
+        score, games = vals["meter_return"], int(vals["meter_games"])
+        if games > 0 and score > trainer.last_mean_rewards and epoch >= cfg.save_best_after:
+            trainer.last_mean_rewards = score
+            save("best", os.path.join(nn_dir, f"{name}_best.pth"))
+            if score > cfg.score_to_win:
+                save("won", os.path.join(nn_dir, f"{name}_ep_{epoch}_rew_{score}.pth"))
+                stopped = True
+        last = stopped or epoch >= total
+        if epoch % cfg.save_frequency == 0 or last:
+            save("latest", os.path.join(nn_dir, f"{name}.pth"))
+        if print_every and (epoch % print_every == 0 or last) and trainer.rank == 0:
+            dt = time.perf_counter() - t0
+            print(f"epoch {epoch} frames {trainer.frame} fps {(trainer.frame - frame0) / dt:.0f} loss {vals['loss']:.4g} a {vals['a_loss']:.4g} "
+                  f"c {vals['c_loss']:.4g} kl {vals['kl']:.3g} clip {vals['clip_frac']:.3f} scale {vals['scale']:.0f} skipped {vals['skipped']:.0f} "
+                  f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f} score {score:.6g} ({games} games)", flush=True)
+            if stopped:
+                print(f"score {score} above score_to_win {cfg.score_to_win}: stopping", flush=True)
+    return dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
+                best_score=trainer.last_mean_rewards, paths=paths, written=written)
 
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
@@ -583,7 +729,11 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.ppo", description="PPO (rl_games a2c_continuous) on the native env and network")
     ap.add_argument("--task", default="HumanoidPingpongTiltNESSparse27DOFG1")
     ap.add_argument("--num-envs", type=int, default=4096, help="envs per rank with --multi-gpu")
-    ap.add_argument("--max-epochs", type=int, default=None)
+    ap.add_argument("--max-epochs", type=int, default=None, help="the total: a run resumed with --checkpoint continues its epoch numbering up to it")
+    ap.add_argument("--checkpoint", default=None, help="resume from this nn/<task>.pth (every rank loads it)")
+    ap.add_argument("--save-best-after", type=int, default=None, help="no nn/<task>_best.pth before this epoch (yaml: 3000)")
+    ap.add_argument("--score-to-win", type=float, default=None, help="stop once the score exceeds it (yaml: 20000)")
+    ap.add_argument("--games-to-track", type=int, default=None, help="finished games the score is the running mean of (rl_games: 100)")
     ap.add_argument("--minibatch-size", type=int, default=None, help="rows per rank with --multi-gpu")
     ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task and train yamls from")
     ap.add_argument("--out", default=None, help="run directory (default runs/<task>)")
@@ -600,7 +750,8 @@ def main(argv=None):
         rank, dev = init_rank(args.dist_backend, force=args.force_dist)
         seed = args.seed + rank
     import isaacgym_amd
-    over = {k: v for k, v in (("max_epochs", args.max_epochs), ("minibatch_size", args.minibatch_size)) if v is not None}
+    over = {k: v for k, v in (("max_epochs", args.max_epochs), ("minibatch_size", args.minibatch_size), ("save_best_after", args.save_best_after),
+                              ("score_to_win", args.score_to_win), ("games_to_track", args.games_to_track)) if v is not None}
     task_cfg = None
     if args.cfg_dir:
         from . import cfgyaml
@@ -617,25 +768,20 @@ def main(argv=None):
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist)
+    if args.checkpoint:
+        tr.load(args.checkpoint)                                   # every rank: the same file
+        if rank == 0:
+            print(f"resumed {args.checkpoint} at epoch {tr.epoch}, best score {tr.last_mean_rewards}", flush=True)
     out = args.out or os.path.join("runs", args.task)
-    ckpt = os.path.join(out, "nn", f"{args.task}.pth")
-    t0 = time.perf_counter()
-    for e in range(cfg.max_epochs):
-        res = tr.train_epoch()
-        last = e + 1 == cfg.max_epochs
-        if ((e + 1) % args.print_every == 0 or last) and rank == 0:
-            vals = {k: float(v) for k, v in res.items()}           # the only host read
-            dt = time.perf_counter() - t0
-            print(f"epoch {tr.epoch} frames {tr.frame} fps {tr.frame / dt:.0f} loss {vals['loss']:.4g} a {vals['a_loss']:.4g} c {vals['c_loss']:.4g} "
-                  f"kl {vals['kl']:.3g} clip {vals['clip_frac']:.3f} scale {vals['scale']:.0f} skipped {vals['skipped']:.0f} "
-                  f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f}", flush=True)
-        if (e + 1) % cfg.save_frequency == 0 or last:
-            tr.save(ckpt)                                          # rank 0 only
+    done = fit(tr, out, args.task, print_every=args.print_every)
     if rank == 0:
-        print(f"saved {ckpt}" + (f" (ranks: {tr.world}, frames global)" if tr.multi else ""), flush=True)
+        for kind, path in done["paths"].items():
+            if path is not None:
+                print(f"saved {path} ({kind})" + (f" (ranks: {tr.world}, frames global)" if tr.multi else ""), flush=True)
     if args.multi_gpu:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
+    return done
 
 
 if __name__ == "__main__":

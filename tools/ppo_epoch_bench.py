@@ -72,10 +72,13 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
         tr.col.collect().next_horizon()
         for t in range(H):
             tr.learner.rms.update(tr.col.obs[t])
-    tr.collect(); tr.prepare(); tr.learn(); tr.col.next_horizon()          # warm-up
+    def rollout():                 # what train_epoch() does before the learning: the horizon, then the score meter's two launches over it
+        tr.collect()
+        tr.meter.update(tr.col.rewards, tr.col.dones)
+    rollout(); tr.prepare(); tr.learn(); tr.col.next_horizon()             # warm-up
     roll_s = learn_s = 0.0
     for _ in range(args.epochs):
-        dt, _ = timed(tr.collect)
+        dt, _ = timed(rollout)
         roll_s += dt
         dt, _ = timed(lambda: (tr.prepare(), tr.learn()))
         learn_s += dt
