@@ -21,17 +21,19 @@ LIB_PATH = os.environ.get("PPENV_LIB", os.path.join(_PKG, "lib", "libppenv.so"))
 SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "ppenv_ta.hip"), os.path.join(_PKG, "csrc", "ppenv_ta_sim.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_device.h"), os.path.join(ROOT, "include", "ppenv_play.h"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter_device.h"), os.path.join(ROOT, "include", "ppenv_ppo_meter.h"),
+           os.path.join(_PKG, "csrc", "ppenv_render_device.h"), os.path.join(ROOT, "include", "ppenv_render.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
-# the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one)
-SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"],
+# the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);
+# the ray caster's depth of a sky pixel is +inf
+SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
 _lib = None
@@ -107,6 +109,40 @@ class PPOMeter(C.Structure):
     """ctypes mirror of ppenv_ppo_meter (include/ppenv_ppo_meter.h)."""
     _fields_ = [("mean_reward", C.c_double), ("mean_length", C.c_double), ("current_size", C.c_int64), ("games_total", C.c_int64),
                 ("updates", C.c_int64)]
+
+
+RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
+RENDER_SPHERE, RENDER_CAPSULE, RENDER_BOX, RENDER_CYLINDER, RENDER_BONE = range(5)
+RENDER_ID_SKY, RENDER_ID_GROUND = -1, -2
+
+
+class RenderSource(C.Structure):
+    """ctypes mirror of pp_render_source (include/ppenv_render.h)."""
+    _fields_ = [("base", C.c_void_p), ("env_stride", C.c_int64), ("row_stride", C.c_int64), ("rows", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RenderPrim(C.Structure):
+    """ctypes mirror of pp_render_prim."""
+    _fields_ = [("kind", C.c_int32), ("source", C.c_int32), ("row", C.c_int32), ("row2", C.c_int32), ("a", C.c_float * 3), ("b", C.c_float * 3),
+                ("radius", C.c_float), ("albedo", C.c_float * 3)]
+
+
+class RenderPosed(C.Structure):
+    """ctypes mirror of pp_render_posed: 20 words."""
+    _fields_ = [("a", C.c_float * 3), ("radius", C.c_float), ("b", C.c_float * 3), ("kind", C.c_int32), ("axis", C.c_float * 9), ("albedo", C.c_float * 3)]
+
+
+class RenderScene(C.Structure):
+    """ctypes mirror of pp_render_scene."""
+    _fields_ = [("num_envs", C.c_int32), ("num_prims", C.c_int32), ("num_sources", C.c_int32), ("checker", C.c_int32),
+                ("source", RenderSource * RENDER_MAX_SOURCES), ("ground_z", C.c_float), ("checker_pitch", C.c_float),
+                ("ground_rgb", (C.c_float * 3) * 2), ("sky_rgb", C.c_float * 3), ("light", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float)]
+
+
+class RenderCamera(C.Structure):
+    """ctypes mirror of pp_render_camera."""
+    _fields_ = [("eye", C.c_float * 3), ("target", C.c_float * 3), ("up", C.c_float * 3), ("fov_deg", C.c_float), ("width", C.c_int32),
+                ("height", C.c_int32), ("follow_source", C.c_int32), ("follow_row", C.c_int32)]
 
 
 def is_stale():
@@ -310,6 +346,11 @@ def load(path):
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]
     L.ppo_meter_update.argtypes = [vp, i64, vp, i64, i32, i32, i32, i64, vp, vp, vp, vp, vp]
+    # ---- include/ppenv_render.h
+    scenep = C.POINTER(RenderScene)
+    L.pp_render_scene_upload.argtypes = [scenep, C.POINTER(RenderPrim), vp, vp]
+    L.pp_render_pose.argtypes = [scenep, vp, vp, i32, vp, vp]
+    L.pp_render_rays.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, vp, vp, vp, vp]
     return L
 
 

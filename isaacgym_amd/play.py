@@ -3,7 +3,7 @@
 
     Player(task, policy, games_num=2000).run()      games_num episodes of `task` under `policy` -> rl_games' numbers (average return,
                                                     average episode length) plus spread
-    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth
+    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --camera side]
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -21,7 +21,8 @@ controlFrequencyInv and both domain-randomisation modes behave as for any caller
 randomisation (evaluation; PPOTrainer's refusal of such a task is about training below that surface and is untouched).
 
 Out of scope: capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
-`Runner` / `player_factory` shim (rl_games itself is absent); video capture; the observer, PBT and W&B hooks.
+`Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
+`--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
 """
 import argparse
 import ctypes as C
@@ -119,7 +120,7 @@ class Player:
     sigma: train.py:214's override — the policy's log-std is filled with it, so sigma = exp(x) (rl_games' _override_sigma for a fixed
     sigma); it matters only with deterministic=False."""
 
-    def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None):
+    def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -138,6 +139,9 @@ class Player:
         if sigma is not None:
             policy.sigma.fill_(math.exp(float(sigma)))
         self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
+        if recorder is not None and recorder.renderer.task is not task:
+            raise ValueError("the recorder renders another task")
+        self.recorder = recorder
         self.steps_played = 0
         self.actions = None
         self._obs = None
@@ -157,6 +161,8 @@ class Player:
         self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
         obs, rew, done, _ = self.task.step(self.actions)
         self.stats.accumulate(rew, done)
+        if self.recorder is not None:
+            self.recorder.capture()
         self._obs = obs["obs"]
         self.steps_played += 1
 
@@ -181,6 +187,8 @@ class Player:
                 on_poll(tot)
         out = summarize(tot, self.num_agents)
         out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
+        if self.recorder is not None:
+            out["captured_frames"] = self.recorder.captured
         return out
 
 
@@ -197,7 +205,28 @@ def parse_args(argv=None):
     ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task yaml from")
     ap.add_argument("--poll-every", type=int, default=64, help="control steps between two host reads of the totals")
     ap.add_argument("--max-steps", type=int, default=108000)
+    ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
+    ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
+    ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
+    ap.add_argument("--capture-every", type=int, default=2, help="control steps between two frames")
+    ap.add_argument("--capture-size", default="640x480", help="WIDTHxHEIGHT of one env's picture")
+    ap.add_argument("--capture-fps", type=float, default=30.0)
+    ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
     return ap.parse_args(argv)
+
+
+def make_recorder(task, args):
+    """The Recorder of the --capture* options."""
+    from . import render
+    try:
+        width, height = (int(v) for v in args.capture_size.lower().split("x"))
+        envs = [int(v) for v in args.capture_envs.split(",")]
+    except ValueError as e:
+        raise SystemExit(f"--capture-size is WIDTHxHEIGHT and --capture-envs a comma-separated list of env ids: {e}")
+    renderer = render.Renderer(task, envs=envs, width=width, height=height)
+    if args.camera == "follow":
+        renderer.set_camera(render.Camera.follow_root(renderer.scene))
+    return render.Recorder(renderer, length=args.capture_len, every=args.capture_every)
 
 
 def main(argv=None):
@@ -210,8 +239,9 @@ def main(argv=None):
         task_cfg = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})["task"]
     task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
+    recorder = make_recorder(task, args) if args.capture else None
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
-                max_steps=args.max_steps, sigma=args.sigma)
+                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder)
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -225,6 +255,10 @@ def main(argv=None):
     for a, p in enumerate(res["per_agent"]):
         print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
+    if recorder is not None:
+        files = recorder.save(args.capture, fps=args.capture_fps)
+        print(f"captured {res['captured_frames']} frames, kept the last {min(res['captured_frames'], recorder.length)}: {files[0]}" +
+              (f" .. {files[-1]}" if len(files) > 1 else ""), flush=True)
     return res
 
 

@@ -1,0 +1,410 @@
+"""Render envs on the GPU and record a played checkpoint (C ABI: include/ppenv_render.h).
+
+    Scene.from_config(task_name)     host only: the primitives of a task's scene from its native config and the G1 body tree
+    Scene.from_task(task)            ... plus the pose tensors of a live task
+    Camera.side_view(scene) / Camera.follow_root(scene)
+    Renderer(task, envs=(0,), width=640, height=480).render()     -> uint8 [E, H, W, 4] on the device, two launches, no host read
+    Recorder(renderer, length=100, every=1).capture() / .save("out.gif")
+
+WHAT IS DRAWN is the project's own UNVERIFIED collision geometry (scene.py: the capsules and spheres the ball collides with, the paddle
+disc, the table slab, the net, the ball) plus a stick figure: one thin capsule ("bone") per parent-child pair of the G1 body tree
+between the two bodies' origins.  No meshes, no textures, no anti-aliasing.  For the 7-dof tasks `rigid_body_states` carries the
+pelvis and the right arm chain only (every other body row sits at the root pose), so their stick figure is the arm; the torso, pelvis
+and head appear as their world-fixed collision shapes.
+
+Rows.  `rigid_body_states` is [N, 40 * A + 2, 13] for the 7-dof tasks (A humanoids, then table and ball) and [N, 42, 13] for the
+27-dof task; row 40 * h + G1_BODY_NAMES.index(name) is body `name` of humanoid h.  `root_states` is [N, A + 2, 13]: humanoids, table,
+ball.  A collision shape hangs on a LINK index of the native model, mapped to its body row BY NAME:
+    7-dof tasks    arm link j      -> scene.G1_RIGHT_ARM[j]["name"]  (right_shoulder_pitch_link .. right_wrist_yaw_link: rows 31 .. 37)
+    27-dof task    tree link l     -> TA_LINK_NAMES[l]                (pelvis, legs, waist, left arm, the five right-arm links)
+    link -1                        -> world-fixed (scene.build_config writes such shapes in world coordinates)
+
+Out of scope: capture during training (the collector drives the native handle below VecTask), meshes / textures / anti-aliasing, mp4.
+"""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+
+from . import _lib, scene, urdf
+from ._lib import (RENDER_BONE, RENDER_BOX, RENDER_CAPSULE, RENDER_CYLINDER, RENDER_ID_GROUND, RENDER_ID_SKY, RENDER_MAX_ENVS,  # noqa: F401
+                   RENDER_MAX_PRIMS, RENDER_SPHERE, RenderCamera, RenderPosed, RenderPrim, RenderScene)
+
+SRC_RB, SRC_ROOT = 0, 1                     # pp_render_scene.source[]: rigid_body_states, root_states
+BONE_RADIUS = 0.02
+# shading constants
+LIGHT = (0.3, -0.4, 0.85)
+AMBIENT, DIFFUSE = 0.35, 0.65
+SKY = (0.55, 0.70, 0.90)
+GROUND = ((0.55, 0.55, 0.55), (0.40, 0.40, 0.40))
+CHECKER_PITCH = 1.0
+COLORS = dict(bone=(0.78, 0.78, 0.82), shape=(0.25, 0.45, 0.85), shape2=(0.90, 0.55, 0.20), paddle=(0.80, 0.10, 0.10), table=(0.10, 0.35, 0.20),
+              net=(0.92, 0.92, 0.92), ball=(1.00, 0.60, 0.10))
+MAX_RING_BYTES = 2 << 30
+
+
+def _ta_link_names():
+    """The 28 links of the 27-dof tree in scene.build_ta_model's order."""
+    arm = [s["name"] for s in scene.G1_RIGHT_ARM]
+    return (["pelvis"] + [s["name"] for s in scene._leg("left")] + [s["name"] for s in scene._leg("right")] + [s["name"] for s in scene.G1_WAIST] +
+            [s["name"] for s in (scene._mirror_arm(s) for s in scene.G1_RIGHT_ARM)] + [arm[0], arm[1], arm[4], arm[5], arm[6]])
+
+
+TA_LINK_NAMES = _ta_link_names()
+
+
+def _rot_to_quat(r):
+    """3x3 rotation -> xyzw."""
+    t = np.trace(r)
+    if t > 0:
+        s = math.sqrt(t + 1.0) * 2
+        q = ((r[2, 1] - r[1, 2]) / s, (r[0, 2] - r[2, 0]) / s, (r[1, 0] - r[0, 1]) / s, 0.25 * s)
+    else:
+        i = int(np.argmax(np.diag(r)))
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = math.sqrt(1.0 + r[i, i] - r[j, j] - r[k, k]) * 2
+        q = [0.0] * 4
+        q[i], q[j], q[k], q[3] = 0.25 * s, (r[j, i] + r[i, j]) / s, (r[k, i] + r[i, k]) / s, (r[k, j] - r[j, k]) / s
+    return np.asarray(q)
+
+
+def _axis_rot(axis, angle):
+    a = np.asarray(axis, dtype=np.float64)
+    a = a / np.linalg.norm(a)
+    k = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    return np.eye(3) + math.sin(angle) * k + (1 - math.cos(angle)) * (k @ k)
+
+
+def body_poses(robot, root_pos, root_quat, dof_pos=None):
+    """Forward kinematics of the parsed body tree on the host: [40, 7] (position, quaternion xyzw) in G1_BODY_NAMES' order.
+    dof_pos: {joint name: angle}, default all zero."""
+    dof_pos = dof_pos or {}
+    pose = {robot.root(): (np.asarray(root_pos, np.float64), scene.quat_to_rot(np.asarray(root_quat, np.float64)))}
+    pending = list(robot.joints.values())
+    while pending:
+        rest = []
+        for j in pending:
+            if j.parent not in pose:
+                rest.append(j)
+                continue
+            p, r = pose[j.parent]
+            rc = r @ scene.rpy_to_rot(*j.rpy)
+            if j.type != "fixed":
+                rc = rc @ _axis_rot(j.axis, float(dof_pos.get(j.name, 0.0)))
+            pose[j.child] = (p + r @ j.xyz, rc)
+        assert len(rest) < len(pending), "the joints do not form a tree"
+        pending = rest
+    return np.stack([np.concatenate([pose[n][0], _rot_to_quat(pose[n][1])]) for n in urdf.G1_BODY_NAMES])
+
+
+class Scene:
+    """The primitives of one task's scene (host data) and, after from_task, their device copy and pose sources."""
+
+    def __init__(self, task_name):
+        self.task_name = task_name
+        self.variant = scene.TASK_VARIANTS[task_name]
+        self.prims = []                       # dicts: kind, source, row, row2, a, b, radius, albedo, name
+        self.source_rows = [0, 0]             # rows per env of rigid_body_states / root_states
+        self.ground_z, self.checker, self.checker_pitch = 0.0, True, CHECKER_PITCH
+        self.ground_rgb, self.sky_rgb = GROUND, SKY
+        light = np.asarray(LIGHT, np.float64)
+        self.light = tuple(light / np.linalg.norm(light))
+        self.ambient, self.diffuse = AMBIENT, DIFFUSE
+        self.header, self.prims_dev, self.sources = None, None, None
+
+    def add(self, kind, name, albedo, source=0, row=-1, row2=-1, a=(0, 0, 0), b=(0, 0, 0), radius=0.0):
+        self.prims.append(dict(kind=int(kind), name=name, source=int(source), row=int(row), row2=int(row2), a=tuple(float(v) for v in a),
+                               b=tuple(float(v) for v in b), radius=float(radius), albedo=tuple(float(v) for v in albedo)))
+
+    # ---- host
+    @classmethod
+    def from_config(cls, task_name, cfg=None):
+        """The scene of a task by its registry name; cfg: its task cfg dict (`env`, `sim`, `scene`; default the yaml defaults).  No GPU."""
+        self = cls(task_name)
+        v = self.variant
+        cfg = scene.default_task_cfg(v) if cfg is None else {k: (dict(x) if isinstance(x, dict) else x) for k, x in cfg.items()}
+        defaults = scene.default_task_cfg(v)
+        for key in ("sim", "scene"):
+            cfg.setdefault(key, defaults[key])
+        cfg["env"] = dict(defaults["env"], **(cfg.get("env") or {}))
+        cfg["env"]["bodyStatesId"] = defaults["env"]["bodyStatesId"]          # which bodies are OBSERVED: nothing that is drawn depends on it
+        table, ball = scene.asset_geometry(cfg["scene"])
+        if v == "TA":
+            c = scene.build_ta_scene(1, table=table, ball=ball)
+            env_keys = ("episodeLength", "alphaVelocityReward", "powerCoefficient", "hitTableReward", "nothitTablePenalty", "crossNetRewardFloat",
+                        "diePenaltyFloat", "hitPaddleReward", "missPaddlePenaltyCoefficient")
+            params = scene.build_ta_params(1, env={k: cfg["env"][k] for k in env_keys if k in cfg["env"]})
+            model = scene.build_ta_model()
+            link_row = [urdf.G1_BODY_NAMES.index(n) for n in TA_LINK_NAMES]
+            assert link_row == [model.link[i].body for i in range(scene.TA_NUM_LINKS)], "TA_LINK_NAMES does not follow scene.build_ta_model"
+            self.ground_z = float(model.ground_z)
+            self._rest = dict(roots=[np.asarray(list(params.init_root[0])[:7])], table=np.asarray(list(params.init_root[1])[:7]),
+                              ball=np.asarray(list(params.init_root[2])[:7]),
+                              dof=dict(zip(urdf.ta_dof_joint_names(), [float(params.init_dof_pos[d]) for d in range(scene.TA_NUM_DOF)])))
+        else:
+            c = scene.build_config(v, cfg=cfg, num_envs=1, table=table, ball=ball)
+            link_row = [urdf.G1_BODY_NAMES.index(s["name"]) for s in scene.G1_RIGHT_ARM]
+            self.ground_z = float(c.ground_z)
+            roots = [np.asarray(list(c.humanoid_root_pos) + list(c.humanoid_root_quat))]
+            if c.num_humanoids == 2:
+                roots.append(np.asarray(list(c.humanoid2_root_pos) + list(c.humanoid2_root_quat)))
+            self._rest = dict(roots=roots, table=np.asarray(list(c.table_root_pos) + list(c.table_root_quat)),
+                              ball=np.asarray(list(c.ball_init_pos) + list(c.ball_init_quat)), dof={})
+        self.config = c
+        A = self.num_humanoids = int(c.num_humanoids) if v != "TA" else 1
+        nb = scene.NUM_HUMANOID_BODIES
+        self.source_rows = [A * nb + 2, A + 2]
+        self.robot = urdf.parse(urdf.write_g1_urdf(weld_right_elbow=(v == "TA")))
+        self.table_top_z = float(c.table.center[2] + c.table.half[2])
+        self.root_rows, self.ball_row = list(range(A)), A + 1
+
+        self.add(RENDER_BOX, "table", COLORS["table"], a=list(c.table.center), b=list(c.table.half))
+        self.add(RENDER_BOX, "net", COLORS["net"], a=list(c.net.center), b=list(c.net.half))
+        self.add(RENDER_SPHERE, "ball", COLORS["ball"], source=SRC_ROOT, row=self.ball_row, radius=float(c.ball_radius))
+        self.bones = []
+        for h in range(A):
+            for j in self.robot.joints.values():
+                pr, ch = h * nb + urdf.G1_BODY_NAMES.index(j.parent), h * nb + urdf.G1_BODY_NAMES.index(j.child)
+                self.bones.append((pr, ch))
+                self.add(RENDER_BONE, f"bone{h}:{j.child}", COLORS["bone"], source=SRC_RB, row=pr, row2=ch, radius=BONE_RADIUS)
+            shapes = c.shape if h == 0 else c.shape2
+            for k in range(c.num_shapes):
+                s = shapes[k]
+                a, b = list(s.a), list(s.b)
+                row = h * nb + link_row[s.link] if s.link >= 0 else -1
+                self.add(RENDER_SPHERE if a == b else RENDER_CAPSULE, f"shape{h}:{k}", COLORS["shape" if h == 0 else "shape2"], source=SRC_RB, row=row,
+                         a=a, b=b, radius=float(s.radius))
+            pc, pn = np.asarray(list(c.paddle_center)), np.asarray(list(c.paddle_normal))
+            self.add(RENDER_CYLINDER, f"paddle{h}", COLORS["paddle"], source=SRC_RB, row=h * nb + link_row[c.paddle_link],
+                     a=pc - pn * c.paddle_half_thickness, b=pc + pn * c.paddle_half_thickness, radius=float(c.paddle_radius))
+        if len(self.prims) > RENDER_MAX_PRIMS:
+            raise ValueError(f"{len(self.prims)} primitives; the ray caster takes at most {RENDER_MAX_PRIMS}")
+        return self
+
+    def rest_states(self):
+        """(rigid_body_states [1, rows, 13], root_states [1, A + 2, 13]) float32 at the task's reset pose, on the host — laid out as the
+        device tensors are (for the 7-dof tasks every body row but the pelvis and the right arm chain sits at the root pose)."""
+        A, nb = self.num_humanoids, scene.NUM_HUMANOID_BODIES
+        rb = np.zeros((1, self.source_rows[0], 13), np.float32)
+        root = np.zeros((1, self.source_rows[1], 13), np.float32)
+        for h, r in enumerate(self._rest["roots"]):
+            poses = body_poses(self.robot, r[:3], r[3:7], self._rest["dof"])
+            if self.variant != "TA":
+                keep = [0] + list(range(31, 40))
+                rows = np.tile(np.concatenate([r[:3], r[3:7] / np.linalg.norm(r[3:7])]), (nb, 1))
+                rows[keep] = poses[keep]
+                poses = rows
+            rb[0, h * nb:(h + 1) * nb, :7] = poses
+            root[0, h, :7] = r
+        rb[0, A * nb, :7] = root[0, A, :7] = self._rest["table"]
+        rb[0, A * nb + 1, :7] = root[0, A + 1, :7] = self._rest["ball"]
+        return rb, root
+
+    def prim_array(self):
+        arr = (RenderPrim * max(len(self.prims), 1))()
+        for p, d in zip(arr, self.prims):
+            p.kind, p.source, p.row, p.row2, p.radius = d["kind"], d["source"], d["row"], d["row2"], d["radius"]
+            p.a[:], p.b[:], p.albedo[:] = d["a"], d["b"], d["albedo"]
+        return arr
+
+    def header_for(self, num_envs, sources):
+        """pp_render_scene for pose tensors `sources`: [(address, env stride, row stride, rows)] in floats."""
+        h = RenderScene()
+        h.num_envs, h.num_prims, h.num_sources, h.checker = int(num_envs), len(self.prims), len(sources), int(self.checker)
+        for s, (base, es, rs, rows) in zip(h.source, sources):
+            s.base, s.env_stride, s.row_stride, s.rows = base, es, rs, rows
+        h.ground_z, h.checker_pitch = self.ground_z, self.checker_pitch
+        for k in range(2):
+            h.ground_rgb[k][:] = self.ground_rgb[k]
+        h.sky_rgb[:], h.light[:] = self.sky_rgb, self.light
+        h.ambient, h.diffuse = self.ambient, self.diffuse
+        return h
+
+    # ---- device
+    @classmethod
+    def from_task(cls, task):
+        """from_config of a live task (isaacgym_amd.make) + its pose tensors + the device copy of the primitives."""
+        import torch
+        name = {v: k for k, v in scene.TASK_VARIANTS.items()}[task.VARIANT]
+        self = cls.from_config(name, task.cfg)
+        self.task, dev, n = task, task.device, task.num_envs
+        self.L = task.env.L if hasattr(task.env, "L") else task.env.sim.L
+        self.rb = torch.zeros((n, self.source_rows[0], 13), dtype=torch.float32, device=dev)      # the renderer's own: no env tensor is written
+        if task.VARIANT == "TA":
+            self.root = task.env.root_states                                                         # used as it is
+        else:
+            self.root = torch.zeros((n, self.source_rows[1], 13), dtype=torch.float32, device=dev)
+        self.sources = [(t.data_ptr(), t.stride(0), t.stride(1), t.shape[1]) for t in (self.rb, self.root)]
+        self.header = self.header_for(n, self.sources)
+        self.prims_dev = torch.zeros(max(len(self.prims), 1) * C.sizeof(RenderPrim), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self.L.pp_render_scene_upload(C.byref(self.header), self.prim_array(), self.prims_dev.data_ptr(), _lib.stream(dev)), self.L)
+            torch.cuda.current_stream(dev).synchronize()         # once: the host array must outlive the copy
+        return self
+
+    def refresh(self):
+        """The pose tensors of the current state: launches only.  7-dof tasks: the gym.refresh_* kernels into the renderer's own tensors;
+        27-dof task: forward kinematics of the current root / dof states (TAEnv.rb_states' kernel) into the renderer's own tensor."""
+        t, s = self.task, _lib.stream(self.task.device)
+        if t.VARIANT == "TA":
+            t.env.sim.forward_kinematics(t.env.root_states, t.env.dof_states, self.rb)
+        else:
+            _lib.check(self.L.ppenv_refresh_rigid_body_states(t.env.h, self.rb.data_ptr(), s), self.L)
+            _lib.check(self.L.ppenv_refresh_root_states(t.env.h, self.root.data_ptr(), s), self.L)
+
+
+class Camera:
+    """eye, target, up, vertical field of view.  follow: (source, row) of a body whose x and y (not z) are added to eye and target on the
+    device, per env — eye and target are then offsets in x, y and absolute in z."""
+
+    def __init__(self, eye, target, up=(0, 0, 1), fov_deg=45, follow=None):
+        self.eye, self.target, self.up = (np.asarray(v, np.float64) for v in (eye, target, up))
+        self.fov_deg, self.follow = float(fov_deg), follow
+        f, r, u = self.basis()
+        if not (np.isfinite(f).all() and np.isfinite(r).all() and 0 < self.fov_deg < 180):
+            raise ValueError("Camera: eye == target, up along the view direction, or a field of view outside (0, 180)")
+
+    def basis(self):
+        """(forward, right, up) — orthonormal."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            f = (self.target - self.eye) / np.linalg.norm(self.target - self.eye)
+            r = np.cross(f, self.up)
+            r = r / np.linalg.norm(r)
+        return f, r, np.cross(r, f)
+
+    def eye_target(self, body_xyz=None):
+        """What the device uses for a followed body at body_xyz: x and y added, z not."""
+        if self.follow is None or body_xyz is None:
+            return self.eye.copy(), self.target.copy()
+        d = np.array([body_xyz[0], body_xyz[1], 0.0])
+        return self.eye + d, self.target + d
+
+    def struct(self, width, height):
+        c = RenderCamera()
+        c.eye[:], c.target[:], c.up[:] = self.eye, self.target, self.up
+        c.fov_deg, c.width, c.height = self.fov_deg, int(width), int(height)
+        c.follow_source, c.follow_row = self.follow if self.follow is not None else (0, -1)
+        return c
+
+    @classmethod
+    def side_view(cls, sc, fov_deg=45):
+        """The table and the humanoid(s) from the side and above, about 45 degrees down (a 4:3 picture holds them; the horizon stays out of
+        the picture, where a one-sample checker would alias)."""
+        c = sc.config
+        xs = [r[0] for r in sc._rest["roots"]] + [c.table.center[0] - c.table.half[0], c.table.center[0] + c.table.half[0]]
+        lo, hi = min(xs) - 0.6, max(xs) + 0.6
+        half_h = math.tan(math.radians(fov_deg) / 2) * 4.0 / 3.0
+        dist = 0.5 * (hi - lo) / half_h + c.table.half[1]
+        cx = 0.5 * (lo + hi)
+        return cls((cx, -0.8 * dist, 4.0), (cx, 0.0, 0.3), fov_deg=fov_deg)
+
+    @classmethod
+    def follow_root(cls, sc, fov_deg=45):
+        """The reference viewer's initial follow-cam (TT:1068-1096): eye = root + (0, -3, .) at height 1.0, target = root at height 1.0."""
+        return cls((0.0, -3.0, 1.0), (0.0, 0.0, 1.0), fov_deg=fov_deg, follow=(SRC_ROOT, 0))
+
+
+class Renderer:
+    def __init__(self, task, envs=(0,), width=640, height=480, camera=None, depth=False, ids=False):
+        import torch
+        envs = [int(e) for e in envs]
+        if not 1 <= len(envs) <= RENDER_MAX_ENVS or min(envs) < 0 or max(envs) >= task.num_envs:
+            raise ValueError(f"Renderer: 1 .. {RENDER_MAX_ENVS} env ids inside [0, {task.num_envs}), got {envs}")
+        if int(width) < 1 or int(height) < 1:
+            raise ValueError(f"Renderer: width x height must be positive, got {width} x {height}")
+        self.task, self.envs, self.width, self.height = task, envs, int(width), int(height)
+        self.scene = Scene.from_task(task)
+        self.L, dev, E = self.scene.L, task.device, len(envs)
+        self.device = dev
+        self.env_ids = torch.tensor(envs, dtype=torch.int32, device=dev)
+        self.posed = torch.zeros((E, max(len(self.scene.prims), 1), C.sizeof(RenderPosed) // 4), dtype=torch.float32, device=dev)
+        self.rgba = torch.zeros((E, self.height, self.width, 4), dtype=torch.uint8, device=dev)
+        self.depth = torch.zeros((E, self.height, self.width), dtype=torch.float32, device=dev) if depth else None
+        self.ids = torch.zeros((E, self.height, self.width), dtype=torch.int32, device=dev) if ids else None
+        self.set_camera(camera if camera is not None else Camera.side_view(self.scene))
+
+    def set_camera(self, camera):
+        self.camera, self._cam = camera, camera.struct(self.width, self.height)
+
+    def render(self, out=None):
+        """The selected envs as they are now -> uint8 [E, H, W, 4] on the device (`out`, default the renderer's own tensor, rewritten by
+        every call; depth / ids, when asked for, land in .depth / .ids).  Launches only: nothing is read on the host, no env state changes."""
+        out = self.rgba if out is None else out
+        if out.dtype != self.rgba.dtype or out.shape != self.rgba.shape or not out.is_contiguous() or out.device != self.rgba.device:
+            raise ValueError(f"Renderer.render: out must be a contiguous uint8 {tuple(self.rgba.shape)} tensor on {self.device}")
+        sc, s = self.scene, _lib.stream(self.device)
+        sc.refresh()
+        _lib.check(self.L.pp_render_pose(C.byref(sc.header), sc.prims_dev.data_ptr(), self.env_ids.data_ptr(), len(self.envs), self.posed.data_ptr(), s), self.L)
+        _lib.check(self.L.pp_render_rays(C.byref(sc.header), C.byref(self._cam), self.posed.data_ptr(), self.env_ids.data_ptr(), len(self.envs),
+                                         out.data_ptr(), _lib.ptr(self.depth), _lib.ptr(self.ids), s), self.L)
+        return out
+
+
+def ring_schedule(calls, length, every):
+    """The Recorder's arithmetic: of `calls` capture() calls (0-based k) those with k % every == 0 render, into slot (k // every) % length.
+    -> (frames rendered, [call index of each kept frame, oldest first])."""
+    rendered = [k for k in range(calls) if k % every == 0]
+    return len(rendered), rendered[-length:]
+
+
+class Recorder:
+    """The last `length` rendered frames in a device ring [length, E, H, W, 4]; capture() once per control step renders every `every`-th call."""
+
+    def __init__(self, renderer, length=100, every=1):
+        import torch
+        if int(length) < 1 or int(every) < 1:
+            raise ValueError(f"Recorder: length {length} and every {every} must be positive")
+        self.renderer, self.length, self.every = renderer, int(length), int(every)
+        nbytes = self.length * renderer.rgba.numel()
+        if nbytes > MAX_RING_BYTES:
+            raise ValueError(f"Recorder: a ring of {self.length} frames of {tuple(renderer.rgba.shape)} is {nbytes} bytes, more than "
+                             f"{MAX_RING_BYTES} (2 GiB): shorten it, pick fewer envs or a smaller picture")
+        self.ring = torch.zeros((self.length,) + tuple(renderer.rgba.shape), dtype=torch.uint8, device=renderer.device)
+        self.calls = self.captured = 0
+
+    def capture(self):
+        if self.calls % self.every == 0:
+            self.renderer.render(out=self.ring[self.captured % self.length])
+            self.captured += 1
+        self.calls += 1
+
+    def frames(self):
+        """The kept frames, oldest first: [T, E, H, W, 4] on the device, T = min(captured, length)."""
+        if self.captured <= self.length:
+            return self.ring[:self.captured]
+        at = self.captured % self.length
+        return self.ring.roll(-at, 0) if at else self.ring
+
+    def save(self, path, fps=30):
+        """The one host copy.  Envs side by side; *.gif (one file), *.png (numbered files <stem>_0000.png ...) through PIL, *.npy
+        ([T, H, E * W, 3] uint8) without it.  -> the list of files written."""
+        return save_frames(self.frames().cpu().numpy(), path, fps)
+
+
+def save_frames(frames, path, fps=30):
+    """frames: uint8 [T, E, H, W, 4] on the host."""
+    frames = np.asarray(frames)
+    T, E, H, W, _ = frames.shape
+    tiled = np.ascontiguousarray(frames[..., :3].transpose(0, 2, 1, 3, 4).reshape(T, H, E * W, 3))
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npy":
+        np.save(path, tiled)
+        return [path]
+    if ext not in (".gif", ".png"):
+        raise ValueError(f"{path}: the capture formats are .gif, .png and .npy")
+    if T == 0:
+        raise ValueError("no frame was captured")
+    try:
+        from PIL import Image
+    except ImportError as e:
+        raise RuntimeError(f"{path}: writing {ext} needs PIL, which is not installed; save to a .npy path instead") from e
+    images = [Image.fromarray(f, "RGB") for f in tiled]
+    if ext == ".gif":
+        images[0].save(path, save_all=True, append_images=images[1:], duration=max(int(round(1000.0 / fps)), 10), loop=0)
+        return [path]
+    stem = os.path.splitext(path)[0]
+    names = [f"{stem}_{k:04d}.png" for k in range(T)]
+    for im, name in zip(images, names):
+        im.save(name)
+    return names

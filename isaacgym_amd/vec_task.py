@@ -54,11 +54,12 @@ class VecTask:
         self.device_id = self.device.index
         self.rl_device = torch.device(rl_device) if rl_device is not None else self.device
         self.graphics_device_id = graphics_device_id
-        self.headless = True          # no viewer: rendering is out of scope
+        self.headless = True          # no viewer window; render() draws env 0 on the GPU (isaacgym_amd.render)
         self.viewer = None
         self.enable_viewer_sync = False
         self.force_render = force_render
         self.physics_engine = "ppenv"
+        self._renderer = None
 
         self.num_envs = int(env_cfg["numEnvs"])
         self.num_agents = int(getattr(self, "NUM_AGENTS", 1))   # rl_games multi-agent convention: batch rows = num_envs * num_agents
@@ -250,6 +251,17 @@ class VecTask:
     def get_env_info(self):
         return {"action_space": self.action_space, "observation_space": self.observation_space, "state_space": self.state_space,
                 "agents": self.num_agents}
+
+    def render(self, mode="rgb_array"):
+        """gym's render call, as the reference's RecordVideo wrapper makes it (train.py:132-143): env 0 at 640 x 480 under the follow-cam
+        (TT:1068-1096) -> uint8 [480, 640, 3] on the host.  The renderer is built by the first call; nothing else builds it."""
+        if mode != "rgb_array":
+            raise ValueError(f"render: mode {mode!r} is not supported (there is no viewer window); use 'rgb_array'")
+        if self._renderer is None:
+            from . import render
+            self._renderer = render.Renderer(self, envs=(0,), width=640, height=480)
+            self._renderer.set_camera(render.Camera.follow_root(self._renderer.scene))
+        return self._renderer.render()[0, :, :, :3].cpu().numpy()
 
     def _to_rl(self, t):
         return t if self.rl_device == self.device else t.to(self.rl_device)
