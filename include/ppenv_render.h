@@ -4,7 +4,7 @@
  * A scene is a short list of analytic primitives — spheres, capsules, boxes, capped cylinders and bones (a capsule between the
  * origins of two body rows) — each attached to a row of a pose tensor in the Isaac Gym [N, B, 13] layout (position 0:3, quaternion
  * xyzw 3:7), or world-fixed (row -1).  What is drawn is the project's own UNVERIFIED collision geometry plus a stick figure of the
- * body tree: no meshes, no textures, no anti-aliasing.
+ * body tree: no meshes, no textures; anti-aliasing is opt-in supersampling (pp_render_rays_aa).
  *
  * Two launches per picture:
  *   pp_render_pose   render_pose_kernel: one workgroup per selected env, lane p places primitive p in world space and writes
@@ -16,6 +16,13 @@
  *                    with one any-hit shadow ray towards the light (from the hit point, offset PP_RENDER_SHADOW_OFFSET along the
  *                    normal) and stores one RGBA8 pixel as a single 4-byte store: channel = (int)(255 * clamp(v, 0, 1) + 0.5),
  *                    alpha 255.  Lanes of a ragged tile that fall outside the image store nothing.
+ *   pp_render_rays_aa  instead of pp_render_rays: pixel (x, y) is the box mean of s x s rays through (x + (i + 1/2) / s, y + (j + 1/2) / s),
+ *                    i, j = 0 .. s - 1, s = `samples` = 1, 2 or 4.  Each ray is shaded as above and its three channels are clamped to [0, 1];
+ *                    the s^2 colours are added in ONE fixed order (a binary tree over k = j * s + i: ppenv_render_device.h,
+ *                    render_aa_tree_sum), the sum is multiplied by the exact 1 / s^2 and channel = (int)(255 v + 0.5), alpha 255.
+ *                    render_rays_aa_kernel: the same workgroup over a 16 x 16 tile of SUB-SAMPLES — s^2 consecutive lanes own a pixel, one
+ *                    ray each, added across lanes in that order; the pixel's first lane stores the 4 bytes.  samples = 1 launches
+ *                    render_rays_kernel itself: the bytes of pp_render_rays.  RGBA only: a mean of depths or ids has no meaning.
  * Images are [E, H, W, 4] uint8; the optional outputs are [E, H, W] fp32 depth (distance along the ray, +inf for sky) and int32
  * primitive id (PP_RENDER_ID_SKY, PP_RENDER_ID_GROUND, or the primitive's index).
  *
@@ -119,6 +126,10 @@ int pp_render_pose(const pp_render_scene* scene, const pp_render_prim* prims_dev
 /* Launch 2.  rgba [count, H, W, 4] uint8, 4-byte aligned; depth [count, H, W] f32 and ids [count, H, W] i32 may be NULL. */
 int pp_render_rays(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids, int32_t count,
                    uint8_t* rgba, float* depth, int32_t* ids, void* stream);
+
+/* Launch 2, supersampled: `samples` sub-samples per axis, 1, 2 or 4 (anything else: PPENV_EINVAL); rgba as for pp_render_rays. */
+int pp_render_rays_aa(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids, int32_t count,
+                      int32_t samples, uint8_t* rgba, void* stream);
 
 #ifdef __cplusplus
 }

@@ -351,6 +351,7 @@ def load(path):
     L.pp_render_scene_upload.argtypes = [scenep, C.POINTER(RenderPrim), vp, vp]
     L.pp_render_pose.argtypes = [scenep, vp, vp, i32, vp, vp]
     L.pp_render_rays.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, vp, vp, vp, vp]
+    L.pp_render_rays_aa.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, i32, vp, vp]
     return L
 
 

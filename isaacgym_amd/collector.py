@@ -50,6 +50,7 @@ class RolloutCollector:
         self.advantages, self.returns = z(self.h, n), z(self.h, n)
         self.sigma = (torch.ones(a, device=dev) if sigma is None else sigma.to(dev, torch.float32)).contiguous()
         self.counter = 0
+        self.on_step = None                   # called with no arguments right after every env.step of collect() (render.TrainingCapture.on_step)
         self.obs[0].copy_(env.obs_buf)
 
     @torch.no_grad()
@@ -60,6 +61,8 @@ class RolloutCollector:
             self.net.forward(self.obs[t], head_out=self.head[t],
                              sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
             self.env.step(self.actions[t], obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
+            if self.on_step is not None:
+                self.on_step()
         self.net.forward(self.obs[self.h], head_out=self.head[self.h])            # bootstrap value of the last observation
         gae(self.rewards, self.values, self.dones, self.gamma, self.tau, self.reward_scale, self.advantages, self.returns)
         return self

@@ -4,6 +4,11 @@
 //   render_rays_kernel   grid (image tiles, selected envs), 256 lanes = a 16 x 16 pixel tile (a wave owns a 16 x 4 strip).  The workgroup
 //                        copies its env's posed primitives into LDS word by word (at most 160 x 20 words = 12.5 KiB), then every lane
 //                        walks the same list for its own ray — the LDS reads are wave-uniform broadcasts — and stores one 4-byte pixel.
+//   render_rays_aa_kernel  the same workgroup and LDS list over a 16 x 16 tile of SUB-SAMPLES: S x S consecutive lanes own one pixel, one ray
+//                        each; their clamped colours are added by a butterfly of log2(S^2) __shfl_xor steps per channel in the
+//                        order render_aa_tree_sum fixes, and the pixel's first lane stores the 4 bytes.  A wave still owns a 16 x 4 strip
+//                        of rays, so a supersampled picture has S^2 times the waves of the plain one (300 workgroups at 320 x 240 become
+//                        1200 / 4800) instead of S^2 sequential rays per lane.
 // A picture is bound by the intersection arithmetic (pixels x primitives x 2 rays), not by bytes: 640 x 480 x 4 B out, a few KiB in.
 // No atomics, no cross-workgroup communication; the only divergence is the per-lane choice of primitive kind and the shadow ray.
 //
@@ -57,6 +62,39 @@ __global__ __launch_bounds__(kBlock) void render_rays_kernel(const pp_render_sce
     rgba[at] = px.rgba;
     if (depth) depth[at] = px.depth;
     if (ids) ids[at] = px.id;
+}
+
+// Lane tid -> pixel tid / S^2 of a (16 / S) x (16 / S) pixel tile, sub-sample tid % S^2 (render_aa_sample's k): the S^2 lanes of a pixel are
+// consecutive and never straddle a wave, and they leave together on a ragged tile, so the butterfly only ever reads lanes that are active.
+template <int S>
+__global__ __launch_bounds__(kBlock) void render_rays_aa_kernel(const pp_render_scene sc, const pp::RenderView view, const pp_render_posed* __restrict__ posed,
+                                                                const int32_t* __restrict__ env_ids, int32_t tiles_x, uint32_t* __restrict__ rgba) {
+    constexpr int kSub = S * S, kPixW = kTileW / S, kPixH = kTileH / S;
+    static_assert((S == 2 || S == 4) && kSub <= 64 && kTileW % S == 0 && kTileH % S == 0, "sub-samples per axis: a power of two inside a wave");
+    __shared__ pp_render_posed lds[PP_RENDER_MAX_PRIMS];
+    const int tid = (int)threadIdx.x;
+    const int32_t sel = (int32_t)blockIdx.y;
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(posed + (size_t)sel * sc.num_prims);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
+        for (int w = tid; w < sc.num_prims * kPosedWords; w += kBlock) dst[w] = src[w];
+    }
+    __syncthreads();
+    const int pix = tid / kSub, k = tid % kSub;
+    const int32_t x = (int32_t)(blockIdx.x % tiles_x) * kPixW + pix % kPixW;
+    const int32_t y = (int32_t)(blockIdx.x / tiles_x) * kPixH + pix / kPixW;
+    if (x >= view.width || y >= view.height) return;         // ragged tiles: after the barrier, all lanes of a pixel together
+    const int32_t env = env_ids[sel];
+    const bool ok = env >= 0 && env < sc.num_envs;
+    const pp::V3 follow = ok ? pp::render_follow(sc, view, env) : pp::mk(0.0f, 0.0f, 0.0f);
+    pp::V3 c = pp::render_aa_sample(sc, view, follow, lds, sc.num_prims, x, y, S, k);
+#pragma unroll
+    for (int m = 1; m < kSub; m *= 2) {                      // render_aa_tree_sum's levels
+        c.x += __shfl_xor(c.x, m);
+        c.y += __shfl_xor(c.y, m);
+        c.z += __shfl_xor(c.z, m);
+    }
+    if (k == 0) rgba[((size_t)sel * view.height + y) * view.width + x] = pp::render_aa_pack(c, S);
 }
 
 bool count_ok(int32_t count, const char* who) {
@@ -124,29 +162,59 @@ extern "C" int pp_render_pose(const pp_render_scene* scene, const pp_render_prim
     return pp_launched("launching render_pose_kernel failed");
 }
 
-extern "C" int pp_render_rays(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids,
-                              int32_t count, uint8_t* rgba, float* depth, int32_t* ids, void* stream) {
+namespace {
+
+// what pp_render_rays and pp_render_rays_aa check alike
+bool rays_ok(const char* who, const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids,
+             int32_t count, const uint8_t* rgba) {
     if (!scene || !camera || !posed || !env_ids || !rgba) {
-        ppenv_set_error("pp_render_rays: NULL pointer");
-        return PPENV_EINVAL;
+        pp_set_errorf("%s: NULL pointer", who);
+        return false;
     }
-    if (!count_ok(count, "pp_render_rays") || !scene_ok(scene, "pp_render_rays")) return PPENV_EINVAL;
+    if (!count_ok(count, who) || !scene_ok(scene, who)) return false;
     if (camera->width <= 0 || camera->height <= 0 || camera->width > 16384 || camera->height > 16384 || !(camera->fov_deg > 0.0f) || !(camera->fov_deg < 180.0f)) {
-        ppenv_set_error("pp_render_rays: width and height must be positive (at most 16384) and the field of view inside (0, 180) degrees");
-        return PPENV_EINVAL;
+        pp_set_errorf("%s: width and height must be positive (at most 16384) and the field of view inside (0, 180) degrees", who);
+        return false;
     }
     if (camera->follow_row >= 0 && !row_ok(scene, camera->follow_source, camera->follow_row)) {
-        ppenv_set_error("pp_render_rays: the camera's follow source or row is out of range");
-        return PPENV_EINVAL;
+        pp_set_errorf("%s: the camera's follow source or row is out of range", who);
+        return false;
     }
     if ((uintptr_t)rgba % 4 != 0) {
-        ppenv_set_error("pp_render_rays: rgba must be 4-byte aligned");
-        return PPENV_EINVAL;
+        pp_set_errorf("%s: rgba must be 4-byte aligned", who);
+        return false;
     }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int pp_render_rays(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids,
+                              int32_t count, uint8_t* rgba, float* depth, int32_t* ids, void* stream) {
+    if (!rays_ok("pp_render_rays", scene, camera, posed, env_ids, count, rgba)) return PPENV_EINVAL;
     pp::RenderView view;
     pp::render_view_of(*camera, view);
     const int32_t tiles_x = (camera->width + kTileW - 1) / kTileW, tiles_y = (camera->height + kTileH - 1) / kTileH;
     hipLaunchKernelGGL(render_rays_kernel, dim3(tiles_x * tiles_y, count), dim3(kBlock), 0, (hipStream_t)stream, *scene, view, posed, env_ids, tiles_x,
                        reinterpret_cast<uint32_t*>(rgba), depth, ids);
     return pp_launched("launching render_rays_kernel failed");
+}
+
+extern "C" int pp_render_rays_aa(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids,
+                                 int32_t count, int32_t samples, uint8_t* rgba, void* stream) {
+    if (!rays_ok("pp_render_rays_aa", scene, camera, posed, env_ids, count, rgba)) return PPENV_EINVAL;
+    if (!pp::render_samples_ok(samples)) {
+        pp_set_errorf("pp_render_rays_aa: samples per axis must be 1, 2 or 4, got %d", samples);
+        return PPENV_EINVAL;
+    }
+    if (samples == 1) return pp_render_rays(scene, camera, posed, env_ids, count, rgba, nullptr, nullptr, stream);      // one ray: that kernel, those bytes
+    pp::RenderView view;
+    pp::render_view_of(*camera, view);
+    const int32_t pw = kTileW / samples, ph = kTileH / samples;                                                       // pixels per workgroup
+    const int32_t tiles_x = (camera->width + pw - 1) / pw, tiles_y = (camera->height + ph - 1) / ph;
+    const dim3 grid(tiles_x * tiles_y, count);
+    uint32_t* out = reinterpret_cast<uint32_t*>(rgba);
+    if (samples == 2) hipLaunchKernelGGL(render_rays_aa_kernel<2>, grid, dim3(kBlock), 0, (hipStream_t)stream, *scene, view, posed, env_ids, tiles_x, out);
+    else hipLaunchKernelGGL(render_rays_aa_kernel<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, *scene, view, posed, env_ids, tiles_x, out);
+    return pp_launched("launching render_rays_aa_kernel failed");
 }

@@ -1,7 +1,8 @@
 // ppenv_render_device.h — per-primitive and per-pixel arithmetic of the ray caster (include/ppenv_render.h): placing a primitive on its
-// body row, the ray of a pixel, the four ray / primitive intersections, the ground, the shading and the RGBA8 packing.
+// body row, the ray of a pixel, the four ray / primitive intersections, the ground, the shading, the RGBA8 packing and the fixed-order box
+// mean of a supersampled pixel (render_pixel_aa).
 //
-// PP_HD like ppenv_play_device.h: the HIP kernels in ppenv_render.hip and the tests' host build (tests/csrc/render_shim.cpp, g++)
+// PP_HD like ppenv_play_device.h: the HIP kernels in ppenv_render.hip and the tests' host build (tests/csrc/render_shim.cpp, render_aa_shim.cpp, g++)
 // compile this text.  fp32 throughout.  The two builds need not agree bit for bit (sqrtf and the divisions may round differently,
 // and the device contracts a * b + c): the tests compare them on the pixels that are not on an edge, DESIGN §5f.
 // Depth uses +inf for the sky: this header is compiled without -ffinite-math-only on both sides (isaacgym_amd/_lib.py SOURCE_FLAGS).
@@ -219,11 +220,19 @@ struct RenderPixel {
     int32_t parity;                     // ground hits: the checker cell's parity; otherwise 0
 };
 
-// One pixel of env `env`: the ray from eye + follow through (px, py) in pixel units (the centre of pixel (x, y) is (x + 0.5, y + 0.5)).
-PP_HD RenderPixel render_pixel(const pp_render_scene& sc, const RenderView& v, V3 follow, const pp_render_posed* posed, int32_t count, float px, float py) {
+// What one ray sees, before the packing: the float colour (not clamped) next to RenderPixel's other fields.
+struct RenderSample {
+    V3 rgb;
+    float depth;
+    int32_t id, shadow, parity;
+};
+
+// The ray from eye + follow through (px, py) in pixel units (the centre of pixel (x, y) is (x + 0.5, y + 0.5)): primary hit, ground and
+// checker, one shadow ray.
+PP_HD RenderSample render_sample(const pp_render_scene& sc, const RenderView& v, V3 follow, const pp_render_posed* posed, int32_t count, float px, float py) {
     const V3 o = ld3(v.eye) + follow;
     const V3 d = render_ray_dir(v, px, py);
-    RenderPixel out;
+    RenderSample out;
     out.id = PP_RENDER_ID_SKY;
     out.depth = render_inf();
     out.shadow = 0;
@@ -239,7 +248,7 @@ PP_HD RenderPixel render_pixel(const pp_render_scene& sc, const RenderView& v, V
         if (t > PP_RENDER_T_MIN && t < out.depth) { out.depth = t; out.id = PP_RENDER_ID_GROUND; n = mk(0.0f, 0.0f, 1.0f); }
     }
     if (out.id == PP_RENDER_ID_SKY) {
-        out.rgba = render_pack(ld3(sc.sky_rgb));
+        out.rgb = ld3(sc.sky_rgb);
         return out;
     }
     const V3 p = o + d * out.depth;
@@ -257,8 +266,60 @@ PP_HD RenderPixel render_pixel(const pp_render_scene& sc, const RenderView& v, V
         out.shadow = render_occluded(posed, count, p + n * PP_RENDER_SHADOW_OFFSET, l) ? 1 : 0;
         lit = out.shadow ? 0.0f : ndl;
     }
-    out.rgba = render_pack(albedo * (sc.ambient + sc.diffuse * lit));
+    out.rgb = albedo * (sc.ambient + sc.diffuse * lit);
     return out;
+}
+
+// One pixel of env `env`: one ray through (px, py), packed.
+PP_HD RenderPixel render_pixel(const pp_render_scene& sc, const RenderView& v, V3 follow, const pp_render_posed* posed, int32_t count, float px, float py) {
+    const RenderSample s = render_sample(sc, v, follow, posed, count, px, py);
+    RenderPixel out;
+    out.rgba = render_pack(s.rgb);
+    out.depth = s.depth;
+    out.id = s.id;
+    out.shadow = s.shadow;
+    out.parity = s.parity;
+    return out;
+}
+
+// ---- supersampling: pixel (x, y) is the box mean of s x s rays, s = 1, 2 or 4 sub-samples per axis (pp_render_rays_aa).
+constexpr int32_t kRenderMaxSamples = 4;
+
+PP_HD bool render_samples_ok(int32_t s) { return s == 1 || s == 2 || s == 4; }
+
+PP_HD float render_clamp01(float v) { return v < 0.0f ? 0.0f : (v > 1.0f ? 1.0f : v); }
+
+// Sub-sample k = j * s + i (i, j = 0 .. s - 1) of pixel (x, y): the ray through (x + (i + 1/2) / s, y + (j + 1/2) / s) — exact in fp32, s being a
+// power of two — shaded as render_sample does, each channel clamped to [0, 1].
+PP_HD V3 render_aa_sample(const pp_render_scene& sc, const RenderView& v, V3 follow, const pp_render_posed* posed, int32_t count, int32_t x, int32_t y,
+                          int32_t s, int32_t k) {
+    const float inv = 1.0f / (float)s;
+    const int32_t i = k % s, j = k / s;
+    const V3 c = render_sample(sc, v, follow, posed, count, (float)x + ((float)i + 0.5f) * inv, (float)y + ((float)j + 0.5f) * inv).rgb;
+    return mk(render_clamp01(c.x), render_clamp01(c.y), render_clamp01(c.z));
+}
+
+// THE ORDER OF THE SUM, per channel: a binary tree over the sub-sample index k.  Level m = 1, 2, 4, 8 (while m < s * s) replaces the value of
+// every k that is a multiple of 2m by value[k] + value[k + m]; the total ends in value[0].  The kernel's lanes do the same additions as a
+// butterfly (lane k adds the value of lane k ^ m: fp32 addition commutes, so every lane of a pixel holds the bits of value[0]).
+PP_HD V3 render_aa_tree_sum(V3* c, int32_t n) {
+    for (int32_t m = 1; m < n; m *= 2)
+        for (int32_t k = 0; k < n; k += 2 * m) c[k] = c[k] + c[k + m];
+    return c[0];
+}
+
+// The sum times the exact 1 / s^2, then channel = (int)(255 v + 0.5), alpha 255.
+PP_HD uint32_t render_aa_pack(V3 sum, int32_t s) {
+    const V3 m = sum * (1.0f / (float)(s * s));
+    return (uint32_t)(int)(255.0f * m.x + 0.5f) | ((uint32_t)(int)(255.0f * m.y + 0.5f) << 8) | ((uint32_t)(int)(255.0f * m.z + 0.5f) << 16) | 0xFF000000u;
+}
+
+// The supersampled pixel (x, y), sub-sample after sub-sample: what the host build runs and what the kernel's lanes, one per sub-sample, add up to.
+PP_HD uint32_t render_pixel_aa(const pp_render_scene& sc, const RenderView& v, V3 follow, const pp_render_posed* posed, int32_t count, int32_t x, int32_t y,
+                               int32_t s) {
+    V3 c[kRenderMaxSamples * kRenderMaxSamples];
+    for (int32_t k = 0; k < s * s; ++k) c[k] = render_aa_sample(sc, v, follow, posed, count, x, y, s, k);
+    return render_aa_pack(render_aa_tree_sum(c, s * s), s);
 }
 
 }  // namespace pp

@@ -3,7 +3,7 @@
 
     Player(task, policy, games_num=2000).run()      games_num episodes of `task` under `policy` -> rl_games' numbers (average return,
                                                     average episode length) plus spread
-    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --camera side]
+    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side]
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -211,22 +211,29 @@ def parse_args(argv=None):
     ap.add_argument("--capture-every", type=int, default=2, help="control steps between two frames")
     ap.add_argument("--capture-size", default="640x480", help="WIDTHxHEIGHT of one env's picture")
     ap.add_argument("--capture-fps", type=float, default=30.0)
+    ap.add_argument("--capture-samples", type=int, default=1, choices=(1, 2, 4), help="rays per pixel and axis: 2 is 2 x 2 supersampling, 4 is 4 x 4")
     ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
     return ap.parse_args(argv)
 
 
-def make_recorder(task, args):
-    """The Recorder of the --capture* options."""
+def make_renderer(task, args):
+    """The Renderer of the --capture-envs, --capture-size, --capture-samples (default 1) and --camera options."""
     from . import render
     try:
         width, height = (int(v) for v in args.capture_size.lower().split("x"))
         envs = [int(v) for v in args.capture_envs.split(",")]
     except ValueError as e:
         raise SystemExit(f"--capture-size is WIDTHxHEIGHT and --capture-envs a comma-separated list of env ids: {e}")
-    renderer = render.Renderer(task, envs=envs, width=width, height=height)
+    renderer = render.Renderer(task, envs=envs, width=width, height=height, samples=getattr(args, "capture_samples", 1))
     if args.camera == "follow":
         renderer.set_camera(render.Camera.follow_root(renderer.scene))
-    return render.Recorder(renderer, length=args.capture_len, every=args.capture_every)
+    return renderer
+
+
+def make_recorder(task, args):
+    """The Recorder of the --capture* options."""
+    from . import render
+    return render.Recorder(make_renderer(task, args), length=args.capture_len, every=args.capture_every)
 
 
 def main(argv=None):

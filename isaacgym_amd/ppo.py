@@ -10,6 +10,10 @@ One epoch (`PPOTrainer.train_epoch`):
 
 There is no host synchronisation inside an epoch: the loss scale, the step count and every statistic stay on the device.
 
+Videos while training (the reference's capture_video / RecordVideo, train.py:132-144): `PPOTrainer.set_capture(render.TrainingCapture(...))`,
+`fit(..., capture=...)`, `--capture-video`.  The collector calls the capture after every control step; it launches renders into a device
+ring and reads nothing, so a run with capture is bitwise the run without and an epoch still has no host synchronisation.
+
 Semantics.  The loss terms are restated from rl_games' published a2c_continuous / common_losses (rl_games is absent offline: parity
 unpinned, the same status as tools/ppo_epoch_bench.py): the clipped surrogate, the clipped value loss, the soft bound loss at +-1.1, and
 loss = mean(a) + 0.5 critic_coef mean(c) - entropy_coef entropy + bounds_loss_coef mean(b).  The gradient-norm clip is
@@ -471,6 +475,19 @@ class PPOTrainer:
             d = u
         return out
 
+    def set_capture(self, capture):
+        """Record videos while training: `capture` (render.TrainingCapture over a Renderer of THIS task; None: stop) gets one on_step() after
+        every control step of the rollout.  Its step count starts at epoch x horizon_length, so a resumed run continues the numbering of
+        the files.  Rendering reads the env's state and writes its own tensors: the run is bitwise the run without it.  Data-parallel:
+        rank 0 alone captures; the other ranks ignore the call."""
+        if capture is not None and capture.renderer.task is not self.task:
+            raise ValueError("the recorder renders another task")
+        if capture is None or self.rank != 0:
+            self.col.on_step = None
+            return
+        capture.start_step = self.epoch * self.cfg.horizon_length
+        self.col.on_step = capture.on_step
+
     # -- the steps of an epoch --
     def collect(self):
         """One horizon; with normalize_value the value column is de-normalised and GAE re-run on it (the collector's own GAE ran on the
@@ -646,7 +663,7 @@ class PPOTrainer:
 
 
 # ---- the run loop -----------------------------------------------------------------------------------------------------------------
-def fit(trainer, out_dir, name, print_every=10, max_epochs=None):
+def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
     """rl_games' train loop around train_epoch(), restated from its published a2c_common.train (rl_games is absent offline: parity
     unpinned).  Runs until trainer.epoch reaches max_epochs (default cfg.max_epochs: the TOTAL, so a resumed trainer continues its
     numbering) or the score wins.  After every epoch, with ONE host read (here, not in train_epoch):
@@ -658,8 +675,12 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None):
     Data-parallel: train_epoch() returns rank 0's score on every rank, so all ranks take the same decisions and leave in the same epoch;
     rank 0 alone writes (trainer.save).  print_every: rank 0 prints a line every so many epochs and at the end (0: never).
     -> dict(epochs: run by this call, epoch: the trainer's, stopped, reason: "max_epochs" | "score_to_win", best_score: last_mean_rewards
-    (NO_SCORE while there is no best), paths: dict(latest, best, won: None where not written by this call), written: every path in order)."""
+    (NO_SCORE while there is no best), paths: dict(latest, best, won: None where not written by this call), written: every path in order).
+    capture: a render.TrainingCapture (trainer.set_capture is called with it): polled after every epoch's host read, closed before
+    returning; the result then has `videos`, the files it wrote."""
     cfg = trainer.cfg
+    if capture is not None:
+        trainer.set_capture(capture)
     total = int(cfg.max_epochs if max_epochs is None else max_epochs)
     nn_dir = os.path.join(out_dir, "nn")
     paths = dict(latest=None, best=None, won=None)
@@ -677,6 +698,8 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None):
         epoch = trainer.epoch
         keys = list(res)
         vals = dict(zip(keys, torch.stack([res[k].detach().double() for k in keys]).tolist()))     # the epoch's only host read
+        if capture is not None:
+            capture.poll()
         score, games = vals["meter_return"], int(vals["meter_games"])
         if games > 0 and score > trainer.last_mean_rewards and epoch >= cfg.save_best_after:
             trainer.last_mean_rewards = score
@@ -694,8 +717,12 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None):
                   f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f} score {score:.6g} ({games} games)", flush=True)
             if stopped:
                 print(f"score {score} above score_to_win {cfg.score_to_win}: stopping", flush=True)
-    return dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
-                best_score=trainer.last_mean_rewards, paths=paths, written=written)
+    out = dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
+               best_score=trainer.last_mean_rewards, paths=paths, written=written)
+    if capture is not None:
+        out["videos"] = capture.close()
+        trainer.set_capture(None)
+    return out
 
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
@@ -742,6 +769,15 @@ def main(argv=None):
     ap.add_argument("--multi-gpu", action="store_true", help="data-parallel, one rank per process under python -m torch.distributed.run")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl (RCCL) one GPU per rank; gloo: ranks may share a GPU")
     ap.add_argument("--force-dist", action="store_true", help="with --multi-gpu: accept a one-rank world and run the collectives anyway")
+    ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
+    ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
+    ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
+    ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
+    ap.add_argument("--capture-size", default="320x240", help="WIDTHxHEIGHT of one env's picture")
+    ap.add_argument("--capture-every", type=int, default=1, help="control steps between two frames of a recording")
+    ap.add_argument("--capture-fps", type=float, default=30.0)
+    ap.add_argument("--capture-samples", type=int, default=2, choices=(1, 2, 4), help="rays per pixel and axis: 2 is 2 x 2 supersampling")
+    ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
     args = ap.parse_args(argv)
     if args.force_dist and not args.multi_gpu:
         ap.error("--force-dist belongs to --multi-gpu")
@@ -757,6 +793,9 @@ def main(argv=None):
         from . import cfgyaml
         composed = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})
         task_cfg = composed["task"]
+        for key in ("capture_video", "capture_video_freq", "capture_video_len"):        # the composed cfg's keys are the defaults
+            if getattr(args, key) is None and key in composed:
+                setattr(args, key, composed[key])
         train = composed.get("train")        # the 27-dof task has no train yaml: the defaults (PPOConfig's, the Tilt yaml's)
         cfg = PPOConfig.from_train_cfg(train, task_cfg=task_cfg, **over) if train else PPOConfig(**over)
         cfg.check()
@@ -773,8 +812,16 @@ def main(argv=None):
         if rank == 0:
             print(f"resumed {args.checkpoint} at epoch {tr.epoch}, best score {tr.last_mean_rewards}", flush=True)
     out = args.out or os.path.join("runs", args.task)
-    done = fit(tr, out, args.task, print_every=args.print_every)
+    capture = None
+    if args.capture_video and rank == 0:
+        from . import play, render
+        renderer = play.make_renderer(task, args)
+        capture = render.TrainingCapture(renderer, os.path.join(out, "videos"), freq=args.capture_video_freq or 1464, length=args.capture_video_len or 100,
+                                         every=args.capture_every, fps=args.capture_fps)
+    done = fit(tr, out, args.task, print_every=args.print_every, capture=capture)
     if rank == 0:
+        for path in done.get("videos", []):
+            print(f"saved {path} (video)", flush=True)
         for kind, path in done["paths"].items():
             if path is not None:
                 print(f"saved {path} ({kind})" + (f" (ranks: {tr.world}, frames global)" if tr.multi else ""), flush=True)

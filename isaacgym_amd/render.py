@@ -3,12 +3,14 @@
     Scene.from_config(task_name)     host only: the primitives of a task's scene from its native config and the G1 body tree
     Scene.from_task(task)            ... plus the pose tensors of a live task
     Camera.side_view(scene) / Camera.follow_root(scene)
-    Renderer(task, envs=(0,), width=640, height=480).render()     -> uint8 [E, H, W, 4] on the device, two launches, no host read
+    Renderer(task, envs=(0,), width=640, height=480, samples=1).render()     -> uint8 [E, H, W, 4] on the device, two launches, no host read
+                                     samples = 2 or 4: every pixel is the box mean of samples x samples rays (pp_render_rays_aa)
     Recorder(renderer, length=100, every=1).capture() / .save("out.gif")
+    TrainingCapture(renderer, out_dir, freq=1464, length=100)     gym's RecordVideo rule inside a training rollout (PPOTrainer.set_capture)
 
 WHAT IS DRAWN is the project's own UNVERIFIED collision geometry (scene.py: the capsules and spheres the ball collides with, the paddle
 disc, the table slab, the net, the ball) plus a stick figure: one thin capsule ("bone") per parent-child pair of the G1 body tree
-between the two bodies' origins.  No meshes, no textures, no anti-aliasing.  For the 7-dof tasks `rigid_body_states` carries the
+between the two bodies' origins.  No meshes, no textures; anti-aliasing is opt-in supersampling (`samples=`).  For the 7-dof tasks `rigid_body_states` carries the
 pelvis and the right arm chain only (every other body row sits at the root pose), so their stick figure is the arm; the torso, pelvis
 and head appear as their world-fixed collision shapes.
 
@@ -19,7 +21,7 @@ ball.  A collision shape hangs on a LINK index of the native model, mapped to it
     27-dof task    tree link l     -> TA_LINK_NAMES[l]                (pelvis, legs, waist, left arm, the five right-arm links)
     link -1                        -> world-fixed (scene.build_config writes such shapes in world coordinates)
 
-Out of scope: capture during training (the collector drives the native handle below VecTask), meshes / textures / anti-aliasing, mp4.
+Out of scope: meshes, textures, mp4.
 """
 import ctypes as C
 import math
@@ -306,8 +308,13 @@ class Camera:
 
 
 class Renderer:
-    def __init__(self, task, envs=(0,), width=640, height=480, camera=None, depth=False, ids=False):
+    def __init__(self, task, envs=(0,), width=640, height=480, camera=None, depth=False, ids=False, samples=1):
         import torch
+        if samples not in (1, 2, 4):
+            raise ValueError(f"Renderer: samples (sub-samples per axis) must be 1, 2 or 4, got {samples!r}")
+        if samples > 1 and (depth or ids):
+            raise ValueError("Renderer: depth and ids need samples=1: a mean of depths or ids has no meaning")
+        self.samples = int(samples)
         envs = [int(e) for e in envs]
         if not 1 <= len(envs) <= RENDER_MAX_ENVS or min(envs) < 0 or max(envs) >= task.num_envs:
             raise ValueError(f"Renderer: 1 .. {RENDER_MAX_ENVS} env ids inside [0, {task.num_envs}), got {envs}")
@@ -336,8 +343,12 @@ class Renderer:
         sc, s = self.scene, _lib.stream(self.device)
         sc.refresh()
         _lib.check(self.L.pp_render_pose(C.byref(sc.header), sc.prims_dev.data_ptr(), self.env_ids.data_ptr(), len(self.envs), self.posed.data_ptr(), s), self.L)
-        _lib.check(self.L.pp_render_rays(C.byref(sc.header), C.byref(self._cam), self.posed.data_ptr(), self.env_ids.data_ptr(), len(self.envs),
-                                         out.data_ptr(), _lib.ptr(self.depth), _lib.ptr(self.ids), s), self.L)
+        if self.samples > 1:
+            _lib.check(self.L.pp_render_rays_aa(C.byref(sc.header), C.byref(self._cam), self.posed.data_ptr(), self.env_ids.data_ptr(), len(self.envs),
+                                                self.samples, out.data_ptr(), s), self.L)
+        else:
+            _lib.check(self.L.pp_render_rays(C.byref(sc.header), C.byref(self._cam), self.posed.data_ptr(), self.env_ids.data_ptr(), len(self.envs),
+                                             out.data_ptr(), _lib.ptr(self.depth), _lib.ptr(self.ids), s), self.L)
         return out
 
 
@@ -380,6 +391,148 @@ class Recorder:
         """The one host copy.  Envs side by side; *.gif (one file), *.png (numbered files <stem>_0000.png ...) through PIL, *.npy
         ([T, H, E * W, 3] uint8) without it.  -> the list of files written."""
         return save_frames(self.frames().cpu().numpy(), path, fps)
+
+
+class TrainingCapture:
+    """gym.wrappers.RecordVideo's rule (the reference's train.py:132-144: capture_video, capture_video_freq 1464, capture_video_len 100) for
+    a rollout that never leaves the device: on_step(), called once after every control step, opens a recording
+    <out_dir>/rl-video-step-<k><ext> at every step k with k % freq == 0 that no recording covers (k counts control steps from start_step),
+    draws every `every`-th of the next `length` steps — ceil(length / every) frames, each after its step — into a device ring, and when
+    the last frame is launched enqueues ONE non_blocking copy of the frames into pinned host memory and records an event.  All of that is
+    host integers and launches: nothing is read from the device, so a training epoch with a recording open still has no host
+    synchronisation, and the env, the policy and the learner never see it.
+    poll() (main thread) hands every copy whose event has completed to the one writer thread, which touches host memory alone
+    (save_frames), and returns the files finished so far; close() writes an open recording short, waits for the copies and the writer.
+    The copy is ordered on the stream before any later render, so a later recording cannot overwrite frames in flight.  The pinned buffer
+    allocated here serves every recording as long as each is written out before the next one ends (freq >> length: always); one more is
+    allocated only when a recording ends while the writer still holds every buffer."""
+
+    def __init__(self, renderer, out_dir, freq=1464, length=100, every=1, fps=30, ext=".gif", start_step=0):
+        for name, v in (("freq", freq), ("length", length), ("every", every)):
+            if int(v) != v or int(v) < 1:
+                raise ValueError(f"TrainingCapture: {name} {v!r} is not a positive integer")
+        if int(start_step) != start_step or int(start_step) < 0:
+            raise ValueError(f"TrainingCapture: start_step {start_step!r} is not a count of control steps")
+        if ext not in (".gif", ".png", ".npy"):
+            raise ValueError(f"TrainingCapture: ext {ext!r}: the capture formats are .gif, .png and .npy")
+        if ext != ".npy":
+            try:
+                import PIL  # noqa: F401
+            except ImportError as e:
+                raise RuntimeError(f"writing {ext} needs PIL, which is not installed; pass ext='.npy' instead") from e
+        self.renderer, self.out_dir, self.fps, self.ext = renderer, out_dir, fps, ext
+        self.freq, self.length, self.every = int(freq), int(length), int(every)
+        self.recorder = Recorder(renderer, length=-(-self.length // self.every), every=self.every)     # one recording never wraps the ring
+        self._k = int(start_step)
+        self._open_at = None                  # k of the step that opened the recording in progress
+        self._free = [self._host_buffer()]
+        self._in_flight = []                  # [(event, path, host buffer, frames)] in stream order
+        self._written, self._errors = [], []  # appended to by the writer thread (list.append: atomic), read by the main thread
+        self._taken = 0                       # entries of _written the main thread has seen
+        self._queue, self._thread = None, None
+        self.paths = []
+        os.makedirs(out_dir, exist_ok=True)
+
+    @property
+    def start_step(self):
+        return self._k
+
+    @start_step.setter
+    def start_step(self, k):
+        if self._open_at is not None:
+            raise RuntimeError("TrainingCapture: start_step cannot change while a recording is open")
+        self._k = int(k)
+
+    @property
+    def recording(self):
+        return self._open_at is not None
+
+    def _host_buffer(self):
+        import torch
+        return torch.zeros(tuple(self.recorder.ring.shape), dtype=torch.uint8, pin_memory=self.renderer.device.type == "cuda")
+
+    def on_step(self):
+        """After a control step.  Host integers and launches only."""
+        k = self._k
+        self._k += 1
+        rec = self.recorder
+        if self._open_at is None:
+            if k % self.freq:
+                return
+            self._open_at = k
+            rec.calls = rec.captured = 0
+        rec.capture()
+        if rec.calls == self.length:
+            self._finish()
+
+    def _finish(self):
+        import torch
+        self._reclaim()
+        rec, dev = self.recorder, self.renderer.device
+        n = rec.captured
+        host = self._free.pop() if self._free else self._host_buffer()
+        host[:n].copy_(rec.ring[:n], non_blocking=True)
+        event = None
+        if dev.type == "cuda":
+            event = torch.cuda.Event()
+            event.record(torch.cuda.current_stream(dev))
+        self._in_flight.append((event, os.path.join(self.out_dir, f"rl-video-step-{self._open_at}{self.ext}"), host, n))
+        self._open_at = None
+
+    def _reclaim(self):
+        """What the writer has finished since the last look: its files, and its host buffers back to the free list."""
+        while self._taken < len(self._written):
+            files, host = self._written[self._taken]
+            self._taken += 1
+            self.paths += files
+            self._free.append(host)
+        if self._errors:
+            raise self._errors.pop(0)
+
+    def _write_loop(self):
+        while True:
+            job = self._queue.get()
+            if job is None:
+                return
+            path, host, n = job
+            try:
+                self._written.append((save_frames(host[:n].numpy(), path, self.fps), host))
+            except Exception as e:      # noqa: BLE001  (raised on the main thread by the next poll() / close())
+                self._errors.append(e)
+                self._written.append(([], host))
+
+    def _hand_over(self, wait):
+        import queue
+        import threading
+        while self._in_flight and (wait or self._in_flight[0][0] is None or self._in_flight[0][0].query()):
+            event, path, host, n = self._in_flight.pop(0)
+            if wait and event is not None:
+                event.synchronize()
+            if self._thread is None:
+                self._queue = queue.Queue()
+                self._thread = threading.Thread(target=self._write_loop, name="TrainingCapture writer", daemon=True)
+                self._thread.start()
+            self._queue.put((path, host, n))
+
+    def poll(self):
+        """-> the files written so far.  Does not wait: neither for a copy nor for the writer."""
+        self._hand_over(wait=False)
+        self._reclaim()
+        return list(self.paths)
+
+    def close(self):
+        """An open recording is written short (if it has a frame); waits for the copies and the writer.  -> all files."""
+        if self._open_at is not None:
+            if self.recorder.captured > 0:
+                self._finish()
+            self._open_at = None
+        self._hand_over(wait=True)
+        if self._thread is not None:
+            self._queue.put(None)
+            self._thread.join()
+            self._thread = self._queue = None
+        self._reclaim()
+        return list(self.paths)
 
 
 def save_frames(frames, path, fps=30):

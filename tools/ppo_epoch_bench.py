@@ -13,6 +13,9 @@ critic_coef 4, clip_value, bounds_loss_coef 1e-4, grad_norm 10, normalize_advant
 rl_games itself is not importable here (absent from the reference and the image); the loss terms are restated from its published a2c_continuous /
 common_losses (actor: clipped surrogate; critic: clipped value loss; bound loss on mu beyond +-1.1) — timing context, parity unpinned.
 Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo] [--num-envs 4096] [--minibatch 32768] [--epochs 3]
+--learner ppo --capture: the same epochs with a render.TrainingCapture on the rollout (env 0 at 320 x 240, --capture-samples rays per axis, recordings of
+100 steps back to back, so one is open in every timed epoch and one finishes every 100 steps); reports every epoch's rollout time, what poll() cost after
+it, and what close() waited for at the end (the last copy and the writer).
 Data-parallel (every learner, --learner ppo included: PPOTrainer with its gradient all-reduce and the mean inside the Adam kernel): under
 `python -m torch.distributed.run --nproc_per_node=N`, or with --force-dist for one rank on RCCL; --dist-backend gloo lets ranks share a GPU."""
 import argparse
@@ -35,6 +38,9 @@ ap.add_argument("--learner", default="native", choices=["native", "torch", "ppo"
 ap.add_argument("--num-envs", type=int, default=4096)
 ap.add_argument("--minibatch", type=int, default=32768)
 ap.add_argument("--epochs", type=int, default=3)
+ap.add_argument("--capture", action="store_true", help="--learner ppo: record the rollout (render.TrainingCapture), to measure what it costs")
+ap.add_argument("--capture-samples", type=int, default=2, choices=(1, 2, 4))
+ap.add_argument("--capture-ext", default=".npy", choices=(".npy", ".gif"))
 ap.add_argument("--force-dist", action="store_true", help="create the nccl group and all-reduce the gradients even with ONE rank (the RCCL path on a one-GPU box)")
 ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share cuda:LOCAL_RANK %% device_count (rehearsal on one GPU)")
 args = ap.parse_args()
@@ -76,10 +82,26 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
         tr.collect()
         tr.meter.update(tr.col.rewards, tr.col.dones)
     rollout(); tr.prepare(); tr.learn(); tr.col.next_horizon()             # warm-up
+    cap, roll_each, poll_each = None, [], []
+    if args.capture and rank == 0:
+        import tempfile  # noqa: E402
+        from isaacgym_amd import render  # noqa: E402
+        cap = render.TrainingCapture(render.Renderer(tr.task, envs=[0], width=320, height=240, samples=args.capture_samples),
+                                     tempfile.mkdtemp(prefix="ppo_epoch_bench_"), freq=100, length=100, ext=args.capture_ext)
+        tr.set_capture(cap)
+        tr.col.on_step()                                                   # warm-up of the two render launches; the recording starts at step 0 anyway
+        cap.close()
+        cap.paths.clear()
+        cap.start_step = 0
     roll_s = learn_s = 0.0
     for _ in range(args.epochs):
         dt, _ = timed(rollout)
         roll_s += dt
+        roll_each.append(dt * 1e3)
+        if cap is not None:
+            t0 = time.perf_counter()
+            cap.poll()
+            poll_each.append((time.perf_counter() - t0) * 1e3)
         dt, _ = timed(lambda: (tr.prepare(), tr.learn()))
         learn_s += dt
         tr.col.sigma.copy_(torch.exp(tr.logstd))
@@ -91,8 +113,14 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
         roll_ms, learn_ms = float(t[0]), float(t[1])
     steps = tr.steps_per_epoch
     f = tr.opt.fields()
+    extra = {"ms_rollout_each_epoch": roll_each}
+    if cap is not None:
+        t0 = time.perf_counter()
+        videos = cap.close()
+        extra.update(capture=f"env 0, 320 x 240, {args.capture_samples} x {args.capture_samples} rays, 100 steps per recording, {args.capture_ext}",
+                     ms_poll_each_epoch=poll_each, ms_close=(time.perf_counter() - t0) * 1e3, videos=len(videos))
     if rank == 0:
-      print(json.dumps({
+      print(json.dumps({**extra,
         "what": "one PPO epoch of BASELINE config 5's per-GPU slice (27-dof task, rl_games a2c_continuous settings of cfg/train/HumanoidPingpongTiltG1PPO.yaml), context only",
         "learner": "ppo", "num_envs": n, "horizon": H, "minibatch_rows": args.minibatch, "mini_epochs": tr.cfg.mini_epochs, "minibatch_steps_per_epoch": steps,
         "ms_rollout_per_epoch": roll_ms, "ms_learning_per_epoch": learn_ms, "ms_per_minibatch_step": learn_ms / steps, "ranks": world,
