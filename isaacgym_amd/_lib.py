@@ -28,6 +28,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_play_device.h"), os.path.join(ROOT, "include", "ppenv_play.h"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter_device.h"), os.path.join(ROOT, "include", "ppenv_ppo_meter.h"),
            os.path.join(_PKG, "csrc", "ppenv_render_device.h"), os.path.join(ROOT, "include", "ppenv_render.h"),
+           os.path.join(_PKG, "csrc", "ppenv_ta_outcome_device.h"), os.path.join(ROOT, "include", "ppenv_ta_outcome.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -109,6 +110,15 @@ class PPOMeter(C.Structure):
     """ctypes mirror of ppenv_ppo_meter (include/ppenv_ppo_meter.h)."""
     _fields_ = [("mean_reward", C.c_double), ("mean_length", C.c_double), ("current_size", C.c_int64), ("games_total", C.c_int64),
                 ("updates", C.c_int64)]
+
+
+TA_OUTCOME_NAMES = ("closer", "hit_paddle", "cross_net", "hit_table", "fall_down")      # PP_TA_OUTCOME_*: the bits 16 .. 256 of the TA flags
+
+
+class TAOutcome(C.Structure):
+    """ctypes mirror of pp_ta_outcome (include/ppenv_ta_outcome.h): 16 words of 8 bytes."""
+    _fields_ = [("windows", C.c_uint64), ("envs", C.c_uint64), ("count", C.c_uint64 * 5), ("last_envs", C.c_uint64), ("last", C.c_uint64 * 5),
+                ("reserved", C.c_uint64 * 3)]
 
 
 RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
@@ -352,6 +362,10 @@ def load(path):
     L.pp_render_pose.argtypes = [scenep, vp, vp, i32, vp, vp]
     L.pp_render_rays.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, vp, vp, vp, vp]
     L.pp_render_rays_aa.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, i32, vp, vp]
+    # ---- include/ppenv_ta_outcome.h
+    L.pp_ta_sim_set_outcome.argtypes = [vp, vp]
+    L.pp_ta_post_physics_step_outcome.argtypes = [C.POINTER(scene.TAParams)] + [vp] * 16
+    L.pp_ta_outcome_latch.argtypes = [vp, vp, i64, vp, vp]
     return L
 
 

@@ -8,6 +8,7 @@
 #include <cstdio>
 
 #include "ppenv_ta_task.h"
+#include "ppenv_ta_outcome_device.h"
 
 using namespace pp;
 
@@ -33,12 +34,55 @@ __global__ __launch_bounds__(kTaBlock) void ta_post_physics_kernel(const ppenv_t
 // TA:1162-1166: whenever ANY env resets, the diagnostic count flags of ALL envs are cleared
 // One workgroup: every thread reads the word before the barrier, then it is zeroed for the next step — the step needs no memset
 // launch (5.5 us of a 133 us step) as long as the word starts at zero.
-__global__ __launch_bounds__(1024) void ta_clear_counts_kernel(int n, uint32_t* flags, uint32_t* any_reset) {
+// With `outcome` (include/ppenv_ta_outcome.h; NULL: off) the five count bits are summed over all n words before they go: every thread its
+// words, a butterfly within the wave, the 16 waves in order through LDS, and thread 0 alone updates the struct (integers: any order
+// gives the same bits).  The branch is uniform, and with outcome NULL the kernel does what it did without the feature.
+__global__ __launch_bounds__(1024) void ta_clear_counts_kernel(int n, uint32_t* flags, uint32_t* any_reset, pp_ta_outcome* outcome) {
+    __shared__ uint32_t wave_sum[16][PP_TA_OUTCOME_COUNTS];
     const bool any = *any_reset != 0u;
     __syncthreads();
     if (threadIdx.x == 0) *any_reset = 0u;
-    if (any)
+    if (!any) return;
+    if (!outcome) {
         for (int i = threadIdx.x; i < n; i += 1024) flags[i] &= ~PPENV_TA_COUNT_MASK;
+        return;
+    }
+    uint32_t c[PP_TA_OUTCOME_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const uint32_t f = flags[i];
+        ta_outcome_word(f, c);
+        flags[i] = f & ~PPENV_TA_COUNT_MASK;
+    }
+#pragma unroll
+    for (int k = 0; k < PP_TA_OUTCOME_COUNTS; ++k) {
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) c[k] += __shfl_xor(c[k], off, 64);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < PP_TA_OUTCOME_COUNTS; ++k) wave_sum[wave][k] = c[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t[PP_TA_OUTCOME_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+        for (int w = 0; w < 16; ++w) {
+#pragma unroll
+            for (int k = 0; k < PP_TA_OUTCOME_COUNTS; ++k) t[k] += wave_sum[w][k];
+        }
+        pp_ta_outcome o = *outcome;
+        ta_outcome_window(o, (uint64_t)n, t);
+        *outcome = o;
+    }
+}
+
+// include/ppenv_ta_outcome.h: *latched = *live while the play totals are not frozen.  One wave; lane w copies 8-byte word w.
+__global__ __launch_bounds__(64) void ta_outcome_latch_kernel(const pp_ta_outcome* __restrict__ live, const ppenv_play_totals* __restrict__ totals,
+                                                              int64_t games_num, pp_ta_outcome* __restrict__ latched) {
+    if (!ta_outcome_latches(totals->games, games_num)) return;       // uniform
+    constexpr int kWords = (int)(sizeof(pp_ta_outcome) / sizeof(uint64_t));
+    static_assert(kWords <= 64, "one lane per word");
+    if ((int)threadIdx.x < kWords) reinterpret_cast<uint64_t*>(latched)[threadIdx.x] = reinterpret_cast<const uint64_t*>(live)[threadIdx.x];
 }
 
 // ---- 4-actor variant: compute_humanoid1_pingpong_reward (== TT's, T4:1113-1278) and its mirror
@@ -104,8 +148,8 @@ int use_device_of(const void* dev_ptr) {
 }  // namespace
 
 // TA:1162-1166 as a launch of its own (also used by the fused step of ppenv_ta_sim.hip); not part of the public ABI
-int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, void* stream) {
-    hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, flags_dev, any_reset_dev);
+int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, pp_ta_outcome* outcome_dev, void* stream) {
+    hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, n, flags_dev, any_reset_dev, outcome_dev);
     return pp_launched("launching ta_clear_counts_kernel failed");
 }
 
@@ -127,23 +171,55 @@ extern "C" int ppenv_t4_rewards(const ppenv_t4_params* params, const float* rb_s
     return pp_launched("launching t4_rewards_kernel failed");
 }
 
-extern "C" int ppenv_ta_post_physics_step(const ppenv_ta_params* params, const float* rb_states_dev, const float* initial_rb_states_dev,
-                                          float* root_states_dev, float* dof_states_dev, const float* dof_force_dev,
-                                          const float* pre_ball_vx_dev, const float* reset_override_dev, uint32_t* flags_dev,
-                                          uint32_t* episode_dev, int64_t* progress_dev, float* obs_dev, float* rew_dev, int64_t* reset_dev,
-                                          uint32_t* scratch_any_reset_dev, void* stream) {
+namespace {
+int ta_post_physics(const char* who, const ppenv_ta_params* params, const float* rb_states_dev, const float* initial_rb_states_dev, float* root_states_dev,
+                    float* dof_states_dev, const float* dof_force_dev, const float* pre_ball_vx_dev, const float* reset_override_dev, uint32_t* flags_dev,
+                    uint32_t* episode_dev, int64_t* progress_dev, float* obs_dev, float* rew_dev, int64_t* reset_dev, uint32_t* scratch_any_reset_dev,
+                    pp_ta_outcome* outcome_dev, void* stream) {
     if (!params || params->num_envs <= 0 || !rb_states_dev || !initial_rb_states_dev || !root_states_dev || !dof_states_dev ||
         !dof_force_dev || !pre_ball_vx_dev || !flags_dev || !episode_dev || !progress_dev || !obs_dev || !rew_dev || !reset_dev ||
         !scratch_any_reset_dev) {
-        ppenv_set_error("ppenv_ta_post_physics_step: NULL argument or num_envs <= 0");
+        pp_set_errorf("%s: NULL argument or num_envs <= 0", who);
         return PPENV_EINVAL;
     }
+    if (reinterpret_cast<uintptr_t>(outcome_dev) & 7) { pp_set_errorf("%s: the outcome struct must be 8-byte aligned", who); return PPENV_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
     const int n = params->num_envs;
     if (int rc = use_device_of(obs_dev)) return rc;
     hipLaunchKernelGGL(ta_post_physics_kernel, dim3((n + kTaBlock - 1) / kTaBlock), dim3(kTaBlock), 0, s, *params, rb_states_dev,
                        initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev, reset_override_dev, flags_dev,
                        episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev, scratch_any_reset_dev);
-    hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, s, n, flags_dev, scratch_any_reset_dev);
+    hipLaunchKernelGGL(ta_clear_counts_kernel, dim3(1), dim3(1024), 0, s, n, flags_dev, scratch_any_reset_dev, outcome_dev);
     return pp_launched("launching the TA post-physics kernels failed");
+}
+}  // namespace
+
+extern "C" int ppenv_ta_post_physics_step(const ppenv_ta_params* params, const float* rb_states_dev, const float* initial_rb_states_dev,
+                                          float* root_states_dev, float* dof_states_dev, const float* dof_force_dev,
+                                          const float* pre_ball_vx_dev, const float* reset_override_dev, uint32_t* flags_dev,
+                                          uint32_t* episode_dev, int64_t* progress_dev, float* obs_dev, float* rew_dev, int64_t* reset_dev,
+                                          uint32_t* scratch_any_reset_dev, void* stream) {
+    return ta_post_physics("ppenv_ta_post_physics_step", params, rb_states_dev, initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev,
+                           pre_ball_vx_dev, reset_override_dev, flags_dev, episode_dev, progress_dev, obs_dev, rew_dev, reset_dev, scratch_any_reset_dev,
+                           nullptr, stream);
+}
+
+extern "C" int pp_ta_post_physics_step_outcome(const ppenv_ta_params* params, const float* rb_states_dev, const float* initial_rb_states_dev,
+                                               float* root_states_dev, float* dof_states_dev, const float* dof_force_dev,
+                                               const float* pre_ball_vx_dev, const float* reset_override_dev, uint32_t* flags_dev,
+                                               uint32_t* episode_dev, int64_t* progress_dev, float* obs_dev, float* rew_dev, int64_t* reset_dev,
+                                               uint32_t* scratch_any_reset_dev, pp_ta_outcome* outcome_dev, void* stream) {
+    return ta_post_physics("pp_ta_post_physics_step_outcome", params, rb_states_dev, initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev,
+                           pre_ball_vx_dev, reset_override_dev, flags_dev, episode_dev, progress_dev, obs_dev, rew_dev, reset_dev, scratch_any_reset_dev,
+                           outcome_dev, stream);
+}
+
+extern "C" int pp_ta_outcome_latch(const pp_ta_outcome* live, const ppenv_play_totals* totals, int64_t games_num, pp_ta_outcome* latched, void* stream) {
+    if (!live || !totals || !latched || games_num < 1 || ((reinterpret_cast<uintptr_t>(live) | reinterpret_cast<uintptr_t>(latched)) & 7)) {
+        ppenv_set_error("pp_ta_outcome_latch: NULL pointer, a struct that is not 8-byte aligned, or games_num < 1");
+        return PPENV_EINVAL;
+    }
+    if (int rc = use_device_of(latched)) return rc;
+    hipLaunchKernelGGL(ta_outcome_latch_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, live, totals, games_num, latched);
+    return pp_launched("launching ta_outcome_latch_kernel failed");
 }

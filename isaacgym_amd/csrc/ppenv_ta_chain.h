@@ -2,6 +2,7 @@
 #pragma once
 
 #include "ppenv_ta_device.h"
+#include "../../include/ppenv_ta_outcome.h"
 
 namespace pp {
 namespace ta {
@@ -39,6 +40,8 @@ struct TAChainArgs {
     const float* dr_es;           // [N] restitution scale of the humanoid's shapes and the paddle
     const float* dr_fs;           // [N] friction scale of the same
     float dr_act_sigma, dr_obs_sigma;
+    // outcome counts (pp_ta_sim_set_outcome; NULL: off): the workgroup that clears the count bits sums them into it first
+    pp_ta_outcome* outcome;
     bool dr_on() const { return dr_kp || dr_kd || dr_ms || dr_es || dr_fs || dr_act_sigma > 0.f || dr_obs_sigma > 0.f; }
 };
 

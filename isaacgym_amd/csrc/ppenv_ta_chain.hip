@@ -40,6 +40,7 @@
 #endif
 #include PPENV_TA_MODEL_HEADER
 #include "ppenv_ta_chain.h"
+#include "ppenv_ta_outcome_device.h"
 
 using namespace pp;
 using namespace pp::ta;
@@ -1101,8 +1102,33 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
         old = __shfl(old, 0);
         if ((old >> 1) == gridDim.x - 1) {
             __threadfence();
-            if ((old & 1u) || any_here)
+            if ((old & 1u) || any_here) {
+                // outcome counts (include/ppenv_ta_outcome.h; NULL: off): this wave sums the five bits over all n words before they go —
+                // four independent loads in flight per lane and trip, a butterfly, and lane 0 alone updates the struct, which only a later
+                // launch reads.  The clear below stays a loop of atomics without a return value: nothing waits for an L2 round trip per word.
+                if (a.outcome) {
+                    uint32_t c[PP_TA_OUTCOME_COUNTS] = {0u, 0u, 0u, 0u, 0u};
+                    for (int i = lane; i < n; i += 256) {
+                        uint32_t w[4];
+#pragma unroll
+                        for (int k = 0; k < 4; k++)
+                            w[k] = i + 64 * k < n ? __hip_atomic_load(&a.flags[i + 64 * k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+#pragma unroll
+                        for (int k = 0; k < 4; k++) ta_outcome_word(w[k], c);
+                    }
+#pragma unroll
+                    for (int k = 0; k < PP_TA_OUTCOME_COUNTS; k++) {
+#pragma unroll
+                        for (int off = 32; off >= 1; off >>= 1) c[k] += __shfl_xor(c[k], off, 64);
+                    }
+                    if (lane == 0) {
+                        pp_ta_outcome o = *a.outcome;
+                        ta_outcome_window(o, (uint64_t)n, c);
+                        *a.outcome = o;
+                    }
+                }
                 for (int i = lane; i < n; i += 64) __hip_atomic_fetch_and(&a.flags[i], ~PPENV_TA_COUNT_MASK, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
             if (lane == 0) __hip_atomic_store(a.scratch, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero again for the next launch
         }
     }

@@ -24,7 +24,7 @@ using namespace pp::ta;
 using std::min;
 
 #include "ppenv_host.h"
-int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, void* stream);   // ppenv_ta.hip
+int ppenv_ta_clear_counts(int n, uint32_t* flags_dev, uint32_t* any_reset_dev, pp_ta_outcome* outcome_dev, void* stream);   // ppenv_ta.hip
 
 namespace {
 // Diagnostic builds only (-DTA_STAMP, tools/gpu_ta_stamps.py): shader-clock stamps of the quad kernel's phases, lane 0 of each workgroup.
@@ -541,6 +541,7 @@ struct ppenv_ta_sim {
     unsigned short* pin_out;
     int pin_ld;
     ppenv_ta_randomization dr;   // ppenv_ta_sim_set_randomization (chain-wave kernel only); all NULL / 0: off
+    pp_ta_outcome* outcome;      // pp_ta_sim_set_outcome (include/ppenv_ta_outcome.h; every kernel); NULL: off
 };
 
 namespace {
@@ -574,6 +575,13 @@ int ppenv_ta_sim_set_randomization(ppenv_ta_sim* s, const ppenv_ta_randomization
     if (!s->chain) { ppenv_set_error("ppenv_ta_sim_set_randomization: only the chain-wave kernel reads the tables (ppenv_ta_sim_kernel() == 2: the compiled G1 model)"); return PPENV_EINVAL; }
     if (!(dr->action_noise_sigma >= 0.f) || !(dr->observation_noise_sigma >= 0.f)) { ppenv_set_error("ppenv_ta_sim_set_randomization: noise amplitudes must be >= 0"); return PPENV_EINVAL; }
     s->dr = *dr;
+    return PPENV_OK;
+}
+/* the outcome counts summed by the launch that clears the count bits (include/ppenv_ta_outcome.h): dev NULL switches it off */
+int pp_ta_sim_set_outcome(ppenv_ta_sim* s, pp_ta_outcome* dev) {
+    if (!s) { ppenv_set_error("pp_ta_sim_set_outcome: NULL handle"); return PPENV_EINVAL; }
+    if (reinterpret_cast<uintptr_t>(dev) & 7) { ppenv_set_error("pp_ta_sim_set_outcome: the struct must be 8-byte aligned"); return PPENV_EINVAL; }
+    s->outcome = dev;
     return PPENV_OK;
 }
 /* which kernel ppenv_ta_step launches: 2 chain-wave, 1 quad, 0 one lane per env */
@@ -707,15 +715,16 @@ int ppenv_ta_step(ppenv_ta_sim* s, const ppenv_ta_params* params, const float* a
                       reset_override_dev, flags_dev, episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev, scratch_any_reset_dev, s->status.dev,
                       s->pin_mean, s->pin_inv_std, s->pin_clip, s->pin_out, s->pin_ld,
                       s->dr.dof_stiffness_scale, s->dr.dof_damping_scale, s->dr.link_mass_scale, s->dr.restitution_scale, s->dr.friction_scale,
-                      s->dr.action_noise_sigma, s->dr.observation_noise_sigma};
+                      s->dr.action_noise_sigma, s->dr.observation_noise_sigma, s->outcome};
         return ta_chain_launch(s->host.sc, a, stream);
     }
     if (!rb_states_dev) { ppenv_set_error("ppenv_ta_step: rb_states may only be NULL with the chain-wave kernel (the compiled G1 model)"); return PPENV_EINVAL; }
     if (!s->quad) {   // another tree, or PPENV_TA_KERNEL=lane: the two launches
         int rc = ppenv_ta_simulate(s, n, actions_dev, root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev, stream);
         if (rc) return rc;
-        return ppenv_ta_post_physics_step(params, rb_states_dev, initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev,
-                                          reset_override_dev, flags_dev, episode_dev, progress_dev, obs_dev, rew_dev, reset_dev, scratch_any_reset_dev, stream);
+        return pp_ta_post_physics_step_outcome(params, rb_states_dev, initial_rb_states_dev, root_states_dev, dof_states_dev, dof_force_dev, pre_ball_vx_dev,
+                                               reset_override_dev, flags_dev, episode_dev, progress_dev, obs_dev, rew_dev, reset_dev, scratch_any_reset_dev,
+                                               s->outcome, stream);
     }
     hipStream_t st = (hipStream_t)stream;
     TaskArgs t{*params, initial_rb_states_dev, reset_override_dev, flags_dev, episode_dev, (long long*)progress_dev, obs_dev, rew_dev, (long long*)reset_dev,
@@ -723,7 +732,7 @@ int ppenv_ta_step(ppenv_ta_sim* s, const ppenv_ta_params* params, const float* a
     hipLaunchKernelGGL((ta_sim_quad_kernel<true, true>), dim3((n + kQuadEnvs - 1) / kQuadEnvs), dim3(64), 0, st, s->dev, s->host.sc, s->devK, n, actions_dev,
                        root_states_dev, dof_states_dev, rb_states_dev, dof_force_dev, pre_ball_vx_dev, t);
     if (int rc = pp_launched("launching the fused 27-dof step failed")) return rc;
-    return ppenv_ta_clear_counts(n, flags_dev, scratch_any_reset_dev, stream);
+    return ppenv_ta_clear_counts(n, flags_dev, scratch_any_reset_dev, s->outcome, stream);
 }
 
 int ppenv_ta_pd_targets(ppenv_ta_sim* s, int32_t n, const float* actions_dev, float* pd_tar_dev, void* stream) {

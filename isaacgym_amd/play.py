@@ -33,6 +33,29 @@ import torch
 
 from . import _lib
 from ._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ctypes mirror of ppenv_play_totals (bound in _lib.load)
+from ._lib import TA_OUTCOME_NAMES, TAOutcome
+
+# the reference's five prints (TA:1164-1168), in its order and wording
+OUTCOME_PRINTS = (("fall_down", "the sum of the huamnoid which fall down:"), ("closer", "the sum of the envs which are closer to the paddle:"),
+                  ("hit_paddle", "the sum of the envs which hit the paddle:"), ("cross_net", "the sum of the envs which cross the net:"),
+                  ("hit_table", "the sum of the envs which hit the table:"))
+
+
+def outcomes_dict(t):
+    """A host copy of pp_ta_outcome (TAOutcome) -> dict(windows, envs, the five counts by name, <name>_rate = count / envs — None while
+    no window was counted — and last_envs, last_<name>: the most recent window alone)."""
+    envs = int(t.envs)
+    out = dict(windows=int(t.windows), envs=envs, last_envs=int(t.last_envs))
+    for k, name in enumerate(TA_OUTCOME_NAMES):
+        out[name] = int(t.count[k])
+        out[f"{name}_rate"] = int(t.count[k]) / envs if envs > 0 else None
+        out[f"last_{name}"] = int(t.last[k])
+    return out
+
+
+def outcome_lines(o):
+    """The reference's five lines for an outcomes dict, as rates of the envs over all windows."""
+    return [f"{text} {o[name + '_rate']} of the envs ({o[name]} / {o['envs']} in {o['windows']} windows)" for name, text in OUTCOME_PRINTS]
 
 
 def totals_dict(t, num_agents=MAX_AGENTS):
@@ -113,14 +136,24 @@ class EpisodeStats:
         """cur_reward, cur_steps and the totals as host bytes (the tests compare them)."""
         return self.cur_reward.cpu().numpy().tobytes(), self.cur_steps.cpu().numpy().tobytes(), self._totals.cpu().numpy().tobytes()
 
+    def latch_outcome(self, live, latched):
+        """pp_ta_outcome_latch (include/ppenv_ta_outcome.h): latched = live (two pp_ta_outcome tensors) while the totals are not frozen.  One
+        launch, before the accumulate of the same control step: `latched` then stops with the totals."""
+        _lib.check(self.L.pp_ta_outcome_latch(live.data_ptr(), self._totals.data_ptr(), self.games_num, latched.data_ptr(), _lib.stream(self.device)),
+                   self.L)
+
 
 class Player:
     """rl_games' BasePlayer.run on a task from isaacgym_amd.make(...) (any of the five registry names; the 4-actor task has two rows per
     env) under an RLGamesPolicy.  The defaults are rl_games' player defaults.
     sigma: train.py:214's override — the policy's log-std is filled with it, so sigma = exp(x) (rl_games' _override_sigma for a fixed
-    sigma); it matters only with deterministic=False."""
+    sigma); it matters only with deterministic=False.
+    outcomes: the 27-dof task's five head-counts (task.enable_outcomes(); the other tasks raise ValueError), zeroed by start() and latched
+    on the device after every env step under the totals' freeze rule: run()'s `outcomes` are those of the step the totals stopped at,
+    whatever poll_every is."""
 
-    def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None):
+    def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
+                 outcomes=False):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -142,6 +175,10 @@ class Player:
         if recorder is not None and recorder.renderer.task is not task:
             raise ValueError("the recorder renders another task")
         self.recorder = recorder
+        self.outcome = self._latched = None
+        if outcomes:
+            self.outcome = task.enable_outcomes()
+            self._latched = torch.zeros_like(self.outcome)
         self.steps_played = 0
         self.actions = None
         self._obs = None
@@ -150,6 +187,9 @@ class Player:
         """Every env to the start of an episode, the accounting to zero, the action-draw counter to zero (a run is a function of the seed)."""
         self.task.reset_idx()
         self.stats.reset()
+        if self.outcome is not None:
+            self.outcome.zero_()
+            self._latched.zero_()
         self.policy._counter = 0
         self._obs = self.task.reset()["obs"]
         self.steps_played = 0
@@ -160,15 +200,24 @@ class Player:
             self.start()
         self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
         obs, rew, done, _ = self.task.step(self.actions)
+        if self.outcome is not None:
+            self.stats.latch_outcome(self.outcome, self._latched)
         self.stats.accumulate(rew, done)
         if self.recorder is not None:
             self.recorder.capture()
         self._obs = obs["obs"]
         self.steps_played += 1
 
+    def read_outcomes(self):
+        """One host copy of the LATCHED outcome struct -> outcomes_dict (None with outcomes off)."""
+        if self._latched is None:
+            return None
+        return outcomes_dict(TAOutcome.from_buffer_copy(self._latched.cpu().numpy().tobytes()))
+
     def run(self, on_poll=None):
         """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
-        host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds)."""
+        host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds); with
+        outcomes=True also `outcomes` (outcomes_dict of the latched struct)."""
         self.start()
         t0 = time.perf_counter()
         tot = None
@@ -187,6 +236,8 @@ class Player:
                 on_poll(tot)
         out = summarize(tot, self.num_agents)
         out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
+        if self.outcome is not None:
+            out["outcomes"] = self.read_outcomes()
         if self.recorder is not None:
             out["captured_frames"] = self.recorder.captured
         return out
@@ -205,6 +256,7 @@ def parse_args(argv=None):
     ap.add_argument("--cfg-dir", default=None, help="a reference cfg/ directory to compose the task yaml from")
     ap.add_argument("--poll-every", type=int, default=64, help="control steps between two host reads of the totals")
     ap.add_argument("--max-steps", type=int, default=108000)
+    ap.add_argument("--outcomes", action="store_true", help="27-dof task: print the reference's five outcome counts (TA:1164-1168) as rates of the envs")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -248,7 +300,7 @@ def main(argv=None):
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
     recorder = make_recorder(task, args) if args.capture else None
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
-                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder)
+                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes)
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -256,9 +308,15 @@ def main(argv=None):
         if n > 0:
             print(f"reward: {(tot['reward'][0] - last['reward'][0]) / n} steps: {(tot['steps'] - last['steps']) / n}", flush=True)
         last.update(games=tot["games"], steps=tot["steps"], reward=list(tot["reward"]))
+        if args.outcomes:
+            o = pl.read_outcomes()
+            if o["windows"] > 0:
+                print("\n".join(outcome_lines(o)), flush=True)
 
     res = pl.run(on_poll=on_poll)
     print(f"av reward: {res['av_reward']} av steps: {res['av_steps']}")
+    if args.outcomes:
+        print("\n".join(outcome_lines(res["outcomes"])) if res["outcomes"]["windows"] > 0 else "no env has reset: no outcome window yet")
     for a, p in enumerate(res["per_agent"]):
         print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)

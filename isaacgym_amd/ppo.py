@@ -399,9 +399,13 @@ class PPOTrainer:
     RolloutCollector; the network is NativeActorCritic (nn.Linear's default initialisation, rl_games' `initializer: default`) with a learnable
     fixed log-std (its `sigma` parameter, initialised to sigma_init) and, with normalize_value, a value RunningMeanStd of width 1.
     group: a torch.distributed process group (None: the default group, if one is initialised); data-parallel when it has more than one rank, or
-    with force=True (the collectives with one rank, as bench.py --force-dist).  See the module docstring for what is per rank and what is global."""
+    with force=True (the collectives with one rank, as bench.py --force-dist).  See the module docstring for what is per rank and what is global.
+    outcomes: the 27-dof task's five head-counts (task.enable_outcomes(); the other tasks raise ValueError) — train_epoch() then also returns
+    outcome_windows, outcome_envs and the five outcome_<name> rates of the most recent window.  The step kernel's clear sums them into a struct
+    of their own: parameters, moments, scaler, statistics and meter stay bitwise those of a run without.  Not checkpointed: the envs restart on
+    resume."""
 
-    def __init__(self, task, cfg=None, seed=0, group=None, force=False):
+    def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if getattr(task, "randomize", False):
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
@@ -450,6 +454,7 @@ class PPOTrainer:
         self.meter = GameMeter(env.num_envs, n // env.num_envs, cfg.games_to_track, dev)     # rl_games' score: per rank, as in rl_games
         self.last_mean_rewards = NO_SCORE                                  # the score of the best checkpoint so far (fit)
         self.epoch, self.frame = 0, 0
+        self.outcome = task.enable_outcomes() if outcomes else None         # pp_ta_outcome, int64 [16] (include/ppenv_ta_outcome.h)
         if self.multi:
             self._broadcast_start()
 
@@ -574,6 +579,20 @@ class PPOTrainer:
         self.ep_len.copy_(torch.where(end < 0, self.ep_len + H, (H - 1 - end).float()))
         return out
 
+    @torch.no_grad()
+    def _outcomes(self):
+        """outcome_windows (cumulative, this rank's), outcome_envs = last_envs and outcome_<name> = last[k] / last_envs as fp32 (0 before the
+        first window), 0-dim device tensors.  Data-parallel: last[] and last_envs are summed over the ranks (one int64 all-reduce)."""
+        o = _lib.TAOutcome
+        t = self.outcome
+        last = t[o.last_envs.offset // 8:o.last.offset // 8 + len(_lib.TA_OUTCOME_NAMES)].clone()        # last_envs, last[5]: adjacent words
+        if self.multi:
+            torch.distributed.all_reduce(last, op=torch.distributed.ReduceOp.SUM, group=self.group)
+        rates = last[1:].float() / last[0].clamp(min=1).float()
+        out = dict(outcome_windows=t[o.windows.offset // 8].clone(), outcome_envs=last[0])
+        out.update({f"outcome_{name}": rates[k] for k, name in enumerate(_lib.TA_OUTCOME_NAMES)})
+        return out
+
     def train_epoch(self):
         """One epoch; no host synchronisation.  -> dict of 0-dim device tensors: the STATS averaged over the epoch's minibatch steps, the
         loss scale, the steps skipped in this epoch, the last gradient norm, the mean return / length of the episodes finished in the
@@ -608,6 +627,8 @@ class PPOTrainer:
                    mean_length=ep[1] / n)
         score = self.meter.fields(score)
         out.update(meter_return=score["mean_reward"], meter_length=score["mean_length"], meter_games=score["current_size"])
+        if self.outcome is not None:
+            out.update(self._outcomes())
         return out
 
     # -- checkpoints --
@@ -714,7 +735,9 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
             dt = time.perf_counter() - t0
             print(f"epoch {epoch} frames {trainer.frame} fps {(trainer.frame - frame0) / dt:.0f} loss {vals['loss']:.4g} a {vals['a_loss']:.4g} "
                   f"c {vals['c_loss']:.4g} kl {vals['kl']:.3g} clip {vals['clip_frac']:.3f} scale {vals['scale']:.0f} skipped {vals['skipped']:.0f} "
-                  f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f} score {score:.6g} ({games} games)", flush=True)
+                  f"return {vals['mean_return']:.4g} length {vals['mean_length']:.1f} score {score:.6g} ({games} games)" +
+                  ("".join(f" {name} {vals['outcome_' + name]:.3f}" for name in _lib.TA_OUTCOME_NAMES) +
+                   f" ({vals['outcome_windows']:.0f} windows)" if "outcome_windows" in vals else ""), flush=True)
             if stopped:
                 print(f"score {score} above score_to_win {cfg.score_to_win}: stopping", flush=True)
     out = dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
@@ -769,6 +792,7 @@ def main(argv=None):
     ap.add_argument("--multi-gpu", action="store_true", help="data-parallel, one rank per process under python -m torch.distributed.run")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl (RCCL) one GPU per rank; gloo: ranks may share a GPU")
     ap.add_argument("--force-dist", action="store_true", help="with --multi-gpu: accept a one-rank world and run the collectives anyway")
+    ap.add_argument("--outcomes", action="store_true", help="27-dof task: report the reference's five outcome counts (TA:1164-1168) as rates of the envs per epoch")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -806,7 +830,7 @@ def main(argv=None):
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, multi_gpu=True, device=dev, cfg=task_cfg)
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
-    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist)
+    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes)
     if args.checkpoint:
         tr.load(args.checkpoint)                                   # every rank: the same file
         if rank == 0:

@@ -14,6 +14,24 @@ from . import _lib, scene
 from .dr import Randomizable
 
 
+OUTCOME_WORDS = C.sizeof(_lib.TAOutcome) // 8      # pp_ta_outcome as an int64 tensor: 16 words
+
+
+def check_outcome(t, device):
+    if t.dtype != torch.int64 or t.numel() != OUTCOME_WORDS or not t.is_contiguous() or t.device != torch.device(device):
+        raise ValueError(f"the outcome struct is a contiguous int64 [{OUTCOME_WORDS}] tensor on {device} (pp_ta_outcome)")
+
+
+def outcome_fields(t):
+    """pp_ta_outcome (an int64 [16] tensor) as a dict of 0-dim views: windows, envs, the five counts by name, last_envs and last_<name>."""
+    o = _lib.TAOutcome
+    out = dict(windows=t[o.windows.offset // 8], envs=t[o.envs.offset // 8], last_envs=t[o.last_envs.offset // 8])
+    for k, name in enumerate(_lib.TA_OUTCOME_NAMES):
+        out[name] = t[o.count.offset // 8 + k]
+        out[f"last_{name}"] = t[o.last.offset // 8 + k]
+    return out
+
+
 class TAState:
     """Per-env buffers the reference keeps across steps (progress, sticky/count flags) plus the outputs."""
 
@@ -34,7 +52,9 @@ class TAState:
     def _ck(self, rc):
         _lib.check(rc, self.L)          # the message is the thread-local one of THIS library instance
 
-    def post_physics_step(self, rb_states, initial_rb_states, root_states, dof_states, dof_force, pre_ball_vx, reset_override=None):
+    def post_physics_step(self, rb_states, initial_rb_states, root_states, dof_states, dof_force, pre_ball_vx, reset_override=None, outcome=None):
+        """outcome: an int64 [16] device tensor (pp_ta_outcome, include/ppenv_ta_outcome.h): the launch that clears the count flags adds
+        their sums to it first (pp_ta_post_physics_step_outcome).  None: ppenv_ta_post_physics_step."""
         n = self.num_envs
         irb_n = 1 if self.params.initial_rb_shared else n
         for t, numel in ((rb_states, n * 42 * 13), (initial_rb_states, irb_n * 42 * 13), (root_states, n * 39), (dof_states, n * 54),
@@ -44,11 +64,15 @@ class TAState:
         if reset_override is not None:
             ov = reset_override.to(self.device, torch.float32).reshape(n, 5).contiguous()
         # (the library launches on the device that owns obs_buf, whatever the caller's current device is)
-        self._ck(self.L.ppenv_ta_post_physics_step(
-            C.byref(self.params), rb_states.data_ptr(), initial_rb_states.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(),
-            dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.ptr(ov), self.flags.data_ptr(),
-            self.episode.data_ptr(), self.progress_buf.data_ptr(), self.obs_buf.data_ptr(), self.rew_buf.data_ptr(),
-            self.reset_buf.data_ptr(), self._any_reset.data_ptr(), _lib.stream(self.device)))
+        args = (C.byref(self.params), rb_states.data_ptr(), initial_rb_states.data_ptr(), root_states.data_ptr(), dof_states.data_ptr(),
+                dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.ptr(ov), self.flags.data_ptr(),
+                self.episode.data_ptr(), self.progress_buf.data_ptr(), self.obs_buf.data_ptr(), self.rew_buf.data_ptr(),
+                self.reset_buf.data_ptr(), self._any_reset.data_ptr())
+        if outcome is None:
+            self._ck(self.L.ppenv_ta_post_physics_step(*args, _lib.stream(self.device)))
+        else:
+            check_outcome(outcome, self.device)
+            self._ck(self.L.pp_ta_post_physics_step_outcome(*args, outcome.data_ptr(), _lib.stream(self.device)))
         if ov is not None:
             torch.cuda.current_stream(self.device).synchronize()   # keep `ov` alive until the kernel has read it
 
@@ -140,6 +164,14 @@ class TASim(Randomizable):
         if ov is not None:
             torch.cuda.current_stream(self.device).synchronize()
 
+    def set_outcome(self, t=None):
+        """pp_ta_sim_set_outcome: from the next `step` on, the launch that clears the count flags (whichever kernel) adds their sums to
+        t, an int64 [16] tensor (pp_ta_outcome; zeroed by the caller), first.  None: off.  The caller keeps the tensor alive."""
+        if t is not None:
+            check_outcome(t, self.device)
+        self._ck(self.L.pp_ta_sim_set_outcome(self.h, _lib.ptr(t)))
+        self._outcome = t
+
     def set_policy_input(self, out=None, mean=None, inv_std=None, clip=5.0):
         """ppenv_ta_sim_set_policy_input: from the next `step` on the chain-wave kernel also writes out [N, ld] fp16 =
         clamp((obs - mean) * inv_std, +-clip), zero beyond column 312 (what policy.prepare_input makes of obs_buf).  out None: off.
@@ -225,6 +257,7 @@ class TAEnv:
         self.obs_buf, self.rew_buf, self.reset_buf, self.progress_buf = self.state.obs_buf, self.state.rew_buf, self.state.reset_buf, self.state.progress_buf
         self.reset_buf.fill_(1)   # upstream VecTask.allocate_buffers
         self.sim.reset_buf = self.reset_buf       # what sim.apply_reset_randomization reads
+        self.outcome = None                       # enable_outcomes(): the pp_ta_outcome struct of this env
 
     def step(self, actions, obs=None, rew=None, reset=None):
         """obs / rew / reset (fused mode only): tensors that receive this step's observations, rewards and reset flags instead of
@@ -240,7 +273,8 @@ class TAEnv:
         else:
             assert obs is None and rew is None and reset is None, "output slices need the fused step"
             self.sim.simulate(actions, self.root_states, self.dof_states, self._rb_states, self.dof_force_tensor, self.pre_ball_vx)
-            self.state.post_physics_step(self._rb_states, self.initial_rb_states, self.root_states, self.dof_states, self.dof_force_tensor, self.pre_ball_vx)
+            self.state.post_physics_step(self._rb_states, self.initial_rb_states, self.root_states, self.dof_states, self.dof_force_tensor, self.pre_ball_vx,
+                                         outcome=self.outcome)
         return {"obs": self.obs_buf}, self.rew_buf, self.reset_buf, {}
 
     @property
@@ -250,6 +284,21 @@ class TAEnv:
         if not self.materialize_rb:
             self.sim.forward_kinematics(self.root_states, self.dof_states, self._rb_states)
         return self._rb_states
+
+    def enable_outcomes(self):
+        """The reference's five head-counts (TA:1161-1175; include/ppenv_ta_outcome.h): a zeroed int64 [16] tensor (pp_ta_outcome) that every
+        later step's clear of the count flags adds to.  -> that tensor (also `outcome`); a second call returns the same one."""
+        if self.outcome is None:
+            self.outcome = torch.zeros(OUTCOME_WORDS, dtype=torch.int64, device=self.device)
+            self.sim.set_outcome(self.outcome)
+        return self.outcome
+
+    def outcome_fields(self, t=None):
+        """`outcome` (or another pp_ta_outcome tensor, a latched copy for instance) as a dict of 0-dim device views (outcome_fields)."""
+        t = self.outcome if t is None else t
+        if t is None:
+            raise ValueError("the outcome counts are off: call enable_outcomes() first")
+        return outcome_fields(t)
 
     def set_policy_input(self, out=None, mean=None, inv_std=None, clip=5.0):
         """The step kernel writes the policy's first-layer input itself (TASim.set_policy_input; NativeMLP.attach_env wires it)."""

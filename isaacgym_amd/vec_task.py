@@ -219,6 +219,14 @@ class VecTask:
         self.env.set_randomization(**kw)
         self.randomize_buf.zero_()
 
+    outcomes = None          # the 27-dof task's pp_ta_outcome tensor once enable_outcomes() was called
+
+    def enable_outcomes(self):
+        """The outcome head-counts exist for the 27-dof task only (HumanoidPingpongTiltNESSparse27DOF.enable_outcomes)."""
+        raise ValueError(f"{type(self).__name__}: no outcome counts — the reference classes of the 7-dof and 4-actor tasks keep no count tensors "
+                         "(their per-step prints, TT:1216, 1236, sit inside the fused reward and are not built); "
+                         "HumanoidPingpongTiltNESSparse27DOFG1 has them (TA:1161-1175)")
+
     def reset(self):
         """Observation dictionary of the current state (upstream VecTask.reset does not step the simulator)."""
         return self._obs_dict()
@@ -472,6 +480,15 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
             self.extras["progress_mean"] = self.progress_buf.float().mean()
         self.extras["time_outs"] = self.timeout_buf if self.rl_device == self.device else self.timeout_buf.to(self.rl_device)
         return self._obs_dict(), self._to_rl(self.rew_buf), self._to_rl(self.reset_buf), self.extras
+
+    def enable_outcomes(self):
+        """The five head-counts the reference prints whenever an env resets (TA:1161-1175: fell down, close to the paddle, hit the paddle,
+        crossed the net, hit the table), summed on the device by the launch that clears them (include/ppenv_ta_outcome.h).  -> the
+        pp_ta_outcome struct as an int64 [16] device tensor, from now on also `outcomes` and extras["outcomes"] (no host read);
+        env.outcome_fields() names its words."""
+        self.outcomes = self.env.enable_outcomes()
+        self.extras["outcomes"] = self.outcomes
+        return self.outcomes
 
     def reset_idx(self, env_ids=None):
         """_reset_idx (TA:965-1028) for the listed envs (None: all): root states, dof states, ball y / z and serve of the env's

@@ -13,6 +13,7 @@ critic_coef 4, clip_value, bounds_loss_coef 1e-4, grad_norm 10, normalize_advant
 rl_games itself is not importable here (absent from the reference and the image); the loss terms are restated from its published a2c_continuous /
 common_losses (actor: clipped surrogate; critic: clipped value loss; bound loss on mu beyond +-1.1) — timing context, parity unpinned.
 Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo] [--num-envs 4096] [--minibatch 32768] [--epochs 3]
+--learner ppo --outcomes: the same epochs with the outcome counts on (PPOTrainer(outcomes=True)); the struct is printed with the result.
 --learner ppo --capture: the same epochs with a render.TrainingCapture on the rollout (env 0 at 320 x 240, --capture-samples rays per axis, recordings of
 100 steps back to back, so one is open in every timed epoch and one finishes every 100 steps); reports every epoch's rollout time, what poll() cost after
 it, and what close() waited for at the end (the last copy and the writer).
@@ -41,6 +42,7 @@ ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--capture", action="store_true", help="--learner ppo: record the rollout (render.TrainingCapture), to measure what it costs")
 ap.add_argument("--capture-samples", type=int, default=2, choices=(1, 2, 4))
 ap.add_argument("--capture-ext", default=".npy", choices=(".npy", ".gif"))
+ap.add_argument("--outcomes", action="store_true", help="--learner ppo: PPOTrainer(outcomes=True), the 27-dof task's outcome counts summed by the step kernel's clear")
 ap.add_argument("--force-dist", action="store_true", help="create the nccl group and all-reduce the gradients even with ONE rank (the RCCL path on a one-GPU box)")
 ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share cuda:LOCAL_RANK %% device_count (rehearsal on one GPU)")
 args = ap.parse_args()
@@ -73,7 +75,7 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
     import isaacgym_amd  # noqa: E402
     from isaacgym_amd.ppo import PPOConfig, PPOTrainer  # noqa: E402
     tr = PPOTrainer(isaacgym_amd.make(seed=rank, task="HumanoidPingpongTiltNESSparse27DOFG1", num_envs=n, multi_gpu=True, device=dev),
-                    PPOConfig(minibatch_size=args.minibatch), seed=rank, force=args.force_dist)
+                    PPOConfig(minibatch_size=args.minibatch), seed=rank, force=args.force_dist, outcomes=args.outcomes)
     for _ in range(3):             # a run that has been training for a while (see below)
         tr.col.collect().next_horizon()
         for t in range(H):
@@ -114,6 +116,8 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
     steps = tr.steps_per_epoch
     f = tr.opt.fields()
     extra = {"ms_rollout_each_epoch": roll_each}
+    if args.outcomes:
+        extra["outcomes"] = {k: int(v) for k, v in tr.env.outcome_fields().items()}
     if cap is not None:
         t0 = time.perf_counter()
         videos = cap.close()
