@@ -23,6 +23,15 @@
  *                    render_rays_aa_kernel: the same workgroup over a 16 x 16 tile of SUB-SAMPLES — s^2 consecutive lanes own a pixel, one
  *                    ray each, added across lanes in that order; the pixel's first lane stores the 4 bytes.  samples = 1 launches
  *                    render_rays_kernel itself: the bytes of pp_render_rays.  RGBA only: a mean of depths or ids has no meaning.
+ * A recording (deferred capture): the posed list is a complete, camera-independent description of a frame, 80 bytes per primitive.
+ *   pp_render_pose_anchor  instead of pp_render_pose: the same bytes into posed_out[count][P], plus anchor_out[count] as float4 — words 0 .. 2 of
+ *                    body row `anchor_row` of pose source `anchor_source` of that env, then 0 (zeros for anchor_row < 0 and for an env id out of
+ *                    range).  The caller keeps a ring of such slots.
+ *   pp_render_rays_frames  posed [F][E][P] + anchor [F][E] -> rgba [F, E, H, W, 4] in ONE launch, grid (image tiles, E, F): per workgroup what
+ *                    pp_render_rays (samples 1) / pp_render_rays_aa (2, 4) do for one env of one picture, the same device functions called the
+ *                    same way, so frame f is byte for byte the picture those entries draw from posed[f].  The one difference: a following camera
+ *                    (follow_row >= 0; follow_source is ignored) adds (anchor.x, anchor.y, 0) of that frame and env.  The scene's source[] is never
+ *                    read and may be empty (num_sources 0): a replay has no task.  RGBA only.
  * Images are [E, H, W, 4] uint8; the optional outputs are [E, H, W] fp32 depth (distance along the ray, +inf for sky) and int32
  * primitive id (PP_RENDER_ID_SKY, PP_RENDER_ID_GROUND, or the primitive's index).
  *
@@ -130,6 +139,17 @@ int pp_render_rays(const pp_render_scene* scene, const pp_render_camera* camera,
 /* Launch 2, supersampled: `samples` sub-samples per axis, 1, 2 or 4 (anything else: PPENV_EINVAL); rgba as for pp_render_rays. */
 int pp_render_rays_aa(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const int32_t* env_ids, int32_t count,
                       int32_t samples, uint8_t* rgba, void* stream);
+
+/* Launch 1 of a recording: pp_render_pose + anchor_out [count][4] f32 (16-byte aligned).  anchor_row < 0: zeros; otherwise checked like a
+ * camera's follow row. */
+int pp_render_pose_anchor(const pp_render_scene* scene, const pp_render_prim* prims_dev, const int32_t* env_ids, int32_t count, int32_t anchor_source,
+                          int32_t anchor_row, pp_render_posed* posed_out, float* anchor_out, void* stream);
+
+/* All rays of `frames` recorded frames.  posed [frames][count][scene->num_prims]; anchor [frames][count][4] f32, 16-byte aligned (may be NULL
+ * under a fixed camera); rgba [frames, count, H, W, 4] uint8, 4-byte aligned.  samples 1, 2 or 4; frames 1 .. 65535 and fewer than 2^32 lanes
+ * (256 per 16 x 16 tile of rays) in the launch — a longer recording is cast in several calls over consecutive frame ranges. */
+int pp_render_rays_frames(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const float* anchor, int32_t frames,
+                          int32_t count, int32_t samples, uint8_t* rgba, void* stream);
 
 #ifdef __cplusplus
 }

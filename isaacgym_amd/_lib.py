@@ -362,6 +362,8 @@ def load(path):
     L.pp_render_pose.argtypes = [scenep, vp, vp, i32, vp, vp]
     L.pp_render_rays.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, vp, vp, vp, vp]
     L.pp_render_rays_aa.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, i32, vp, vp]
+    L.pp_render_pose_anchor.argtypes = [scenep, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.pp_render_rays_frames.argtypes = [scenep, C.POINTER(RenderCamera), vp, vp, i32, i32, i32, vp, vp]
     # ---- include/ppenv_ta_outcome.h
     L.pp_ta_sim_set_outcome.argtypes = [vp, vp]
     L.pp_ta_post_physics_step_outcome.argtypes = [C.POINTER(scene.TAParams)] + [vp] * 16

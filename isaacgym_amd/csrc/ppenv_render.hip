@@ -9,6 +9,10 @@
 //                        order render_aa_tree_sum fixes, and the pixel's first lane stores the 4 bytes.  A wave still owns a 16 x 4 strip
 //                        of rays, so a supersampled picture has S^2 times the waves of the plain one (300 workgroups at 320 x 240 become
 //                        1200 / 4800) instead of S^2 sequential rays per lane.
+//   render_pose_anchor_kernel  render_pose_kernel plus one float4 per env: words 0 .. 2 of the anchor row (what a following camera adds to
+//                        eye and target), so a recorded frame needs no pose tensor later.
+//   render_rays_frames_kernel<S>  grid (image tiles, envs, frames): the workgroup of render_rays_kernel (S = 1) or render_rays_aa_kernel (S = 2, 4)
+//                        over posed[F][E][P], `follow` read from anchor[F][E] instead of a pose tensor: a whole recording in one launch.
 // A picture is bound by the intersection arithmetic (pixels x primitives x 2 rays), not by bytes: 640 x 480 x 4 B out, a few KiB in.
 // No atomics, no cross-workgroup communication; the only divergence is the per-lane choice of primitive kind and the shadow ray.
 //
@@ -95,6 +99,69 @@ __global__ __launch_bounds__(kBlock) void render_rays_aa_kernel(const pp_render_
         c.z += __shfl_xor(c.z, m);
     }
     if (k == 0) rgba[((size_t)sel * view.height + y) * view.width + x] = pp::render_aa_pack(c, S);
+}
+
+// render_pose_kernel + the anchor: lane 0 also writes (row[0], row[1], row[2], 0) of body `anchor_row`, zeros without one or for an env id out of range.
+__global__ __launch_bounds__(kBlock) void render_pose_anchor_kernel(const pp_render_scene sc, const pp_render_prim* __restrict__ prims,
+                                                                    const int32_t* __restrict__ env_ids, int32_t anchor_source, int32_t anchor_row,
+                                                                    pp_render_posed* __restrict__ posed, float4* __restrict__ anchor) {
+    const int32_t p = (int32_t)threadIdx.x;
+    const int32_t env = env_ids[blockIdx.x];
+    const bool ok = env >= 0 && env < sc.num_envs;
+    if (p == 0) {
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (ok && anchor_row >= 0) {
+            const float* r = pp::render_row(sc.source[anchor_source], env, anchor_row);
+            a = make_float4(r[0], r[1], r[2], 0.0f);
+        }
+        anchor[blockIdx.x] = a;
+    }
+    if (p >= sc.num_prims) return;
+    pp_render_posed out;
+    if (ok) pp::render_place(sc, prims[p], env, out);
+    else pp::render_place_none(out);
+    posed[(size_t)blockIdx.x * sc.num_prims + p] = out;
+}
+
+// Frame blockIdx.z, env blockIdx.y of a recording: S = 1 is render_rays_kernel's workgroup (a 16 x 16 pixel tile), S = 2, 4 render_rays_aa_kernel<S>'s
+// (a 16 x 16 tile of sub-samples), the same PP_HD calls in the same order.  `follow` comes from anchor[frame][env] (anchor may be NULL under a fixed
+// camera); sc.source is never touched.
+template <int S>
+__global__ __launch_bounds__(kBlock) void render_rays_frames_kernel(const pp_render_scene sc, const pp::RenderView view, const pp_render_posed* __restrict__ posed,
+                                                                    const float4* __restrict__ anchor, int32_t tiles_x, uint32_t* __restrict__ rgba) {
+    constexpr int kSub = S * S, kPixW = kTileW / S, kPixH = kTileH / S;
+    static_assert((S == 1 || S == 2 || S == 4) && kTileW % S == 0 && kTileH % S == 0, "sub-samples per axis: a power of two inside a wave");
+    __shared__ pp_render_posed lds[PP_RENDER_MAX_PRIMS];
+    const int tid = (int)threadIdx.x;
+    const size_t slot = (size_t)blockIdx.z * gridDim.y + blockIdx.y;          // [frame][env]
+    {
+        const uint32_t* src = reinterpret_cast<const uint32_t*>(posed + slot * sc.num_prims);
+        uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
+        for (int w = tid; w < sc.num_prims * kPosedWords; w += kBlock) dst[w] = src[w];
+    }
+    __syncthreads();
+    const int pix = tid / kSub, k = tid % kSub;
+    const int32_t x = (int32_t)(blockIdx.x % tiles_x) * kPixW + pix % kPixW;
+    const int32_t y = (int32_t)(blockIdx.x / tiles_x) * kPixH + pix / kPixW;
+    if (x >= view.width || y >= view.height) return;         // ragged tiles: after the barrier, all lanes of a pixel together
+    pp::V3 follow = pp::mk(0.0f, 0.0f, 0.0f);
+    if (view.follow_row >= 0) {
+        const float4 a = anchor[slot];
+        follow = pp::mk(a.x, a.y, 0.0f);
+    }
+    const size_t at = (slot * view.height + y) * view.width + x;
+    if constexpr (S == 1) {
+        rgba[at] = pp::render_pixel(sc, view, follow, lds, sc.num_prims, (float)x + 0.5f, (float)y + 0.5f).rgba;
+    } else {
+        pp::V3 c = pp::render_aa_sample(sc, view, follow, lds, sc.num_prims, x, y, S, k);
+#pragma unroll
+        for (int m = 1; m < kSub; m *= 2) {                  // render_aa_tree_sum's levels
+            c.x += __shfl_xor(c.x, m);
+            c.y += __shfl_xor(c.y, m);
+            c.z += __shfl_xor(c.z, m);
+        }
+        if (k == 0) rgba[at] = pp::render_aa_pack(c, S);
+    }
 }
 
 bool count_ok(int32_t count, const char* who) {
@@ -217,4 +284,77 @@ extern "C" int pp_render_rays_aa(const pp_render_scene* scene, const pp_render_c
     if (samples == 2) hipLaunchKernelGGL(render_rays_aa_kernel<2>, grid, dim3(kBlock), 0, (hipStream_t)stream, *scene, view, posed, env_ids, tiles_x, out);
     else hipLaunchKernelGGL(render_rays_aa_kernel<4>, grid, dim3(kBlock), 0, (hipStream_t)stream, *scene, view, posed, env_ids, tiles_x, out);
     return pp_launched("launching render_rays_aa_kernel failed");
+}
+
+extern "C" int pp_render_pose_anchor(const pp_render_scene* scene, const pp_render_prim* prims_dev, const int32_t* env_ids, int32_t count,
+                                     int32_t anchor_source, int32_t anchor_row, pp_render_posed* posed_out, float* anchor_out, void* stream) {
+    if (!scene || !prims_dev || !env_ids || !posed_out || !anchor_out) {
+        ppenv_set_error("pp_render_pose_anchor: NULL pointer");
+        return PPENV_EINVAL;
+    }
+    if (!count_ok(count, "pp_render_pose_anchor") || !scene_ok(scene, "pp_render_pose_anchor")) return PPENV_EINVAL;
+    if (anchor_row >= 0 && !row_ok(scene, anchor_source, anchor_row)) {
+        ppenv_set_error("pp_render_pose_anchor: the anchor's source or row is out of range");
+        return PPENV_EINVAL;
+    }
+    if ((uintptr_t)anchor_out % 16 != 0) {
+        ppenv_set_error("pp_render_pose_anchor: anchor_out must be 16-byte aligned");
+        return PPENV_EINVAL;
+    }
+    hipLaunchKernelGGL(render_pose_anchor_kernel, dim3(count), dim3(kBlock), 0, (hipStream_t)stream, *scene, prims_dev, env_ids, anchor_source, anchor_row,
+                       posed_out, reinterpret_cast<float4*>(anchor_out));
+    return pp_launched("launching render_pose_anchor_kernel failed");
+}
+
+extern "C" int pp_render_rays_frames(const pp_render_scene* scene, const pp_render_camera* camera, const pp_render_posed* posed, const float* anchor,
+                                     int32_t frames, int32_t count, int32_t samples, uint8_t* rgba, void* stream) {
+    const char* who = "pp_render_rays_frames";
+    if (!scene || !camera || !posed || !rgba) {
+        pp_set_errorf("%s: NULL pointer", who);
+        return PPENV_EINVAL;
+    }
+    if (!count_ok(count, who)) return PPENV_EINVAL;
+    if (frames < 1) {
+        pp_set_errorf("%s: frames must be positive, got %d", who, frames);
+        return PPENV_EINVAL;
+    }
+    if (!pp::render_samples_ok(samples)) {
+        pp_set_errorf("%s: samples per axis must be 1, 2 or 4, got %d", who, samples);
+        return PPENV_EINVAL;
+    }
+    // the header's constants alone: a replay has no pose tensor (num_sources 0, NULL bases), and none is read here
+    if (scene->num_prims < 0 || scene->num_prims > PP_RENDER_MAX_PRIMS || scene->num_sources < 0 || scene->num_sources > PP_RENDER_MAX_SOURCES) {
+        pp_set_errorf("%s: num_prims must be 0 .. %d and num_sources 0 .. %d", who, PP_RENDER_MAX_PRIMS, PP_RENDER_MAX_SOURCES);
+        return PPENV_EINVAL;
+    }
+    if (camera->width <= 0 || camera->height <= 0 || camera->width > 16384 || camera->height > 16384 || !(camera->fov_deg > 0.0f) || !(camera->fov_deg < 180.0f)) {
+        pp_set_errorf("%s: width and height must be positive (at most 16384) and the field of view inside (0, 180) degrees", who);
+        return PPENV_EINVAL;
+    }
+    if (camera->follow_row >= 0 && !anchor) {
+        pp_set_errorf("%s: a following camera needs the anchor array", who);
+        return PPENV_EINVAL;
+    }
+    if ((uintptr_t)rgba % 4 != 0 || (uintptr_t)anchor % 16 != 0) {
+        pp_set_errorf("%s: rgba must be 4-byte aligned and anchor 16-byte aligned", who);
+        return PPENV_EINVAL;
+    }
+    const int32_t pw = kTileW / samples, ph = kTileH / samples;                                                       // pixels per workgroup
+    const int64_t tiles_x = (camera->width + pw - 1) / pw, tiles_y = (camera->height + ph - 1) / ph;
+    // grid limits: z at most 65535, x below 2^31, and fewer than 2^32 lanes in all
+    if (frames > 65535 || tiles_x * tiles_y * (int64_t)count * frames * kBlock >= ((int64_t)1 << 32)) {
+        pp_set_errorf("%s: %d frames of %d x %d pictures of %d envs with %d x %d samples exceed one launch's grid (65535 frames, 2^32 lanes): split the frames", who,
+                      frames, camera->width, camera->height, count, samples, samples);
+        return PPENV_EINVAL;
+    }
+    pp::RenderView view;
+    pp::render_view_of(*camera, view);
+    const dim3 grid((uint32_t)(tiles_x * tiles_y), (uint32_t)count, (uint32_t)frames);
+    uint32_t* out = reinterpret_cast<uint32_t*>(rgba);
+    const float4* anc = reinterpret_cast<const float4*>(anchor);
+    const hipStream_t st = (hipStream_t)stream;
+    if (samples == 1) hipLaunchKernelGGL(render_rays_frames_kernel<1>, grid, dim3(kBlock), 0, st, *scene, view, posed, anc, (int32_t)tiles_x, out);
+    else if (samples == 2) hipLaunchKernelGGL(render_rays_frames_kernel<2>, grid, dim3(kBlock), 0, st, *scene, view, posed, anc, (int32_t)tiles_x, out);
+    else hipLaunchKernelGGL(render_rays_frames_kernel<4>, grid, dim3(kBlock), 0, st, *scene, view, posed, anc, (int32_t)tiles_x, out);
+    return pp_launched("launching render_rays_frames_kernel failed");
 }

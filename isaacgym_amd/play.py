@@ -3,7 +3,7 @@
 
     Player(task, policy, games_num=2000).run()      games_num episodes of `task` under `policy` -> rl_games' numbers (average return,
                                                     average episode length) plus spread
-    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side]
+    python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side --capture-deferred --capture-trajectory out.npz]
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -264,6 +264,10 @@ def parse_args(argv=None):
     ap.add_argument("--capture-size", default="640x480", help="WIDTHxHEIGHT of one env's picture")
     ap.add_argument("--capture-fps", type=float, default=30.0)
     ap.add_argument("--capture-samples", type=int, default=1, choices=(1, 2, 4), help="rays per pixel and axis: 2 is 2 x 2 supersampling, 4 is 4 x 4")
+    ap.add_argument("--capture-deferred", action="store_true", help="record the posed primitives while playing and cast all rays in one batched launch at the "
+                    "end (render.Trajectory): the same file, byte for byte")
+    ap.add_argument("--capture-trajectory", default=None, metavar="FILE.npz", help="also save the recording as data (records deferred): "
+                    "python -m isaacgym_amd.render replay draws it again at any size, sample count and camera")
     ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
     return ap.parse_args(argv)
 
@@ -285,7 +289,8 @@ def make_renderer(task, args):
 def make_recorder(task, args):
     """The Recorder of the --capture* options."""
     from . import render
-    return render.Recorder(make_renderer(task, args), length=args.capture_len, every=args.capture_every)
+    deferred = bool(getattr(args, "capture_deferred", False) or getattr(args, "capture_trajectory", None))
+    return render.Recorder(make_renderer(task, args), length=args.capture_len, every=args.capture_every, deferred=deferred)
 
 
 def main(argv=None):
@@ -298,7 +303,7 @@ def main(argv=None):
         task_cfg = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})["task"]
     task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
-    recorder = make_recorder(task, args) if args.capture else None
+    recorder = make_recorder(task, args) if args.capture or args.capture_trajectory else None
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
                 max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes)
     last = dict(games=0, steps=0, reward=[0.0])
@@ -320,7 +325,9 @@ def main(argv=None):
     for a, p in enumerate(res["per_agent"]):
         print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
-    if recorder is not None:
+    if recorder is not None and args.capture_trajectory:
+        print(f"saved {recorder.trajectory.save(args.capture_trajectory, fps=args.capture_fps)} (trajectory)", flush=True)
+    if recorder is not None and args.capture:
         files = recorder.save(args.capture, fps=args.capture_fps)
         print(f"captured {res['captured_frames']} frames, kept the last {min(res['captured_frames'], recorder.length)}: {files[0]}" +
               (f" .. {files[-1]}" if len(files) > 1 else ""), flush=True)

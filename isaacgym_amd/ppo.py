@@ -801,6 +801,10 @@ def main(argv=None):
     ap.add_argument("--capture-every", type=int, default=1, help="control steps between two frames of a recording")
     ap.add_argument("--capture-fps", type=float, default=30.0)
     ap.add_argument("--capture-samples", type=int, default=2, choices=(1, 2, 4), help="rays per pixel and axis: 2 is 2 x 2 supersampling")
+    ap.add_argument("--capture-deferred", action="store_true", help="a drawn step records the posed primitives only; a recording's rays are cast in one batched "
+                    "launch when it ends (render.Trajectory): the same files, byte for byte")
+    ap.add_argument("--capture-trajectories", action="store_true", help="also write rl-video-step-<k>.traj.npz beside each video (records deferred): "
+                    "python -m isaacgym_amd.render replay draws it again at any size, sample count and camera")
     ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
     args = ap.parse_args(argv)
     if args.force_dist and not args.multi_gpu:
@@ -841,7 +845,7 @@ def main(argv=None):
         from . import play, render
         renderer = play.make_renderer(task, args)
         capture = render.TrainingCapture(renderer, os.path.join(out, "videos"), freq=args.capture_video_freq or 1464, length=args.capture_video_len or 100,
-                                         every=args.capture_every, fps=args.capture_fps)
+                                         every=args.capture_every, fps=args.capture_fps, deferred=args.capture_deferred, trajectories=args.capture_trajectories)
     done = fit(tr, out, args.task, print_every=args.print_every, capture=capture)
     if rank == 0:
         for path in done.get("videos", []):

@@ -7,6 +7,13 @@
                                      samples = 2 or 4: every pixel is the box mean of samples x samples rays (pp_render_rays_aa)
     Recorder(renderer, length=100, every=1).capture() / .save("out.gif")
     TrainingCapture(renderer, out_dir, freq=1464, length=100)     gym's RecordVideo rule inside a training rollout (PPOTrainer.set_capture)
+    Trajectory(renderer, length=100, every=1).capture() / .render(camera=, width=, height=, samples=) / .save("traj.npz")
+                                     deferred capture: a drawn step records the POSED primitives (80 bytes each) and the camera's anchor, one
+                                     small launch; all rays are cast later in one batched launch (pp_render_rays_frames), at any size, sample
+                                     count and camera.  Recorder(..., deferred=True) and TrainingCapture(..., deferred=True, trajectories=True)
+                                     record that way and hand out the bytes the eager recorder gives.
+    Replay.load("traj.npz").render(...) / .save("out.gif")       a saved trajectory drawn again: no task, no checkpoint
+    python -m isaacgym_amd.render replay traj.npz --out x.gif [--size WxH] [--samples 1|2|4] [--camera recorded|side|follow] [--fps]
 
 WHAT IS DRAWN is the project's own UNVERIFIED collision geometry (scene.py: the capsules and spheres the ball collides with, the paddle
 disc, the table slab, the net, the ball) plus a stick figure: one thin capsule ("bone") per parent-child pair of the G1 body tree
@@ -24,6 +31,7 @@ ball.  A collision shape hangs on a LINK index of the native model, mapped to it
 Out of scope: meshes, textures, mp4.
 """
 import ctypes as C
+import json
 import math
 import os
 
@@ -44,6 +52,11 @@ CHECKER_PITCH = 1.0
 COLORS = dict(bone=(0.78, 0.78, 0.82), shape=(0.25, 0.45, 0.85), shape2=(0.90, 0.55, 0.20), paddle=(0.80, 0.10, 0.10), table=(0.10, 0.35, 0.20),
               net=(0.92, 0.92, 0.92), ball=(1.00, 0.60, 0.10))
 MAX_RING_BYTES = 2 << 30
+POSED_WORDS = C.sizeof(RenderPosed) // 4    # 20
+TRAJECTORY_VERSION = 1                      # of the .npz a Trajectory saves
+# One pp_render_rays_frames launch casts at most this many rays (pixels x samples^2); cast_frames splits a recording into consecutive frame ranges.
+# 20 ms at the 5.6e9 rays / s the eager kernels reach on a full MI355X (27-dof scene, 49 primitives).
+MAX_LAUNCH_RAYS = 112_000_000
 
 
 def _ta_link_names():
@@ -360,9 +373,11 @@ def ring_schedule(calls, length, every):
 
 
 class Recorder:
-    """The last `length` rendered frames in a device ring [length, E, H, W, 4]; capture() once per control step renders every `every`-th call."""
+    """The last `length` rendered frames in a device ring [length, E, H, W, 4]; capture() once per control step renders every `every`-th call.
+    deferred=True: capture() records into a Trajectory (`.trajectory`; None when eager) instead of casting rays, and frames() / save() first
+    cast the frames not yet drawn, batched, into the same ring slots: what a caller reads is what the eager recorder gives, byte for byte."""
 
-    def __init__(self, renderer, length=100, every=1):
+    def __init__(self, renderer, length=100, every=1, deferred=False):
         import torch
         if int(length) < 1 or int(every) < 1:
             raise ValueError(f"Recorder: length {length} and every {every} must be positive")
@@ -373,15 +388,40 @@ class Recorder:
                              f"{MAX_RING_BYTES} (2 GiB): shorten it, pick fewer envs or a smaller picture")
         self.ring = torch.zeros((self.length,) + tuple(renderer.rgba.shape), dtype=torch.uint8, device=renderer.device)
         self.calls = self.captured = 0
+        self.trajectory = Trajectory(renderer, self.length, self.every) if deferred else None
+        self._drawn = 0                       # deferred: captured frames whose rays have been cast
+
+    def reset(self, base=0):
+        """Forget the frames: the next capture() is call 0 (a deferred recording numbers its steps from `base`)."""
+        self.calls = self.captured = self._drawn = 0
+        if self.trajectory is not None:
+            self.trajectory.reset(base)
 
     def capture(self):
+        if self.trajectory is not None:
+            self.trajectory.capture()
+            self.calls, self.captured = self.trajectory.calls, self.trajectory.captured
+            return
         if self.calls % self.every == 0:
             self.renderer.render(out=self.ring[self.captured % self.length])
             self.captured += 1
         self.calls += 1
 
+    def flush(self):
+        """Deferred: cast the rays of the captured frames not yet drawn into their ring slots (launches only; at most two slot ranges)."""
+        t = self.trajectory
+        if t is None or self._drawn == self.captured:
+            return
+        r = self.renderer
+        lo = max(self._drawn, self.captured - self.length)
+        a, b = lo % self.length, (self.captured - 1) % self.length + 1
+        for i, j in ([(a, b)] if a < b else [(a, self.length), (0, b)]):
+            cast_frames(r.L, r.scene.header, r._cam, t.posed[i:j], t.anchor[i:j], r.samples, self.ring[i:j])
+        self._drawn = self.captured
+
     def frames(self):
         """The kept frames, oldest first: [T, E, H, W, 4] on the device, T = min(captured, length)."""
+        self.flush()
         if self.captured <= self.length:
             return self.ring[:self.captured]
         at = self.captured % self.length
@@ -391,6 +431,205 @@ class Recorder:
         """The one host copy.  Envs side by side; *.gif (one file), *.png (numbered files <stem>_0000.png ...) through PIL, *.npy
         ([T, H, E * W, 3] uint8) without it.  -> the list of files written."""
         return save_frames(self.frames().cpu().numpy(), path, fps)
+
+
+def launch_frames(samples, envs, width, height):
+    """Frames one pp_render_rays_frames launch may take: at most MAX_LAUNCH_RAYS rays, 65535 frames (grid z) and fewer than 2^32 lanes; at least 1."""
+    pw = 16 // samples
+    lanes = -(-width // pw) * -(-height // pw) * envs * 256
+    return max(1, min(MAX_LAUNCH_RAYS // (envs * width * height * samples * samples), 65535, ((1 << 32) - 1) // lanes))
+
+
+def cast_frames(L, header, cam, posed, anchor, samples, out):
+    """posed [T, E, P, 20] words + anchor [T, E, 4] -> out [T, E, H, W, 4] (H, W: cam's), all contiguous on one device: pp_render_rays_frames over
+    consecutive frame ranges of launch_frames() frames.  Host integers and launches only."""
+    T, E = int(posed.shape[0]), int(posed.shape[1])
+    if tuple(out.shape) != (T, E, cam.height, cam.width, 4) or tuple(anchor.shape) != (T, E, 4) or not (posed.is_contiguous() and anchor.is_contiguous() and out.is_contiguous()):
+        raise ValueError(f"cast_frames: posed {tuple(posed.shape)}, anchor {tuple(anchor.shape)} and out {tuple(out.shape)} do not belong together")
+    s = _lib.stream(out.device)
+    step = launch_frames(samples, E, cam.width, cam.height)
+    for lo in range(0, T, step):
+        n = min(step, T - lo)
+        _lib.check(L.pp_render_rays_frames(C.byref(header), C.byref(cam), posed[lo].data_ptr(), anchor[lo].data_ptr(), n, E, samples, out[lo].data_ptr(), s), L)
+    return out
+
+
+def _frames_out(who, T, E, width, height, device):
+    import torch
+    nbytes = T * E * height * width * 4
+    if nbytes > MAX_RING_BYTES:
+        raise ValueError(f"{who}: {T} frames of {(E, height, width, 4)} are {nbytes} bytes, more than "
+                         f"{MAX_RING_BYTES} (2 GiB): shorten it, pick fewer envs or a smaller picture")
+    return torch.zeros((T, E, height, width, 4), dtype=torch.uint8, device=device)
+
+
+def _samples_ok(who, samples):
+    if samples not in (1, 2, 4):
+        raise ValueError(f"{who}: samples (sub-samples per axis) must be 1, 2 or 4, got {samples!r}")
+    return int(samples)
+
+
+class Trajectory:
+    """The posed primitives of the last `length` drawn control steps: a device ring posed [length, E, P, 20] (raw 32-bit words of
+    pp_render_posed), anchor [length, E, 4] (x, y, z, 0 of the body a following camera follows) and, on the host, the control-step index of
+    every slot.  capture() has Recorder's call arithmetic (ring_schedule); a drawn call is scene.refresh() + pp_render_pose_anchor.
+    The anchor is the renderer camera's follow body when it has one, else the first humanoid's root (SRC_ROOT, 0)."""
+
+    def __init__(self, renderer, length=100, every=1):
+        import torch
+        if int(length) < 1 or int(every) < 1:
+            raise ValueError(f"Trajectory: length {length} and every {every} must be positive")
+        self.renderer, self.length, self.every = renderer, int(length), int(every)
+        E, P = len(renderer.envs), max(len(renderer.scene.prims), 1)
+        self.posed = torch.zeros((self.length, E, P, POSED_WORDS), dtype=torch.int32, device=renderer.device)
+        self.anchor = torch.zeros((self.length, E, 4), dtype=torch.float32, device=renderer.device)
+        self.steps = [0] * self.length
+        self.calls = self.captured = self.base = 0
+
+    def reset(self, base=0):
+        self.calls = self.captured = 0
+        self.base = int(base)
+
+    def capture(self):
+        if self.calls % self.every == 0:
+            r = self.renderer
+            sc, slot = r.scene, self.captured % self.length
+            src, row = r.camera.follow if r.camera.follow is not None else (SRC_ROOT, 0)
+            sc.refresh()
+            _lib.check(r.L.pp_render_pose_anchor(C.byref(sc.header), sc.prims_dev.data_ptr(), r.env_ids.data_ptr(), len(r.envs), src, row,
+                                                 self.posed[slot].data_ptr(), self.anchor[slot].data_ptr(), _lib.stream(r.device)), r.L)
+            self.steps[slot] = self.base + self.calls
+            self.captured += 1
+        self.calls += 1
+
+    def frames(self):
+        """The kept slots, oldest first: (posed [T, E, P, 20], anchor [T, E, 4], [control-step index] * T), T = min(captured, length)."""
+        if self.captured <= self.length:
+            return self.posed[:self.captured], self.anchor[:self.captured], self.steps[:self.captured]
+        at = self.captured % self.length
+        if not at:
+            return self.posed, self.anchor, list(self.steps)
+        return self.posed.roll(-at, 0), self.anchor.roll(-at, 0), self.steps[at:] + self.steps[:at]
+
+    def render(self, camera=None, width=None, height=None, samples=None):
+        """The kept frames as pictures: uint8 [T, E, H, W, 4] on the device.  The defaults are the renderer's own camera, size and sample
+        count: then frame t is byte for byte what Renderer.render() drew (or would have drawn) at that step.  Launches only."""
+        r = self.renderer
+        camera = r.camera if camera is None else camera
+        width, height = int(r.width if width is None else width), int(r.height if height is None else height)
+        samples = _samples_ok("Trajectory.render", r.samples if samples is None else samples)
+        if width < 1 or height < 1:
+            raise ValueError(f"Trajectory.render: width x height must be positive, got {width} x {height}")
+        posed, anchor, _ = self.frames()
+        out = _frames_out("Trajectory.render", int(posed.shape[0]), len(r.envs), width, height, r.device)
+        if posed.shape[0]:
+            cast_frames(r.L, r.scene.header, camera.struct(width, height), posed.contiguous(), anchor.contiguous(), samples, out)
+        return out
+
+    def constants(self, fps=30):
+        """What a file holds besides the frames (host data): the scene header's constants, the recording camera, the side view, the JSON."""
+        r = self.renderer
+        sc, cam, side = r.scene, r.camera, Camera.side_view(r.scene)
+        f32 = lambda v: np.asarray(v, np.float32)       # noqa: E731
+        meta = dict(version=TRAJECTORY_VERSION, task=sc.task_name, every=self.every, fps=float(fps), posed_words=POSED_WORDS, num_prims=len(sc.prims))
+        return dict(env_ids=np.asarray(r.envs, np.int32), ground_z=f32(sc.ground_z), checker=np.asarray(int(sc.checker), np.int32),
+                    checker_pitch=f32(sc.checker_pitch), ground_rgb=f32(sc.ground_rgb), sky_rgb=f32(sc.sky_rgb), light=f32(sc.light), ambient=f32(sc.ambient),
+                    diffuse=f32(sc.diffuse), camera_pose=np.stack([cam.eye, cam.target, cam.up]), camera_fov=np.asarray(cam.fov_deg, np.float64),
+                    camera_follow=np.asarray(int(cam.follow is not None), np.int32), camera_size=np.asarray([r.width, r.height, r.samples], np.int32),
+                    side_pose=np.stack([side.eye, side.target, side.up]), side_fov=np.asarray(side.fov_deg, np.float64), meta=np.asarray(json.dumps(meta)))
+
+    def save(self, path, fps=30):
+        """One .npz, data only (write_trajectory): the one host copy.  -> path."""
+        posed, anchor, steps = self.frames()
+        return write_trajectory(path, posed.cpu().numpy(), anchor.cpu().numpy(), steps, self.constants(fps))
+
+
+def write_trajectory(path, posed, anchor, steps, constants):
+    """posed: int32 / uint32 [T, E, P, 20] on the host — stored as uint32 WORDS (the kind word is an integer: bits are kept, not values)."""
+    posed = np.ascontiguousarray(posed)
+    with open(path, "wb") as fh:
+        np.savez(fh, posed=posed.view(np.uint32), anchor=np.asarray(anchor, np.float32), steps=np.asarray(steps, np.int64), **constants)
+    return path
+
+
+TRAJECTORY_KEYS = ("posed", "anchor", "steps", "env_ids", "ground_z", "checker", "checker_pitch", "ground_rgb", "sky_rgb", "light", "ambient", "diffuse",
+                   "camera_pose", "camera_fov", "camera_follow", "camera_size", "side_pose", "side_fov", "meta")
+
+
+def read_trajectory(path):
+    """-> {key: array} of a file write_trajectory wrote, `meta` parsed.  A file that does not fit is refused by name."""
+    with np.load(path, allow_pickle=False) as z:
+        missing = [k for k in TRAJECTORY_KEYS if k not in z.files]
+        if missing:
+            raise ValueError(f"{path}: not a trajectory file: {', '.join(missing)} missing")
+        d = {k: z[k] for k in TRAJECTORY_KEYS}
+    meta = d["meta"] = json.loads(str(d["meta"]))
+    if meta.get("version") != TRAJECTORY_VERSION:
+        raise ValueError(f"{path}: trajectory format version {meta.get('version')!r}; this build reads version {TRAJECTORY_VERSION}")
+    posed = d["posed"]
+    if posed.dtype != np.uint32 or posed.ndim != 4 or posed.shape[3] != POSED_WORDS or meta.get("posed_words") != POSED_WORDS:
+        raise ValueError(f"{path}: {posed.shape[-1] if posed.ndim else 0} words per primitive (the file says {meta.get('posed_words')!r}); "
+                         f"pp_render_posed has {POSED_WORDS}")
+    num_prims = meta.get("num_prims")
+    if not isinstance(num_prims, int) or not 0 <= num_prims <= RENDER_MAX_PRIMS or posed.shape[2] != max(num_prims, 1):
+        raise ValueError(f"{path}: primitive count: the file says {meta.get('num_prims')!r}, its frames hold {posed.shape[2]}; the ray caster takes "
+                         f"at most {RENDER_MAX_PRIMS}")
+    T, E = posed.shape[:2]
+    if not 1 <= E <= RENDER_MAX_ENVS or d["anchor"].shape != (T, E, 4) or d["steps"].shape != (T,) or d["env_ids"].shape != (E,):
+        raise ValueError(f"{path}: {E} envs (1 .. {RENDER_MAX_ENVS}), or anchor, steps and env_ids do not match posed {posed.shape}")
+    return d
+
+
+class Replay:
+    """A saved trajectory, drawn again without a task or a checkpoint: the arrays on `device`, the scene header rebuilt from the file's constants
+    with no pose source.  A following camera (Camera(..., follow=...), any body) follows the RECORDED anchor."""
+
+    def __init__(self, data, device="cuda:0", path=None):
+        import torch
+        self.data, self.meta, self.path, self.device = data, data["meta"], path, torch.device(device)
+        self.posed = torch.from_numpy(np.ascontiguousarray(data["posed"]).view(np.int32)).to(self.device)
+        self.anchor = torch.from_numpy(np.ascontiguousarray(data["anchor"], np.float32)).to(self.device)
+        self.steps, self.envs = [int(k) for k in data["steps"]], [int(e) for e in data["env_ids"]]
+        self.width, self.height, self.samples = (int(v) for v in data["camera_size"])
+        self.fps = float(self.meta.get("fps", 30))
+        h = self.header = RenderScene()
+        h.num_envs, h.num_prims, h.num_sources, h.checker = max(self.envs) + 1, int(self.meta["num_prims"]), 0, int(data["checker"])
+        h.ground_z, h.checker_pitch = float(data["ground_z"]), float(data["checker_pitch"])
+        for k in range(2):
+            h.ground_rgb[k][:] = [float(v) for v in data["ground_rgb"][k]]
+        h.sky_rgb[:], h.light[:] = [float(v) for v in data["sky_rgb"]], [float(v) for v in data["light"]]
+        h.ambient, h.diffuse = float(data["ambient"]), float(data["diffuse"])
+
+    @classmethod
+    def load(cls, path, device="cuda:0"):
+        return cls(read_trajectory(path), device, path)
+
+    def camera(self, name="recorded"):
+        """recorded: the recording's own; side: Camera.side_view as the file keeps it; follow: the follow-cam on the recorded anchor."""
+        d = self.data
+        if name == "recorded":
+            return Camera(*d["camera_pose"], fov_deg=float(d["camera_fov"]), follow=(SRC_ROOT, 0) if int(d["camera_follow"]) else None)
+        if name == "side":
+            return Camera(*d["side_pose"], fov_deg=float(d["side_fov"]))
+        if name == "follow":
+            return Camera.follow_root(None)
+        raise ValueError(f"Replay.camera: {name!r} is not recorded, side or follow")
+
+    def render(self, camera=None, width=None, height=None, samples=None):
+        """uint8 [T, E, H, W, 4] on the device; the defaults are the recording's camera, size and sample count."""
+        camera = self.camera() if camera is None else camera
+        width, height = int(self.width if width is None else width), int(self.height if height is None else height)
+        samples = _samples_ok("Replay.render", self.samples if samples is None else samples)
+        if width < 1 or height < 1:
+            raise ValueError(f"Replay.render: width x height must be positive, got {width} x {height}")
+        out = _frames_out("Replay.render", int(self.posed.shape[0]), len(self.envs), width, height, self.device)
+        if self.posed.shape[0]:
+            cast_frames(_lib.lib(), self.header, camera.struct(width, height), self.posed, self.anchor, samples, out)
+        return out
+
+    def save(self, out, fps=None, **kw):
+        """render(**kw) through save_frames -> the files written."""
+        return save_frames(self.render(**kw).cpu().numpy(), out, self.fps if fps is None else fps)
 
 
 class TrainingCapture:
@@ -405,9 +644,13 @@ class TrainingCapture:
     (save_frames), and returns the files finished so far; close() writes an open recording short, waits for the copies and the writer.
     The copy is ordered on the stream before any later render, so a later recording cannot overwrite frames in flight.  The pinned buffer
     allocated here serves every recording as long as each is written out before the next one ends (freq >> length: always); one more is
-    allocated only when a recording ends while the writer still holds every buffer."""
+    allocated only when a recording ends while the writer still holds every buffer.
+    deferred=True: a drawn step records into the recorder's Trajectory (refresh + one pose launch); when the recording ends the batched ray
+    launch is enqueued ahead of the pinned copy — stream order keeps every guarantee above, and the files hold the same bytes.
+    trajectories=True (records deferred as well): each video gets rl-video-step-<k>.traj.npz beside it, a second non_blocking copy of the posed
+    words and anchors, written by the same writer thread (Replay.load draws it again at any size and camera)."""
 
-    def __init__(self, renderer, out_dir, freq=1464, length=100, every=1, fps=30, ext=".gif", start_step=0):
+    def __init__(self, renderer, out_dir, freq=1464, length=100, every=1, fps=30, ext=".gif", start_step=0, deferred=False, trajectories=False):
         for name, v in (("freq", freq), ("length", length), ("every", every)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"TrainingCapture: {name} {v!r} is not a positive integer")
@@ -422,7 +665,9 @@ class TrainingCapture:
                 raise RuntimeError(f"writing {ext} needs PIL, which is not installed; pass ext='.npy' instead") from e
         self.renderer, self.out_dir, self.fps, self.ext = renderer, out_dir, fps, ext
         self.freq, self.length, self.every = int(freq), int(length), int(every)
-        self.recorder = Recorder(renderer, length=-(-self.length // self.every), every=self.every)     # one recording never wraps the ring
+        self.deferred, self.trajectories = bool(deferred or trajectories), bool(trajectories)
+        self.recorder = Recorder(renderer, length=-(-self.length // self.every), every=self.every, deferred=self.deferred)     # one recording never wraps the ring
+        self._traj_host, self._constants = {}, None     # trajectories: id(frame buffer) -> its pinned (posed, anchor); the files' constants
         self._k = int(start_step)
         self._open_at = None                  # k of the step that opened the recording in progress
         self._free = [self._host_buffer()]
@@ -449,7 +694,13 @@ class TrainingCapture:
 
     def _host_buffer(self):
         import torch
-        return torch.zeros(tuple(self.recorder.ring.shape), dtype=torch.uint8, pin_memory=self.renderer.device.type == "cuda")
+        pin = self.renderer.device.type == "cuda"
+        host = torch.zeros(tuple(self.recorder.ring.shape), dtype=torch.uint8, pin_memory=pin)
+        if self.trajectories:
+            t = self.recorder.trajectory
+            self._traj_host[id(host)] = (torch.zeros(tuple(t.posed.shape), dtype=t.posed.dtype, pin_memory=pin),
+                                         torch.zeros(tuple(t.anchor.shape), dtype=t.anchor.dtype, pin_memory=pin))
+        return host
 
     def on_step(self):
         """After a control step.  Host integers and launches only."""
@@ -460,7 +711,7 @@ class TrainingCapture:
             if k % self.freq:
                 return
             self._open_at = k
-            rec.calls = rec.captured = 0
+            rec.reset(base=k)
         rec.capture()
         if rec.calls == self.length:
             self._finish()
@@ -471,12 +722,21 @@ class TrainingCapture:
         rec, dev = self.recorder, self.renderer.device
         n = rec.captured
         host = self._free.pop() if self._free else self._host_buffer()
+        rec.flush()                           # deferred: the batched ray launch, ahead of the copy on the stream
         host[:n].copy_(rec.ring[:n], non_blocking=True)
+        traj = None
+        if self.trajectories:
+            t, (posed, anchor) = rec.trajectory, self._traj_host[id(host)]
+            posed[:n].copy_(t.posed[:n], non_blocking=True)
+            anchor[:n].copy_(t.anchor[:n], non_blocking=True)
+            if self._constants is None:
+                self._constants = t.constants(self.fps)
+            traj = (os.path.join(self.out_dir, f"rl-video-step-{self._open_at}.traj.npz"), posed, anchor, t.steps[:n])
         event = None
         if dev.type == "cuda":
             event = torch.cuda.Event()
             event.record(torch.cuda.current_stream(dev))
-        self._in_flight.append((event, os.path.join(self.out_dir, f"rl-video-step-{self._open_at}{self.ext}"), host, n))
+        self._in_flight.append((event, os.path.join(self.out_dir, f"rl-video-step-{self._open_at}{self.ext}"), host, n, traj))
         self._open_at = None
 
     def _reclaim(self):
@@ -494,9 +754,12 @@ class TrainingCapture:
             job = self._queue.get()
             if job is None:
                 return
-            path, host, n = job
+            path, host, n, traj = job
             try:
-                self._written.append((save_frames(host[:n].numpy(), path, self.fps), host))
+                files = save_frames(host[:n].numpy(), path, self.fps)
+                if traj is not None:
+                    files = files + [write_trajectory(traj[0], traj[1][:n].numpy(), traj[2][:n].numpy(), traj[3], self._constants)]
+                self._written.append((files, host))
             except Exception as e:      # noqa: BLE001  (raised on the main thread by the next poll() / close())
                 self._errors.append(e)
                 self._written.append(([], host))
@@ -505,14 +768,14 @@ class TrainingCapture:
         import queue
         import threading
         while self._in_flight and (wait or self._in_flight[0][0] is None or self._in_flight[0][0].query()):
-            event, path, host, n = self._in_flight.pop(0)
+            event, path, host, n, traj = self._in_flight.pop(0)
             if wait and event is not None:
                 event.synchronize()
             if self._thread is None:
                 self._queue = queue.Queue()
                 self._thread = threading.Thread(target=self._write_loop, name="TrainingCapture writer", daemon=True)
                 self._thread.start()
-            self._queue.put((path, host, n))
+            self._queue.put((path, host, n, traj))
 
     def poll(self):
         """-> the files written so far.  Does not wait: neither for a copy nor for the writer."""
@@ -561,3 +824,34 @@ def save_frames(frames, path, fps=30):
     for im, name in zip(images, names):
         im.save(name)
     return names
+
+
+# ---- CLI --------------------------------------------------------------------------------------------------------------------------
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.render", description="draw a saved pose trajectory again (no task, no checkpoint)")
+    sub = ap.add_subparsers(dest="command", required=True)
+    rp = sub.add_parser("replay", help="cast the rays of a trajectory file (Trajectory.save, --capture-trajectory, --capture-trajectories)")
+    rp.add_argument("trajectory", help="the .npz file")
+    rp.add_argument("--out", required=True, metavar="FILE", help=".gif, .png (numbered files) or .npy")
+    rp.add_argument("--size", default=None, help="WIDTHxHEIGHT of one env's picture (default: as recorded)")
+    rp.add_argument("--samples", type=int, default=None, choices=(1, 2, 4), help="rays per pixel and axis (default: as recorded)")
+    rp.add_argument("--camera", choices=("recorded", "side", "follow"), default="recorded", help="side: the table and humanoid(s), as the file keeps it; "
+                    "follow: the follow-cam on the recorded anchor")
+    rp.add_argument("--fps", type=float, default=None, help="default: as recorded")
+    rp.add_argument("--device", default="cuda:0")
+    args = ap.parse_args(argv)
+    width = height = None
+    if args.size:
+        try:
+            width, height = (int(v) for v in args.size.lower().split("x"))
+        except ValueError as e:
+            raise SystemExit(f"--size is WIDTHxHEIGHT: {e}")
+    rep = Replay.load(args.trajectory, args.device)
+    files = rep.save(args.out, fps=args.fps, camera=rep.camera(args.camera), width=width, height=height, samples=args.samples)
+    print(f"replayed {len(rep.steps)} frames of {rep.meta['task']}, envs {rep.envs}: {files[0]}" + (f" .. {files[-1]}" if len(files) > 1 else ""), flush=True)
+    return files
+
+
+if __name__ == "__main__":
+    main()

@@ -16,7 +16,7 @@ Run on the GPU box:  python tools/ppo_epoch_bench.py [--learner native|torch|ppo
 --learner ppo --outcomes: the same epochs with the outcome counts on (PPOTrainer(outcomes=True)); the struct is printed with the result.
 --learner ppo --capture: the same epochs with a render.TrainingCapture on the rollout (env 0 at 320 x 240, --capture-samples rays per axis, recordings of
 100 steps back to back, so one is open in every timed epoch and one finishes every 100 steps); reports every epoch's rollout time, what poll() cost after
-it, and what close() waited for at the end (the last copy and the writer).
+it, and what close() waited for at the end (the last copy and the writer).  --capture-deferred: TrainingCapture(deferred=True).
 Data-parallel (every learner, --learner ppo included: PPOTrainer with its gradient all-reduce and the mean inside the Adam kernel): under
 `python -m torch.distributed.run --nproc_per_node=N`, or with --force-dist for one rank on RCCL; --dist-backend gloo lets ranks share a GPU."""
 import argparse
@@ -42,6 +42,7 @@ ap.add_argument("--epochs", type=int, default=3)
 ap.add_argument("--capture", action="store_true", help="--learner ppo: record the rollout (render.TrainingCapture), to measure what it costs")
 ap.add_argument("--capture-samples", type=int, default=2, choices=(1, 2, 4))
 ap.add_argument("--capture-ext", default=".npy", choices=(".npy", ".gif"))
+ap.add_argument("--capture-deferred", action="store_true", help="--capture: record posed primitives per step, cast a recording's rays in one batched launch (render.Trajectory)")
 ap.add_argument("--outcomes", action="store_true", help="--learner ppo: PPOTrainer(outcomes=True), the 27-dof task's outcome counts summed by the step kernel's clear")
 ap.add_argument("--force-dist", action="store_true", help="create the nccl group and all-reduce the gradients even with ONE rank (the RCCL path on a one-GPU box)")
 ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="gloo: ranks may share cuda:LOCAL_RANK %% device_count (rehearsal on one GPU)")
@@ -89,9 +90,9 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
         import tempfile  # noqa: E402
         from isaacgym_amd import render  # noqa: E402
         cap = render.TrainingCapture(render.Renderer(tr.task, envs=[0], width=320, height=240, samples=args.capture_samples),
-                                     tempfile.mkdtemp(prefix="ppo_epoch_bench_"), freq=100, length=100, ext=args.capture_ext)
+                                     tempfile.mkdtemp(prefix="ppo_epoch_bench_"), freq=100, length=100, ext=args.capture_ext, deferred=args.capture_deferred)
         tr.set_capture(cap)
-        tr.col.on_step()                                                   # warm-up of the two render launches; the recording starts at step 0 anyway
+        tr.col.on_step()                                                   # warm-up of the render launches (close() casts a deferred frame); the recording starts at step 0 anyway
         cap.close()
         cap.paths.clear()
         cap.start_step = 0
@@ -121,7 +122,7 @@ if args.learner == "ppo":          # the library trainer: the same epoch, its ta
     if cap is not None:
         t0 = time.perf_counter()
         videos = cap.close()
-        extra.update(capture=f"env 0, 320 x 240, {args.capture_samples} x {args.capture_samples} rays, 100 steps per recording, {args.capture_ext}",
+        extra.update(capture=f"env 0, 320 x 240, {args.capture_samples} x {args.capture_samples} rays, 100 steps per recording, {args.capture_ext}" + (", deferred" if args.capture_deferred else ""),
                      ms_poll_each_epoch=poll_each, ms_close=(time.perf_counter() - t0) * 1e3, videos=len(videos))
     if rank == 0:
       print(json.dumps({**extra,
