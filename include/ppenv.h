@@ -128,7 +128,7 @@ typedef struct ppenv_config {
     int32_t variant;          /* PPENV_VARIANT_* */
     int32_t num_envs;         /* envs owned by this handle (local shard) */
     int32_t env_id_offset;    /* global id of local env 0 (multi-GPU shard; keys the RNG) */
-    uint64_t seed;
+    uint64_t seed;            /* keys the RNG AS GIVEN: see "What a seed means here" at ppenv_randomization below */
     int32_t device_id;
 
     /* simulation (yaml sim: block) */
@@ -294,7 +294,14 @@ int ppenv_serve_from_draws(struct ppenv* env, const float* draws_dev, int32_t m,
  *   action_noise_sigma / observation_noise_sigma    additive Gaussian white noise on the raw actions (before the clipActions clamp) and on
  *                                                   every observation value (yaml:106-113), drawn from the counter RNG keyed by
  *                                                   (seed, global env id, episode, progress, index) — identical in kernel and oracle
- * Gravity (sim_params.gravity, yaml:114-120) is one value for the whole simulation, as upstream: ppenv_set_gravity. */
+ * Gravity (sim_params.gravity, yaml:114-120) is one value for the whole simulation, as upstream: ppenv_set_gravity.
+ *
+ * What a seed means here.  Every seed of this ABI — ppenv_config.seed, ppenv_ta_params.seed, ppenv_dr_plan.seed, the seed of
+ * ppenv_mlp_sample_actions / ppenv_mlp_heads_sample — keys the counter RNG as given, and the RNG XORs its low word into the env id before
+ * any mixing: env g under seed s has the stream of env g ^ s ^ s' under seed s'.  These are therefore STREAM seeds, which a caller derives
+ * from a user's seed as mix64(seed ^ salt) with one salt per family of draws (mix64 = the SplitMix64 finaliser; isaacgym_amd/scene.py
+ * stream_seed and STREAM_ENV / STREAM_TABLES / STREAM_SAMPLER, which the task classes, the trainer and the player apply).  Handing a user's
+ * seed, seed + 1 or seed + rank straight to two handles makes them draw the same numbers, permuted over envs. */
 typedef struct ppenv_randomization {
     const float* dof_stiffness_scale;   /* [7][N] or NULL */
     const float* dof_damping_scale;     /* [7][N] or NULL */
@@ -502,7 +509,7 @@ const char* ppenv_ta_sim_kernel_name(const ppenv_ta_sim* sim);
  * 7-dof yamls; TA's apply_randomizations call sits in its reset path as TT:849-850's does): per-env tables in device memory, SoA, NULL = not
  * randomised — drive stiffness / damping scales [27][N], link mass scales [28][N] (link 0 = pelvis; mass and inertia together), restitution and
  * friction scales [N] of the humanoid's shapes and the paddle; additive Gaussian noise on the raw actions (before the clipActions clamp) and on every
- * observation value, drawn from the counter RNG keyed by (params.seed, global env id, episode, progress at the step's start, index).  The tables are read
+ * observation value, drawn from the counter RNG keyed by (params.seed as given — a stream seed, see ppenv_randomization —, global env id, episode, progress at the step's start, index).  The tables are read
  * by every following ppenv_ta_step (the caller keeps them alive); dr NULL switches the randomisation off.  Only with ppenv_ta_sim_kernel() == 2 (the
  * chain-wave kernel: the scales multiply its compiled-in literals). */
 typedef struct ppenv_ta_randomization {

@@ -60,7 +60,7 @@ typedef struct ppenv_dr_entry {
 typedef struct ppenv_dr_plan {
     int32_t num_envs;
     int32_t env_id_offset;     /* global id of env 0 (ppenv_config.env_id_offset) */
-    uint64_t seed;
+    uint64_t seed;             /* keys the draws as given: a stream seed (ppenv.h "What a seed means here"; the tasks pass the tables' own) */
     int32_t frequency;         /* >= 1: control steps an env must have run since its last redraw before a reset redraws it */
     int32_t reset_rows;        /* rows of reset_buf per env: 1; 2 for the 4-actor variant, whose two agent rows reset together (row 2 e is read) */
     int32_t num_tables;        /* 1 .. PPENV_DR_MAX_TABLES */

@@ -77,7 +77,9 @@ int ppenv_mlp_prepare_input(const float* obs, int32_t m, int32_t k, int32_t ld_o
  *   raw = mu[i, j] + sigma[j] * g,  g = the counter RNG's standard normal at (seed, counter, i, j)   (ppenv_device.h dr_gauss)
  *   actions[i, j] = clamp(raw, lo, hi)            (lo >= hi: no clamp)        [m, a] contiguous
  *   neglogp[i]    = sum_j (0.5 g^2 + log sigma[j]) + 0.5 a log(2 pi)          (NULL: not wanted)
- * The same (seed, counter) gives the same draws; the caller advances `counter` every step.  a <= 256. */
+ * The same (seed, counter) gives the same draws; the caller advances `counter` every step.  a <= 256.
+ * `seed` keys the draws as given and is the env noise's family: pass a stream seed of the sampler's own (ppenv.h "What a seed means here";
+ * scene.stream_seed(seed, STREAM_SAMPLER), as PPOTrainer and RLGamesPolicy.act do), not the seed of the task. */
 int ppenv_mlp_sample_actions(const float* mu, int32_t m, int32_t a, int32_t ld_mu, const float* sigma, uint64_t seed, uint64_t counter,
                              float lo, float hi, float* actions, float* neglogp, void* stream);
 

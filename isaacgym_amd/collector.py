@@ -35,7 +35,9 @@ def gae(rewards, values, dones, gamma=0.99, tau=0.95, reward_scale=1.0, advantag
 
 class RolloutCollector:
     """`collect()` plays `horizon` steps of env + policy and leaves the horizon in `obs [H+1, N, num_obs]`, `actions [H, N, A]`,
-    `neglogp [H, N]`, `mu [H+1, N, A]`, `values [H+1, N]`, `rewards [H, N]`, `dones [H, N]`, `advantages`, `returns [H, N]`."""
+    `neglogp [H, N]`, `mu [H+1, N, A]`, `values [H+1, N]`, `rewards [H, N]`, `dones [H, N]`, `advantages`, `returns [H, N]`.
+    `seed` goes to the sampling launch as given (policy.sample_actions): with the env's own seed the exploration draw of step t would be
+    the env's action noise of step t + 1 for the same row and action.  Pass policy.sampler_stream_seed(user seed), as PPOTrainer does."""
 
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0):
         self.env, self.net, self.h = env, net, int(horizon)

@@ -18,15 +18,24 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, scene
 from ._lib import MLPCast, MLPDw, MLPLayer     # the ctypes mirrors of include/ppenv_policy.h (bound in _lib.load)
 
 UNITS = [2048, 1536, 1024, 1024, 512, 512]     # cfg/train/HumanoidPingpongTiltG1PPO.yaml:29
 
 
+def sampler_stream_seed(seed):
+    """The seed the sampling launches below are given for a USER seed: its sampler stream (scene.stream_seed).  PPOTrainer and
+    RLGamesPolicy.act go through here; whoever calls sample_actions / heads_sample / NativeMLP.forward(sample=...) / RolloutCollector
+    with a seed of their own should too."""
+    return scene.stream_seed(seed, scene.STREAM_SAMPLER)
+
+
 def sample_actions(actions, mu, sigma, seed, counter, lo=-1.0, hi=1.0, neglogp=None):
     """ppenv_mlp_sample_actions on torch tensors: actions [M, A] = clamp(mu + sigma * N(0, 1), lo, hi), neglogp [M] of the unclamped
-    draw (rl_games a2c_continuous with fixed sigma); deterministic in (seed, counter)."""
+    draw (rl_games a2c_continuous with fixed sigma); deterministic in (seed, counter).  `seed` keys the counter RNG AS GIVEN, in the
+    family of an env's step noise: row i's draw at counter c is env i's noise at (episode 0, progress c) under the same seed, and seeds
+    s and s' give the same rows permuted (i ^ s ^ s').  Pass sampler_stream_seed(user seed), not a user's or a task's seed."""
     L = _lib.lib()
     assert actions.is_contiguous() and mu.stride(1) == 1 and sigma.is_contiguous()
     _lib.check(L.ppenv_mlp_sample_actions(mu.data_ptr(), mu.shape[0], mu.shape[1], mu.stride(0), sigma.data_ptr(), seed, counter, lo, hi,
@@ -86,7 +95,8 @@ def chain_status(workspace):
 
 def heads_sample(out, x, w, bias, num_actions, actions, sigma, seed, counter, lo=-1.0, hi=1.0, neglogp=None):
     """ppenv_mlp_heads_sample: the heads layer out [M, n <= 32] (fp32) = x . w^T + bias and, in the same launch, what
-    sample_actions(actions, out[:, :num_actions], sigma, seed, counter, lo, hi, neglogp) would produce."""
+    sample_actions(actions, out[:, :num_actions], sigma, seed, counter, lo, hi, neglogp) would produce (`seed` as there: a stream seed,
+    taken as given)."""
     d = _descriptor(out, x, w, bias, False)
     assert actions.is_contiguous() and actions.shape[1] == num_actions and sigma.is_contiguous()
     _lib.check(_lib.lib().ppenv_mlp_heads_sample(C.byref(d), num_actions, sigma.data_ptr(), seed, counter, lo, hi, actions.data_ptr(),
@@ -680,7 +690,8 @@ class RLGamesPolicy:
         return cls(ckpt["model"] if "model" in ckpt else ckpt, device, max_rows=max_rows)
 
     def act(self, obs, deterministic=True, seed=0):
-        """obs [M, num_obs] fp32 on the device -> (actions [M, A] in [-1, 1], value [M, 1] de-normalised)."""
+        """obs [M, num_obs] fp32 on the device -> (actions [M, A] in [-1, 1], value [M, 1] de-normalised).  seed: the user's; the draws are
+        keyed by its sampler stream (sampler_stream_seed), never by the seed itself — the task played with the same seed shares no draw with it."""
         m = obs.shape[0]
         if self._actions is None or self._actions.shape[0] != m:
             self._actions = torch.empty(m, self.net.num_actions, device=self.device)
@@ -690,5 +701,6 @@ class RLGamesPolicy:
             torch.clamp(mu, -1.0, 1.0, out=self._actions)
         else:                                                  # the heads launch draws the actions as well
             self._counter += 1
-            mu, v = self.net.forward(obs, sample=dict(actions=self._actions, sigma=self.sigma, seed=seed, counter=self._counter, neglogp=self._neglogp))
+            mu, v = self.net.forward(obs, sample=dict(actions=self._actions, sigma=self.sigma, seed=sampler_stream_seed(seed), counter=self._counter,
+                                                         neglogp=self._neglogp))
         return self._actions, v * self.value_std + self.value_mean

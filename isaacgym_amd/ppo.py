@@ -67,7 +67,7 @@ from . import _lib
 from . import distributed as D
 from ._lib import PPOAdam, PPOLossArgs, PPOMeter, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h and ppenv_ppo_meter.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
-from .policy import UNITS, NativeActorCritic, RunningMeanStd
+from .policy import UNITS, NativeActorCritic, RunningMeanStd, sampler_stream_seed
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 STATS = ("loss", "a_loss", "c_loss", "b_loss", "entropy", "kl", "clip_frac")     # ppenv_ppo_loss_grad's stats[] (include/ppenv_ppo.h)
@@ -437,7 +437,7 @@ class PPOTrainer:
         self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
         H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
-                                    sigma=torch.exp(self.logstd), seed=self.seed)
+                                    sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed))   # ranks under seed + r share no exploration noise, and none is the env's noise
         self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,

@@ -959,6 +959,19 @@ def _mix64(z):
     return z
 
 
+# What a user's `seed` becomes before a kernel is keyed by it.  The native entries (ppenv_config.seed, ppenv_ta_params.seed, ppenv_dr_plan.seed, the
+# sampler's seed) take STREAM seeds: the counter RNG XORs the low word of its seed into the env id before any mixing, so keyed by raw user seeds
+# env g of seed s has the stream of env g ^ s ^ s' of seed s'.  Whoever owns a user seed — the task classes behind isaacgym_amd.make(), PPOTrainer,
+# RLGamesPolicy.act — hands mix64(seed ^ the salt of the family of draws) down instead: seeds that differ in any bit (seed + rank) give unrelated
+# streams, and one user seed given to a task, its randomisation plan and its trainer never yields one draw twice.
+STREAM_ENV, STREAM_TABLES, STREAM_SAMPLER = 0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0   # serve / reset draws + step noise; tables; exploration noise
+
+
+def stream_seed(seed, family_salt):
+    """mix64(seed ^ family_salt): the seed the native layer is given for one family of draws of the user's `seed`."""
+    return _mix64((int(seed) ^ family_salt) & 0xFFFFFFFFFFFFFFFF)
+
+
 def ta_reset_draws(params, env_ids, episodes):
     """Host restatement of the 27-DoF task's reset draws (ta_post_physics_kernel, TA:976-979 + 346-377): for each (env,
     episode) the five values ball y, ball z, vx, vy, vz.  Used to lay out the state at creation (episode 0); resets during

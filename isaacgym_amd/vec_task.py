@@ -110,6 +110,15 @@ class VecTask:
         self.reset_buf_force = torch.zeros(rows, device=self.device, dtype=torch.long)
         self._obs_clipped = None if not np.isfinite(self.clip_obs) else torch.empty_like(self.obs_buf)
 
+    @staticmethod
+    def native_seeds(cfg):
+        """cfg["seed"] — the user's — as the native layer gets it: (the env stream, for ppenv_config.seed / ppenv_ta_params.seed: serve and
+        reset draws, step noise; the tables' stream, for the reset-randomisation plan).  The native seeds key the counter RNG as given, and
+        it XORs its seed into the env id before any mixing: tasks keyed by seed and seed + 1 themselves would serve the same balls, permuted
+        over envs (scene.stream_seed)."""
+        seed = int((cfg or {}).get("seed", 0))
+        return scene.stream_seed(seed, scene.STREAM_ENV), scene.stream_seed(seed, scene.STREAM_TABLES)
+
     def _set_reset_randomization(self):
         """apply_at: "reset" — the actor-parameter tables of randomization_params become a device plan of the environment
         (set_reset_randomization); `randomize_buf` is from now on the buffer the kernel maintains: control steps since the env's last
@@ -118,7 +127,8 @@ class VecTask:
                                               mass_rows=getattr(self, "DR_MASS_ROWS", scene.NUM_DOF))
         if not plan["tables"]:
             return
-        self.randomize_buf = self.env.set_reset_randomization(plan).randomize_buf
+        # the tables' own stream of the task's seed: not the serve's, not the noise's, and unrelated to seed + 1's
+        self.randomize_buf = self.env.set_reset_randomization(plan, seed=self.native_seeds(self.cfg)[1]).randomize_buf
         self._dr_reset = True
 
     # -- the surface rl_games drives
@@ -326,12 +336,17 @@ class _HumanoidPingpongBase(VecTask):
         self.body_states_id = torch.tensor(env["bodyStatesId"], dtype=torch.long, device=self.device)
         self.num_steps = 0
 
+    @classmethod
+    def build_native_config(cls, cfg, num_envs=None, device_id=0):
+        """The ppenv_config of this task for a task cfg: cfg["seed"] enters as its env stream (native_seeds), cfg["env_id_offset"] as given."""
+        table, ball = scene.asset_geometry(cfg["scene"])              # pingpong_table.urdf / small_ball.urdf when the cfg names them (TT:496,502)
+        return scene.build_config(cls.VARIANT, cfg=cfg, num_envs=num_envs, seed=cls.native_seeds(cfg)[0], device_id=device_id,
+                                  env_id_offset=int(cfg.get("env_id_offset", 0)), table=table, ball=ball)
+
     def create_sim(self):
         """TT:325-344: build the scene.  Here: scene constants -> ppenv_config -> native handle."""
         self.up_axis_idx = 2
-        table, ball = scene.asset_geometry(self.cfg["scene"])         # pingpong_table.urdf / small_ball.urdf when the cfg names them (TT:496,502)
-        self.native_config = scene.build_config(self.VARIANT, cfg=self.cfg, num_envs=self.num_envs, seed=self._seed,
-                                                device_id=self.device_id, env_id_offset=self._env_id_offset, table=table, ball=ball)
+        self.native_config = self.build_native_config(self.cfg, self.num_envs, self.device_id)
         k = self.control_freq_inv
         if k < 1:
             raise ValueError("controlFrequencyInv must be >= 1")
@@ -448,7 +463,8 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
         table, ball = scene.asset_geometry(self.cfg.get("scene", {}))     # TA:551,557
         scene_cfg = scene.build_ta_scene(self.num_envs, device_id=self.device_id, table=table, ball=ball) if (table or ball) else None
         with torch.cuda.device(self.device):
-            self.env = TAEnv(self.num_envs, device=self.device, seed=self._seed, env_id_offset=self._env_id_offset, env=env, scene_cfg=scene_cfg)
+            self.env = TAEnv(self.num_envs, device=self.device, seed=self.native_seeds(self.cfg)[0], env_id_offset=self._env_id_offset,
+                             env=env, scene_cfg=scene_cfg)
         e = self.env
         self.root_states = self.vec_root_states = e.root_states
         self.vec_dof_states = e.dof_states

@@ -110,6 +110,13 @@ void shim_serve_velocity(const ppenv_config* cfg, uint32_t gid, uint32_t episode
     V3 v = serve_velocity(make_step_consts(*cfg), gid, episode);
     out[0] = v.x; out[1] = v.y; out[2] = v.z;
 }
+
+// The keyed streams (tests/test_rng_streams_host.py): the counter RNG under the seed a kernel is given, and the noise draw the step kernels and
+// the sampler take from it (host branch: libm)
+float shim_rng_uniform(uint64_t kernel_seed, uint32_t gid, uint32_t episode, uint32_t k) { return rng_uniform(kernel_seed, gid, episode, k); }
+float shim_dr_gauss(uint64_t kernel_seed, uint32_t gid, uint32_t episode, uint32_t progress, uint32_t index) {
+    return dr_gauss(kernel_seed, gid, episode, progress, index);
+}
 }
 
 // ---- 27-DoF variant: the rigid-body step through the kernels' arithmetic (ppenv_ta_device.h)

@@ -137,7 +137,7 @@ def test_4actor_step_under_the_drawn_tables_matches_oracle(torch_cuda, oracle_li
     task = make_task(T4, n, 17, block, frequency=5, apply_at="reset")
     env, rr, cfg = task.env, task.env.reset_randomization, task.native_config
     assert rr.reset_rows == 2 and env.num_agents == 2
-    host = drs.HostDR(rr.plan, n, seed=17, env_id_offset=0, reset_rows=2)
+    host = drs.HostDR(rr.plan, n, seed=scene.stream_seed(17, scene.STREAM_TABLES), env_id_offset=0, reset_rows=2)   # the task's seed as its plan gets it
     gen = torch.Generator(device="cuda:0").manual_seed(3)
     for _ in range(120):
         task.step(torch.rand(2 * n, 7, device="cuda:0", generator=gen) * 2 - 1)
@@ -291,7 +291,7 @@ def test_two_task_shards_compute_the_whole_task(torch_cuda, name):
     R = whole.num_agents
     for t, off in zip(halves, (0, h)):
         P = uploaded_plan(torch, t.env.reset_randomization)
-        assert (P.seed, P.env_id_offset, P.num_envs, P.reset_rows, P.frequency) == (5, off, h, R, 3)
+        assert (P.seed, P.env_id_offset, P.num_envs, P.reset_rows, P.frequency) == (scene.stream_seed(5, scene.STREAM_TABLES), off, h, R, 3)     # the tables' stream of the task's seed
     gen = torch.Generator(device="cuda:0").manual_seed(6)
     cat = lambda f, axis=0: np.concatenate([f(t) for t in halves], axis=axis)
     redraws_after_first = 0
@@ -324,17 +324,18 @@ def test_27dof_task_hands_its_seed_and_offset_to_the_plan(torch_cuda, monkeypatc
     n, seed, off = 128, 21, 128
     task = make_task(TA, n, seed, block_of(TA), env_id_offset=off, frequency=3, apply_at="reset")
     rr, p = task.env.reset_randomization, task.env.params
-    assert (int(p.seed), int(p.env_id_offset)) == (seed, off)
+    tseed = scene.stream_seed(seed, scene.STREAM_TABLES)                           # the task hands each family its own stream of cfg["seed"]
+    assert (int(p.seed), int(p.env_id_offset)) == (scene.stream_seed(seed, scene.STREAM_ENV), off)
     P = uploaded_plan(torch, rr)
-    assert (P.seed, P.env_id_offset, P.num_envs, P.reset_rows, P.frequency) == (seed, off, n, 1, 3)
+    assert (P.seed, P.env_id_offset, P.num_envs, P.reset_rows, P.frequency) == (tseed, off, n, 1, 3)
     gen = torch.Generator(device="cuda:0").manual_seed(1)
     task.step(torch.rand(n, 27, device="cuda:0", generator=gen) * 2 - 1)
-    host = drs.HostDR(rr.plan, n, seed=seed, env_id_offset=off)
+    host = drs.HostDR(rr.plan, n, seed=tseed, env_id_offset=off)
     host.apply(np.ones(n, np.int64))
     for k in TABLES:
         np.testing.assert_array_equal(bits(rr.tables[k]), host.tables[k].reshape(-1).view(np.uint32), err_msg=k)
     assert bool((rr.draws == 1).all()) and not bool(task.randomize_buf.any())
-    unshifted = drs.HostDR(rr.plan, n, seed=seed, env_id_offset=0)
+    unshifted = drs.HostDR(rr.plan, n, seed=tseed, env_id_offset=0)
     unshifted.apply(np.ones(n, np.int64))
     assert (unshifted.tables["link_mass_scale"] != host.tables["link_mass_scale"]).any()   # the offset is in the numbers
 

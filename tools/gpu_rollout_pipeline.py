@@ -12,7 +12,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
-from isaacgym_amd.policy import NativeMLP  # noqa: E402
+from isaacgym_amd.policy import NativeMLP, sampler_stream_seed  # noqa: E402
 from isaacgym_amd.tensor_api import TAEnv  # noqa: E402
 
 UNITS = [2048, 1536, 1024, 1024, 512, 512]
@@ -52,7 +52,7 @@ for K, CUS in KS:
             nets[k].attach_env(envs[k])
 
     def chain(k, s):
-        nets[k].forward(envs[k].obs_buf, prepared=ATTACH, sample=dict(actions=acts[k], sigma=sigma, seed=k, counter=s + 1, neglogp=nlps[k]))
+        nets[k].forward(envs[k].obs_buf, prepared=ATTACH, sample=dict(actions=acts[k], sigma=sigma, seed=sampler_stream_seed(k), counter=s + 1, neglogp=nlps[k]))
         envs[k].step(acts[k])
 
     with torch.no_grad():
