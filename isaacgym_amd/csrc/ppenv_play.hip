@@ -9,12 +9,15 @@
 // The totals are written by the second launch only, which has one workgroup: nothing a workgroup reads is written by another one in
 // the same launch, without atomics, tickets or device-scope fences (such a hand-off costs more than the launch boundary).
 //
+// The grouped entries (include/ppenv_play_group.h: the same accounting for G populations of envs in the same two launches) are at the end.
+//
 // -ffinite-math-only is NOT in this unit's flags (isaacgym_amd/_lib.py): the minima / maxima start at +-inf.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "ppenv_play_device.h"
+#include "../../include/ppenv_play_group.h"
 
 #include "ppenv_host.h"
 
@@ -122,4 +125,101 @@ extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int3
     if (int rc = pp_launched("launching play_rows_kernel failed")) return rc;
     hipLaunchKernelGGL(play_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
     return pp_launched("launching play_totals_kernel failed");
+}
+
+// ---- grouped accounting (include/ppenv_play_group.h): G populations of S envs, each with its own totals and its own freeze ------------
+// The same two launches, whatever G is:
+//   play_group_rows_kernel     workgroup b is chunk b % P of group b / P (P = chunks of 256 envs in S, counted from the group's first env,
+//                              ragged last chunk per group): the freeze test on totals[g] is uniform in the workgroup, and lane / wave /
+//                              chunk of an env are the ones play_rows_kernel gives it in a run of S envs — the same sums, bit for bit.
+//   play_group_totals_kernel   one wave per group: play_totals_kernel on the group's P partials and totals[g].
+// Wave g of the second launch reads and writes totals[g] alone; the first launch writes no totals.
+namespace {
+
+__global__ __launch_bounds__(kBlock) void play_group_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t envs_per_group,
+                                                                 int32_t parts, int32_t num_agents, int64_t games_num, float* __restrict__ cur_reward,
+                                                                 int32_t* __restrict__ cur_steps, const ppenv_play_totals* __restrict__ totals,
+                                                                 ppenv_play_partial* __restrict__ partial) {
+    __shared__ ppenv_play_partial wave_part[kWaves];
+    const int32_t g = (int32_t)blockIdx.x / parts, chunk = (int32_t)blockIdx.x - g * parts;
+    if (pp::play_frozen(totals[g].games, games_num)) return;     // uniform: the whole workgroup leaves (its partial is not read either)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int32_t local = chunk * kBlock + tid;                  // the env's index within its group
+    ppenv_play_partial acc;
+    pp::play_clear(acc);
+    if (local < envs_per_group) pp::play_env(g * envs_per_group + local, num_agents, rew, done, cur_reward, cur_steps, acc);
+    wave_merge(acc);
+    if (lane == 0) wave_part[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        ppenv_play_partial s = wave_part[0];
+        for (int w = 1; w < kWaves; ++w) pp::play_merge(s, wave_part[w]);
+        partial[blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(64) void play_group_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
+                                                               ppenv_play_totals* __restrict__ totals) {
+    const int32_t g = (int32_t)blockIdx.x;
+    if (pp::play_frozen(totals[g].games, games_num)) return;     // the word the group's chunks tested: nothing wrote it in between
+    const ppenv_play_partial* mine = partial + (size_t)g * parts;
+    ppenv_play_partial acc;
+    pp::play_clear(acc);
+    for (int32_t b = (int32_t)threadIdx.x; b < parts; b += 64) pp::play_merge(acc, mine[b]);
+    wave_merge(acc);
+    if (threadIdx.x == 0) {
+        ppenv_play_totals t = totals[g];
+        pp::play_totals_add(t, acc);
+        totals[g] = t;
+    }
+}
+
+__global__ __launch_bounds__(kBlock) void play_group_reset_kernel(int32_t num_envs, int32_t rows, int32_t groups, float* __restrict__ cur_reward,
+                                                                  int32_t* __restrict__ cur_steps, ppenv_play_totals* __restrict__ totals) {
+    const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (i < rows) cur_reward[i] = 0.0f;
+    if (i < num_envs) cur_steps[i] = 0;
+    if (i < groups) {                                            // groups <= num_envs <= rows: the grid covers them
+        ppenv_play_totals t;
+        pp::play_totals_clear(t);
+        totals[i] = t;
+    }
+}
+
+bool group_sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents) {
+    return groups >= 1 && groups <= PP_PLAY_GROUP_MAX && envs_per_group > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS &&
+           (int64_t)envs_per_group * groups * num_agents <= INT32_MAX;
+}
+
+}  // namespace
+
+extern "C" size_t pp_play_group_partial_bytes(int32_t envs_per_group, int32_t groups) {
+    return group_sizes_ok(envs_per_group, groups, 1) ? (size_t)groups * (size_t)blocks_of(envs_per_group) * sizeof(ppenv_play_partial) : 0;
+}
+
+extern "C" int pp_play_group_reset(int32_t envs_per_group, int32_t groups, int32_t num_agents, float* cur_reward, int32_t* cur_steps,
+                                   ppenv_play_totals* totals, void* stream) {
+    if (!group_sizes_ok(envs_per_group, groups, num_agents) || !cur_reward || !cur_steps || !totals) {
+        ppenv_set_error("pp_play_group_reset: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
+        return PPENV_EINVAL;
+    }
+    const int32_t num_envs = envs_per_group * groups, rows = num_envs * num_agents;
+    hipLaunchKernelGGL(play_group_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, groups, cur_reward, cur_steps,
+                       totals);
+    return pp_launched("launching play_group_reset_kernel failed");
+}
+
+extern "C" int pp_play_group_accumulate(const float* rew, const int64_t* done, int32_t envs_per_group, int32_t groups, int32_t num_agents, int64_t games_num,
+                                        float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
+    if (!group_sizes_ok(envs_per_group, groups, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+        ppenv_set_error("pp_play_group_accumulate: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, "
+                        "or games_num < 1");
+        return PPENV_EINVAL;
+    }
+    const int32_t parts = blocks_of(envs_per_group);             // per group; groups * parts <= 2^31 / 256 workgroups
+    hipLaunchKernelGGL(play_group_rows_kernel, dim3((uint32_t)groups * (uint32_t)parts), dim3(kBlock), 0, (hipStream_t)stream, rew, done, envs_per_group, parts,
+                       num_agents, games_num, cur_reward, cur_steps, totals, partial);
+    if (int rc = pp_launched("launching play_group_rows_kernel failed")) return rc;
+    hipLaunchKernelGGL(play_group_totals_kernel, dim3(groups), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
+    return pp_launched("launching play_group_totals_kernel failed");
 }

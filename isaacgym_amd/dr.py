@@ -9,6 +9,9 @@ import torch
 
 from . import _lib, scene
 
+# the per-env tables of set_randomization, in the order of scene.Randomization's pointers (the keys of every DR_TABLE_ROWS)
+TABLE_NAMES = ("dof_stiffness_scale", "dof_damping_scale", "link_mass_scale", "restitution_scale", "friction_scale")
+
 
 class ResetRandomizer:
     def __init__(self, L, device, num_envs, plan, table_rows, seed=0, env_id_offset=0, reset_rows=1):

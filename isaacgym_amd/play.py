@@ -4,6 +4,7 @@
     Player(task, policy, games_num=2000).run()      games_num episodes of `task` under `policy` -> rl_games' numbers (average return,
                                                     average episode length) plus spread
     python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side --capture-deferred --capture-trajectory out.npz]
+    python -m isaacgym_amd.play ... --sweep link_mass_scale=0.7:1.3:4 --sweep friction_scale=0.5,1.0 [--sweep-out cells.json]      one pass over the grid
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -20,20 +21,34 @@ The player drives `task.step(actions)` — the VecTask surface rl_games' player 
 controlFrequencyInv and both domain-randomisation modes behave as for any caller; a task with `randomize: True` plays under its
 randomisation (evaluation; PPOTrainer's refusal of such a task is about training below that surface and is untouched).
 
-Out of scope: capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
+Sweeps.  `Player(task, policy, sweep=Sweep.grid({"link_mass_scale": [0.7, 1.3], "friction_scale": [0.5, 1.0]}))` plays the checkpoint under
+every cell of a grid of physical-parameter scales in ONE pass: the envs are split into G equal groups (group g is envs [g * S, (g + 1) * S)),
+each group runs whole episodes under its cell's per-env tables (the domain-randomisation tables of dr.Randomizable.set_randomization, set before
+the first reset), and `GroupStats` keeps one totals struct and one freeze per group in the same two launches per control step, whatever G
+is (include/ppenv_play_group.h).  Groups see DIFFERENT serves that are identically distributed — the env RNG is keyed by the global env
+id, and there are no common random numbers across groups — which is why every group reports `reward_stderr` = reward_std / sqrt(games):
+two cells differ when their averages differ by more than a few standard errors, not when they differ at all.
+
+Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), serve sweeps, common random
+numbers across groups, per-group outcome counts, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
 `--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
 """
 import argparse
 import ctypes as C
+import itertools
+import json
 import math
+import re
 import time
 
+import numpy as np
 import torch
 
 from . import _lib
 from ._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ctypes mirror of ppenv_play_totals (bound in _lib.load)
 from ._lib import TA_OUTCOME_NAMES, TAOutcome
+from .dr import TABLE_NAMES
 
 # the reference's five prints (TA:1164-1168), in its order and wording
 OUTCOME_PRINTS = (("fall_down", "the sum of the huamnoid which fall down:"), ("closer", "the sum of the envs which are closer to the paddle:"),
@@ -143,6 +158,194 @@ class EpisodeStats:
                    self.L)
 
 
+MAX_GROUPS = 1024                          # PP_PLAY_GROUP_MAX
+
+
+class GroupStats:
+    """The EpisodeStats of the grouped entries (include/ppenv_play_group.h): `groups` populations of `envs_per_group` envs, group g being
+    envs [g * S, (g + 1) * S) of the task, each with its own totals struct and its own freeze at games_num; two launches per
+    accumulate whatever the group count.  Group g's totals and its slices of cur_reward / cur_steps are byte for byte those of an
+    EpisodeStats(envs_per_group, num_agents, games_num) fed the group's slices.  Nothing here synchronises except read()."""
+
+    def __init__(self, envs_per_group, groups, num_agents, games_num, device):
+        self.envs_per_group, self.groups, self.num_agents, self.games_num = int(envs_per_group), int(groups), int(num_agents), int(games_num)
+        if self.envs_per_group < 1 or not 1 <= self.groups <= MAX_GROUPS or self.num_agents not in (1, 2) or self.games_num < 1 or \
+                self.envs_per_group * self.groups * self.num_agents > 2 ** 31 - 1:
+            raise ValueError(f"GroupStats: envs_per_group {envs_per_group} (>= 1), groups {groups} (1..{MAX_GROUPS}), num_agents {num_agents} (1 or 2), "
+                             f"games_num {games_num} (>= 1), at most 2^31 - 1 rows")
+        self.device = torch.device(device)
+        self.num_envs = self.envs_per_group * self.groups
+        self.rows = self.num_envs * self.num_agents
+        L = self.L = _lib.lib()
+        dev = self.device
+        self.cur_reward = torch.zeros(self.rows, dtype=torch.float32, device=dev)
+        self.cur_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self._totals = torch.zeros(self.groups * C.sizeof(PlayTotals), dtype=torch.uint8, device=dev)
+        self._partial = torch.zeros(int(L.pp_play_group_partial_bytes(self.envs_per_group, self.groups)), dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self):
+        _lib.check(self.L.pp_play_group_reset(self.envs_per_group, self.groups, self.num_agents, self.cur_reward.data_ptr(), self.cur_steps.data_ptr(),
+                                              self._totals.data_ptr(), _lib.stream(self.device)), self.L)
+
+    def accumulate(self, rew, done):
+        """One control step of every group, after the env step: rew [rows] f32, done [rows] int64 (all groups' rows, in env order),
+        contiguous, on this device.  Two launches, no synchronisation."""
+        if rew.dtype != torch.float32 or done.dtype != torch.int64 or rew.numel() != self.rows or done.numel() != self.rows or \
+                not rew.is_contiguous() or not done.is_contiguous() or rew.device != self.device or done.device != self.device:
+            raise ValueError(f"GroupStats.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
+        _lib.check(self.L.pp_play_group_accumulate(rew.data_ptr(), done.data_ptr(), self.envs_per_group, self.groups, self.num_agents, self.games_num,
+                                                   self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self._totals.data_ptr(),
+                                                   self._partial.data_ptr(), _lib.stream(self.device)), self.L)
+
+    def read(self):
+        """One host copy of the `groups` structs (groups x 72 bytes; the stream is waited for) -> a list of totals_dict, in group order."""
+        raw, n = self._totals.cpu().numpy().tobytes(), C.sizeof(PlayTotals)
+        return [totals_dict(PlayTotals.from_buffer_copy(raw[g * n:(g + 1) * n]), self.num_agents) for g in range(self.groups)]
+
+    def state_bytes(self):
+        """cur_reward, cur_steps and the `groups` totals structs as host bytes."""
+        return self.cur_reward.cpu().numpy().tobytes(), self.cur_steps.cpu().numpy().tobytes(), self._totals.cpu().numpy().tobytes()
+
+    def group_state_bytes(self, g):
+        """Group g's part of state_bytes(): what EpisodeStats.state_bytes() gives for that group's envs alone."""
+        cr, cs, tot = self.state_bytes()
+        S, A, n = self.envs_per_group, self.num_agents, C.sizeof(PlayTotals)
+        return cr[4 * A * S * g:4 * A * S * (g + 1)], cs[4 * S * g:4 * S * (g + 1)], tot[n * g:n * (g + 1)]
+
+
+_AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
+
+
+def _axis(axis):
+    """'name' or 'name[row]' -> (table name, row or None); a name that is no table of set_randomization raises ValueError."""
+    m = _AXIS.match(axis) if isinstance(axis, str) else None
+    if m is None or m.group(1) not in TABLE_NAMES:
+        raise ValueError(f"sweep axis {axis!r}: an axis is one of {', '.join(TABLE_NAMES)}, or one row of a table as name[row]")
+    return m.group(1), None if m.group(2) is None else int(m.group(2))
+
+
+class Sweep:
+    """G cells of physical-parameter scales, one per group of envs.  A cell maps an axis to one scalar scale; an axis is a table of
+    dr.Randomizable.set_randomization (`friction_scale`: every row of it) or one row of one (`dof_stiffness_scale[5]`, which wins over
+    the plain axis of the same table in that row).  What a cell does not name stays 1.0."""
+
+    def __init__(self, cells):
+        self.cells = [dict(c) for c in cells]
+        if not 1 <= len(self.cells) <= MAX_GROUPS:
+            raise ValueError(f"a sweep has 1..{MAX_GROUPS} cells, not {len(self.cells)}")
+        for cell in self.cells:
+            for axis, v in cell.items():
+                _axis(axis)
+                cell[axis] = float(v)
+                if not math.isfinite(cell[axis]) or cell[axis] < 0.0:
+                    raise ValueError(f"sweep axis {axis!r}: the scale {v!r} is not a finite number >= 0")
+
+    def __len__(self):
+        return len(self.cells)
+
+    @classmethod
+    def grid(cls, axes):
+        """{axis: values, ...} -> the Cartesian product, the last axis fastest."""
+        names = list(axes)
+        values = [list(axes[k]) for k in names]
+        if not names or any(len(v) == 0 for v in values):
+            raise ValueError("Sweep.grid: at least one axis, and at least one value per axis")
+        return cls([dict(zip(names, combo)) for combo in itertools.product(*values)])
+
+    @classmethod
+    def parse(cls, specs):
+        """The CLI form, one 'AXIS=SPEC' per axis -> Sweep.grid: SPEC is `lo:hi:count` (an inclusive linspace) or a comma list taken as given."""
+        axes = {}
+        for spec in specs:
+            axis, eq, text = str(spec).partition("=")
+            axis = axis.strip()
+            try:
+                if not eq or not text.strip():
+                    raise ValueError("no '=' or nothing after it")
+                if ":" in text:
+                    lo, hi, count = text.split(":")
+                    if int(count) < 1:
+                        raise ValueError("count < 1")
+                    values = [float(v) for v in np.linspace(float(lo), float(hi), int(count))]
+                else:
+                    values = [float(v) for v in text.split(",")]
+            except ValueError as e:
+                raise ValueError(f"--sweep {spec!r}: expected AXIS=lo:hi:count or AXIS=v0,v1,... ({e})") from None
+            if axis in axes:
+                raise ValueError(f"--sweep {spec!r}: the axis {axis!r} is given twice")
+            _axis(axis)
+            axes[axis] = values
+        return cls.grid(axes)
+
+    def tables(self, rows_by_name, num_envs):
+        """The per-env tables of this sweep for an environment of num_envs envs whose tables have rows_by_name rows (its DR_TABLE_ROWS; 0: a
+        per-env scalar) -> {name: float32 array [rows, N] or [N]} for the tables some cell names; cell g fills columns [g * S, (g + 1) * S)."""
+        G, N = len(self.cells), int(num_envs)
+        if N < G or N % G:
+            below = N // G * G
+            raise ValueError(f"a sweep of {G} cells needs a multiple of {G} envs, not {N}: the nearest are " +
+                             (f"{below} and {below + G}" if below > 0 else f"{G}"))
+        S = N // G
+        out = {}
+        for plain in (True, False):                                  # the whole-table axes first, then the single rows over them
+            for g, cell in enumerate(self.cells):
+                for axis, v in cell.items():
+                    name, row = _axis(axis)
+                    if (row is None) != plain:
+                        continue
+                    if name not in rows_by_name:
+                        raise ValueError(f"sweep axis {axis!r}: this environment's tables are {', '.join(rows_by_name)}")
+                    rows = int(rows_by_name[name])
+                    if name not in out:
+                        out[name] = np.ones((rows, N) if rows else (N,), np.float32)
+                    if row is None:
+                        out[name][..., g * S:(g + 1) * S] = v
+                    elif row >= rows:
+                        raise ValueError(f"sweep axis {axis!r}: {name} has " + (f"{rows} rows (0..{rows - 1})" if rows else "no rows (one scale per env: name it plainly)") +
+                                         f"; the tables and their rows are {dict(rows_by_name)}")
+                    else:
+                        out[name][row, g * S:(g + 1) * S] = v
+        return out
+
+
+def sum_totals(per_group):
+    """A list of totals dicts (GroupStats.read()) -> one totals dict over all groups: counts and sums added in group order (`launches` too:
+    group-steps), the extrema merged."""
+    A = len(per_group[0]["reward"])
+    out = dict(games=0, steps=0, launches=0, reward=[0.0] * A, reward_sq=[0.0] * A, reward_min=[math.inf] * A, reward_max=[-math.inf] * A)
+    for t in per_group:
+        for k in ("games", "steps", "launches"):
+            out[k] += t[k]
+        for a in range(A):
+            out["reward"][a] += t["reward"][a]
+            out["reward_sq"][a] += t["reward_sq"][a]
+            out["reward_min"][a] = min(out["reward_min"][a], t["reward_min"][a])
+            out["reward_max"][a] = max(out["reward_max"][a], t["reward_max"][a])
+    return out
+
+
+def group_summary(cell, totals, num_agents, games_num):
+    """One entry of run()'s `groups`: the cell, summarize() of the group's totals, reward_stderr = reward_std / sqrt(games) (nan with no
+    game) and complete = games >= games_num."""
+    out = dict(cell=dict(cell))
+    out.update(summarize(totals, num_agents))
+    g = out["games"]
+    out["reward_stderr"] = out["reward_std"] / math.sqrt(g) if g > 0 else float("nan")
+    out["complete"] = g >= int(games_num)
+    return out
+
+
+def cell_text(cell):
+    return " ".join(f"{k}={v:g}" for k, v in cell.items()) or "(plain)"
+
+
+def group_line(g):
+    """The CLI's line for one entry of `groups`."""
+    return (f"cell {cell_text(g['cell'])}: games {g['games']} av reward {g['av_reward']:.6g} +- {g['reward_stderr']:.3g} av steps {g['av_steps']:.6g} "
+            f"min {g['reward_min']:.6g} max {g['reward_max']:.6g}" + ("" if g["complete"] else " (incomplete)"))
+
+
 class Player:
     """rl_games' BasePlayer.run on a task from isaacgym_amd.make(...) (any of the five registry names; the 4-actor task has two rows per
     env) under an RLGamesPolicy.  The defaults are rl_games' player defaults.
@@ -150,13 +353,26 @@ class Player:
     sigma); it matters only with deterministic=False.
     outcomes: the 27-dof task's five head-counts (task.enable_outcomes(); the other tasks raise ValueError), zeroed by start() and latched
     on the device after every env step under the totals' freeze rule: run()'s `outcomes` are those of the step the totals stopped at,
-    whatever poll_every is."""
+    whatever poll_every is.
+    sweep: a Sweep of G cells — the envs are split into G equal groups, group g plays under cell g's tables (start() hands
+    sweep.tables(...) to task.env.set_randomization before the first reset, so every counted episode runs whole under its cell), and
+    games_num is PER GROUP: each group freezes on its own.  run() ends at the first poll that finds every group frozen, returns the usual
+    dict summed over the groups plus `groups` (one group_summary per cell, in cell order) and leaves the task as it found it: the
+    randomisation cleared and the envs' episode counters (the RNG key of their serves) put back, so what is played on the task afterwards is
+    what would have been played without the sweep.  Groups see different, identically distributed serves (the RNG is keyed by the global
+    env id): compare cells by `reward_stderr`.  Refused with a sweep: a task with `randomize: True` (its tables are the sweep's) and
+    outcomes=True (the 27-dof counts are cross-env windows and cannot be split by group)."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
-                 outcomes=False):
+                 outcomes=False, sweep=None):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
+        if sweep is not None:
+            if outcomes:
+                raise ValueError("outcomes=True with a sweep: the 27-dof outcome counts are cross-env reset windows and cannot be split by group")
+            if getattr(task, "randomize", False):
+                raise ValueError("a sweep on a task with randomize: True: the sweep sets the task's randomisation tables itself; set task.randomize=False")
         rl, sim = torch.device(task.rl_device), torch.device(task.device)
         if rl != sim or sim.type != "cuda":
             raise ValueError(f"Player needs rl_device == sim_device on a GPU (no per-step copies): rl_device is {rl}, sim_device is {sim}")
@@ -171,7 +387,13 @@ class Player:
         self.num_agents = int(getattr(task, "num_agents", 1))
         if sigma is not None:
             policy.sigma.fill_(math.exp(float(sigma)))
-        self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
+        self.sweep = sweep
+        self._tables = self._episode0 = None
+        if sweep is None:
+            self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
+        else:
+            self._tables = sweep.tables(self._dr_handle().DR_TABLE_ROWS, task.num_envs)
+            self.stats = GroupStats(task.num_envs // len(sweep), len(sweep), self.num_agents, self.games_num, sim)
         if recorder is not None and recorder.renderer.task is not task:
             raise ValueError("the recorder renders another task")
         self.recorder = recorder
@@ -183,8 +405,32 @@ class Player:
         self.actions = None
         self._obs = None
 
+    def _dr_handle(self):
+        """The handle that owns the randomisation tables: the 7-dof / 4-actor env itself, the 27-dof env's simulation."""
+        env = self.task.env
+        return env if hasattr(env, "DR_TABLE_ROWS") else env.sim
+
+    def _episode(self):
+        env = self.task.env
+        return env.episode if hasattr(env, "episode") else env.state.episode
+
+    def end_sweep(self):
+        """The task as the sweep found it: the plain step kernel (clear_randomization) and the episode counters of before start().  run() calls
+        it at its end, also on an exception; a caller that drives start() / step() itself calls it when done."""
+        if self.sweep is None:
+            return
+        self.task.env.clear_randomization()
+        if self._episode0 is not None:
+            self._episode().copy_(self._episode0)
+            self._episode0 = None
+        self._obs = None
+
     def start(self):
         """Every env to the start of an episode, the accounting to zero, the action-draw counter to zero (a run is a function of the seed)."""
+        if self.sweep is not None:
+            if self._episode0 is None:
+                self._episode0 = self._episode().clone()
+            self.task.env.set_randomization(**self._tables)           # before the reset: the first counted episode is already the cell's
         self.task.reset_idx()
         self.stats.reset()
         if self.outcome is not None:
@@ -217,7 +463,10 @@ class Player:
     def run(self, on_poll=None):
         """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
         host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds); with
-        outcomes=True also `outcomes` (outcomes_dict of the latched struct)."""
+        outcomes=True also `outcomes` (outcomes_dict of the latched struct).  With a sweep: until EVERY group has counted games_num games;
+        on_poll gets the groups' totals summed (sum_totals), the result is summarize() of that sum plus `groups`."""
+        if self.sweep is not None:
+            return self._run_sweep(on_poll)
         self.start()
         t0 = time.perf_counter()
         tot = None
@@ -242,6 +491,33 @@ class Player:
             out["captured_frames"] = self.recorder.captured
         return out
 
+    def _run_sweep(self, on_poll):
+        try:
+            self.start()
+            t0 = time.perf_counter()
+            per = None
+            while self.steps_played < self.max_steps:
+                self.step()
+                per = None
+                if self.steps_played % self.poll_every == 0:
+                    per = self.stats.read()
+                    if on_poll is not None:
+                        on_poll(sum_totals(per))
+                    if all(t["games"] >= self.games_num for t in per):
+                        break
+            if per is None:
+                per = self.stats.read()
+                if on_poll is not None:
+                    on_poll(sum_totals(per))
+            out = summarize(sum_totals(per), self.num_agents)
+            out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
+            out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num) for cell, t in zip(self.sweep.cells, per)]
+            if self.recorder is not None:
+                out["captured_frames"] = self.recorder.captured
+            return out
+        finally:
+            self.end_sweep()
+
 
 # ---- CLI --------------------------------------------------------------------------------------------------------------------------
 def parse_args(argv=None):
@@ -257,6 +533,10 @@ def parse_args(argv=None):
     ap.add_argument("--poll-every", type=int, default=64, help="control steps between two host reads of the totals")
     ap.add_argument("--max-steps", type=int, default=108000)
     ap.add_argument("--outcomes", action="store_true", help="27-dof task: print the reference's five outcome counts (TA:1164-1168) as rates of the envs")
+    ap.add_argument("--sweep", action="append", default=None, metavar="AXIS=SPEC", help="play under a grid of physical-parameter scales in one pass (repeatable: "
+                    "one axis each; the envs are split into one group per cell and --games is per cell): AXIS is dof_stiffness_scale, dof_damping_scale, "
+                    "link_mass_scale, restitution_scale or friction_scale, or one row of a table as NAME[ROW]; SPEC is lo:hi:count (inclusive) or v0,v1,...")
+    ap.add_argument("--sweep-out", default=None, metavar="FILE.json", help="with --sweep: write the per-cell results (the result's `groups`) to FILE.json")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -269,7 +549,15 @@ def parse_args(argv=None):
     ap.add_argument("--capture-trajectory", default=None, metavar="FILE.npz", help="also save the recording as data (records deferred): "
                     "python -m isaacgym_amd.render replay draws it again at any size, sample count and camera")
     ap.add_argument("--camera", choices=("side", "follow"), default="side", help="side: table and humanoid(s); follow: the reference viewer's follow-cam")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.sweep_out and not args.sweep:
+        ap.error("--sweep-out needs --sweep")
+    if args.sweep:
+        try:
+            Sweep.parse(args.sweep)
+        except ValueError as e:
+            ap.error(str(e))
+    return args
 
 
 def make_renderer(task, args):
@@ -304,8 +592,9 @@ def main(argv=None):
     task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
     recorder = make_recorder(task, args) if args.capture or args.capture_trajectory else None
+    sweep = Sweep.parse(args.sweep) if getattr(args, "sweep", None) else None
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
-                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes)
+                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep)
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -324,6 +613,12 @@ def main(argv=None):
         print("\n".join(outcome_lines(res["outcomes"])) if res["outcomes"]["windows"] > 0 else "no env has reset: no outcome window yet")
     for a, p in enumerate(res["per_agent"]):
         print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
+    for g in res.get("groups", ()):
+        print(group_line(g))
+    if getattr(args, "sweep_out", None):
+        with open(args.sweep_out, "w") as fh:
+            json.dump(res["groups"], fh, indent=1)
+        print(f"wrote {args.sweep_out}")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
     if recorder is not None and args.capture_trajectory:
         print(f"saved {recorder.trajectory.save(args.capture_trajectory, fps=args.capture_fps)} (trajectory)", flush=True)

@@ -4,6 +4,7 @@ accounting (the eager, non-graph step of tools/rollout_bench.py through the VecT
 
     python tools/play_bench.py --task HumanoidPingpongTiltG1 --num-envs 4096
     rocprofv3 --kernel-trace --stats -d out -o play -- python tools/play_bench.py --num-envs 4096 --repeats 1      # the launches' own time
+    python tools/play_bench.py --num-envs 4096 --sweep-groups 16      # the same loops under Player(sweep=): 16 groups, the grouped accounting
 """
 import argparse
 import json
@@ -25,6 +26,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=128)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--poll-every", type=int, default=64)
+    ap.add_argument("--sweep-groups", type=int, default=0, help="G > 0: play under a sweep of G cells (friction_scale 0.5 .. 1.5), G groups of num_envs / G envs")
     args = ap.parse_args()
     import torch
     import isaacgym_amd
@@ -34,7 +36,11 @@ def main():
     task = isaacgym_amd.make(seed=1, task=args.task, num_envs=args.num_envs)
     sd = _rlgames_state_dict(torch, task.num_obs, tuple(UNITS), task.num_actions, torch.Generator().manual_seed(0))
     policy = RLGamesPolicy(sd, task.device)
-    pl = Player(task, policy, games_num=1 << 40, poll_every=args.poll_every)       # never frozen: every step pays the full accounting
+    sweep = {}
+    if args.sweep_groups > 0:
+        from isaacgym_amd.play import Sweep
+        sweep["sweep"] = Sweep.parse([f"friction_scale=0.5:1.5:{args.sweep_groups}"])
+    pl = Player(task, policy, games_num=1 << 40, poll_every=args.poll_every, **sweep)       # never frozen: every step pays the full accounting
     pl.start()
 
     def bare():
@@ -63,7 +69,11 @@ def main():
         for k, fn in loops.items():
             us[k].append(timed(fn, args.steps))
     tot = pl.stats.read()
-    out = {"task": args.task, "num_envs": args.num_envs, "rows": pl.stats.rows, "steps": args.steps, "repeats": args.repeats,
+    if args.sweep_groups > 0:
+        from isaacgym_amd.play import sum_totals
+        tot = sum_totals(tot)
+        tot["launches"] //= args.sweep_groups
+    out = {"task": args.task, "num_envs": args.num_envs, "sweep_groups": args.sweep_groups, "rows": pl.stats.rows, "steps": args.steps, "repeats": args.repeats,
            "poll_every": args.poll_every, "games": tot["games"], "launches": tot["launches"]}
     for k, v in us.items():
         out[f"{k}_us"] = round(statistics.median(v), 2)
