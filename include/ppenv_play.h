@@ -16,9 +16,12 @@
  * Two launches per call, the shape of ppenv_ppo_loss_grad.  play_rows_kernel: lane e owns env e, 256 envs per workgroup; it
  * advances cur_reward / cur_steps, and each workgroup writes ONE ppenv_play_partial (its finished games, summed by wave shuffles and LDS
  * in a fixed order).  play_totals_kernel: one wave sums the partials in a fixed order and adds them to the totals.  Both read
- * totals.games for the freeze; only the second writes the totals, and it is alone in its launch — no word a workgroup reads is written
- * by another workgroup in the same launch.  No atomics: every sum has a fixed order, results are bitwise reproducible run to run.
+ * totals.games for the freeze; only the second writes the totals — no word a workgroup reads is written by another workgroup in the
+ * same launch.  No atomics: every sum has a fixed order, results are bitwise reproducible run to run.
  * Sums across games are fp64 (a game's return itself is fp32, rl_games' `cr += r` in step order).
+ *
+ * These entries are the G = 1 case of ppenv_play_group.h's (one group of num_envs envs, totals[0] = *totals) and run the same kernels;
+ * they keep their own argument validation and error texts.
  *
  * Plain C, device pointers, caller's HIP stream, no synchronisation; returns 0 or a negative PPENV_E* code (ppenv.h) with the
  * message in ppenv_last_error().

@@ -7,17 +7,18 @@
  * group has its own ppenv_play_totals, totals[g], and its own FREEZE: a call that finds totals[g].games >= games_num changes no word of
  * totals[g] and no cur_reward / cur_steps of group g's envs, bit for bit, while the other groups go on; `launches` counts per group.
  *
- * The contract that makes this checkable: after any sequence of calls, totals[g] and group g's slices of cur_reward and cur_steps are
- * BYTE FOR BYTE what ppenv_play_reset / ppenv_play_accumulate leave when given S envs and group g's slices of `rew` and `done`.  The
- * sums therefore keep the order of play_rows_kernel / play_totals_kernel: chunks of PPENV_PLAY_BLOCK envs counted from the GROUP's first
- * env (a ragged last chunk per group), the xor butterfly within a wave, the four waves in order through LDS, one ppenv_play_partial per
- * chunk; then per group lane l sums the group's partials l, l + 64, ... in order, a butterfly, lane 0 adds the result to totals[g].
+ * The rule: after any sequence of calls, totals[g] and group g's slices of cur_reward and cur_steps are BYTE FOR BYTE what
+ * ppenv_play_reset / ppenv_play_accumulate leave when given S envs and group g's slices of `rew` and `done`.  It holds by construction:
+ * ppenv_play.h's entries are the G = 1 case of these and run the same kernels, and nothing an env goes through depends on its group —
+ * the sum order is chunks of PPENV_PLAY_BLOCK envs counted from the GROUP's first env (a ragged last chunk per group), the xor butterfly
+ * within a wave, the four waves in order through LDS, one ppenv_play_partial per chunk; then per group lane l sums the group's partials
+ * l, l + 64, ... in order, a butterfly, lane 0 adds the result to totals[g].
  *
- * Two launches per call, whatever G is.  play_group_rows_kernel: one workgroup per chunk, so a workgroup belongs to one group and the
- * freeze test is uniform in it; it reads totals[g].games and writes no word of the totals.  play_group_totals_kernel: one wave per
+ * Two launches per call, whatever G is.  play_rows_kernel: one workgroup per chunk, so a workgroup belongs to one group and the
+ * freeze test is uniform in it; it reads totals[g].games and writes no word of the totals.  play_totals_kernel: one wave per
  * group; wave g reads and writes totals[g] and nobody else's.  No word read by one workgroup is written by another in the same launch;
  * no atomics; every sum has a fixed order, results are bitwise reproducible run to run.  The per-env arithmetic is
- * ppenv_play_device.h's, unchanged.
+ * ppenv_play_device.h's.
  *
  * Plain C, device pointers, caller's HIP stream, no synchronisation; returns 0 or a negative PPENV_E* code (ppenv.h) with the
  * message in ppenv_last_error().  Refused with PPENV_EINVAL before any device call: a NULL pointer, groups outside

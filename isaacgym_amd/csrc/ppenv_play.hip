@@ -1,15 +1,18 @@
-// ppenv_play.hip — episode accounting for playing a checkpoint, on the device (include/ppenv_play.h).
+// ppenv_play.hip — episode accounting for playing a checkpoint, on the device: G populations of S envs, each with its own totals and
+// its own freeze (include/ppenv_play_group.h); the single accounting (include/ppenv_play.h) is G = 1, S = num_envs of the same kernels.
 //
-// Bound by launch latency, not bytes: a control step moves 12-20 B per row.  Two launches per step, the shape of ppo_loss_grad_kernel /
-// ppo_loss_reduce_kernel:
-//   play_rows_kernel     lane e owns env e (256 envs per workgroup, ragged tail guarded): the per-env step of ppenv_play_device.h, then
-//                        the workgroup's finished games summed in a fixed order (xor butterfly within a wave, the four waves in order through
-//                        LDS) into ONE ppenv_play_partial.  Reads totals.games for the freeze; writes no word of the totals.
-//   play_totals_kernel   one wave: lane l sums partials l, l + 64, ... in order, a butterfly, lane 0 adds the result to the totals.
-// The totals are written by the second launch only, which has one workgroup: nothing a workgroup reads is written by another one in
-// the same launch, without atomics, tickets or device-scope fences (such a hand-off costs more than the launch boundary).
-//
-// The grouped entries (include/ppenv_play_group.h: the same accounting for G populations of envs in the same two launches) are at the end.
+// Bound by launch latency, not bytes: a control step moves 12-20 B per row.  Two launches per step whatever G is, the shape of
+// ppo_loss_grad_kernel / ppo_loss_reduce_kernel:
+//   play_rows_kernel     workgroup (x, y) of a P x G grid is chunk x of group y (P = chunks of 256 envs in S, counted from the group's first
+//                        env, ragged last chunk per group guarded); a lane owns one env: the per-env step of ppenv_play_device.h, then the workgroup's
+//                        finished games summed in a fixed order (xor butterfly within a wave, the four waves in order through LDS) into
+//                        ONE ppenv_play_partial.  Reads totals[g].games for the freeze; writes no word of the totals.
+//   play_totals_kernel   one wave per group: lane l sums the group's partials l, l + 64, ... in order, a butterfly, lane 0 adds the result
+//                        to totals[g].
+// The totals are written by the second launch only, and wave g of it reads and writes totals[g] alone: nothing a workgroup reads is
+// written by another one in the same launch, without atomics, tickets or device-scope fences (such a hand-off costs more than
+// the launch boundary).  An env's lane, wave and chunk depend on its index within its group alone, so a group's sums are bit for bit
+// those of a run of its S envs by themselves.
 //
 // -ffinite-math-only is NOT in this unit's flags (isaacgym_amd/_lib.py): the minima / maxima start at +-inf.
 #include <hip/hip_runtime.h>
@@ -46,102 +49,13 @@ __device__ __forceinline__ void wave_merge(ppenv_play_partial& p) {
     }
 }
 
-__global__ __launch_bounds__(kBlock) void play_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t num_envs,
-                                                           int32_t num_agents, int64_t games_num, float* __restrict__ cur_reward,
+// Workgroup (x, y) is chunk x of group y: a workgroup belongs to one group, so the freeze test is uniform in it.
+__global__ __launch_bounds__(kBlock) void play_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t envs_per_group,
+                                                           int32_t parts, int32_t num_agents, int64_t games_num, float* __restrict__ cur_reward,
                                                            int32_t* __restrict__ cur_steps, const ppenv_play_totals* __restrict__ totals,
                                                            ppenv_play_partial* __restrict__ partial) {
     __shared__ ppenv_play_partial wave_part[kWaves];
-    if (pp::play_frozen(totals->games, games_num)) return;       // uniform: the whole grid leaves
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t e = (int32_t)(blockIdx.x * kBlock + tid);
-    ppenv_play_partial acc;
-    pp::play_clear(acc);
-    if (e < num_envs) pp::play_env(e, num_agents, rew, done, cur_reward, cur_steps, acc);
-    wave_merge(acc);
-    if (lane == 0) wave_part[wave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        ppenv_play_partial s = wave_part[0];
-        for (int w = 1; w < kWaves; ++w) pp::play_merge(s, wave_part[w]);
-        partial[blockIdx.x] = s;
-    }
-}
-
-__global__ __launch_bounds__(64) void play_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
-                                                         ppenv_play_totals* __restrict__ totals) {
-    if (pp::play_frozen(totals->games, games_num)) return;       // the same word play_rows_kernel tested: nothing wrote it in between
-    ppenv_play_partial acc;
-    pp::play_clear(acc);
-    for (int32_t b = (int32_t)threadIdx.x; b < parts; b += 64) pp::play_merge(acc, partial[b]);
-    wave_merge(acc);
-    if (threadIdx.x == 0) {
-        ppenv_play_totals t = *totals;
-        pp::play_totals_add(t, acc);
-        *totals = t;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void play_reset_kernel(int32_t num_envs, int32_t rows, float* __restrict__ cur_reward, int32_t* __restrict__ cur_steps,
-                                                            ppenv_play_totals* __restrict__ totals) {
-    const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
-    if (i < rows) cur_reward[i] = 0.0f;
-    if (i < num_envs) cur_steps[i] = 0;
-    if (i == 0) {
-        ppenv_play_totals t;
-        pp::play_totals_clear(t);
-        *totals = t;
-    }
-}
-
-bool sizes_ok(int32_t num_envs, int32_t num_agents) {
-    return num_envs > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS && (int64_t)num_envs * num_agents <= INT32_MAX;
-}
-
-}  // namespace
-
-extern "C" size_t ppenv_play_partial_bytes(int32_t num_envs) {
-    return num_envs > 0 ? (size_t)blocks_of(num_envs) * sizeof(ppenv_play_partial) : 0;
-}
-
-extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
-    if (!sizes_ok(num_envs, num_agents) || !cur_reward || !cur_steps || !totals) {
-        ppenv_set_error("ppenv_play_reset: NULL pointer, num_envs <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
-        return PPENV_EINVAL;
-    }
-    const int32_t rows = num_envs * num_agents;
-    hipLaunchKernelGGL(play_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, cur_reward, cur_steps, totals);
-    return pp_launched("launching play_reset_kernel failed");
-}
-
-extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int32_t num_envs, int32_t num_agents, int64_t games_num, float* cur_reward,
-                                     int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
-    if (!sizes_ok(num_envs, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
-        ppenv_set_error("ppenv_play_accumulate: NULL pointer, num_envs <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, or games_num < 1");
-        return PPENV_EINVAL;
-    }
-    const int32_t parts = blocks_of(num_envs);
-    hipLaunchKernelGGL(play_rows_kernel, dim3(parts), dim3(kBlock), 0, (hipStream_t)stream, rew, done, num_envs, num_agents, games_num, cur_reward,
-                       cur_steps, totals, partial);
-    if (int rc = pp_launched("launching play_rows_kernel failed")) return rc;
-    hipLaunchKernelGGL(play_totals_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
-    return pp_launched("launching play_totals_kernel failed");
-}
-
-// ---- grouped accounting (include/ppenv_play_group.h): G populations of S envs, each with its own totals and its own freeze ------------
-// The same two launches, whatever G is:
-//   play_group_rows_kernel     workgroup b is chunk b % P of group b / P (P = chunks of 256 envs in S, counted from the group's first env,
-//                              ragged last chunk per group): the freeze test on totals[g] is uniform in the workgroup, and lane / wave /
-//                              chunk of an env are the ones play_rows_kernel gives it in a run of S envs — the same sums, bit for bit.
-//   play_group_totals_kernel   one wave per group: play_totals_kernel on the group's P partials and totals[g].
-// Wave g of the second launch reads and writes totals[g] alone; the first launch writes no totals.
-namespace {
-
-__global__ __launch_bounds__(kBlock) void play_group_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t envs_per_group,
-                                                                 int32_t parts, int32_t num_agents, int64_t games_num, float* __restrict__ cur_reward,
-                                                                 int32_t* __restrict__ cur_steps, const ppenv_play_totals* __restrict__ totals,
-                                                                 ppenv_play_partial* __restrict__ partial) {
-    __shared__ ppenv_play_partial wave_part[kWaves];
-    const int32_t g = (int32_t)blockIdx.x / parts, chunk = (int32_t)blockIdx.x - g * parts;
+    const int32_t g = (int32_t)blockIdx.y, chunk = (int32_t)blockIdx.x;
     if (pp::play_frozen(totals[g].games, games_num)) return;     // uniform: the whole workgroup leaves (its partial is not read either)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int32_t local = chunk * kBlock + tid;                  // the env's index within its group
@@ -154,12 +68,12 @@ __global__ __launch_bounds__(kBlock) void play_group_rows_kernel(const float* __
     if (tid == 0) {
         ppenv_play_partial s = wave_part[0];
         for (int w = 1; w < kWaves; ++w) pp::play_merge(s, wave_part[w]);
-        partial[blockIdx.x] = s;
+        partial[g * parts + chunk] = s;
     }
 }
 
-__global__ __launch_bounds__(64) void play_group_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
-                                                               ppenv_play_totals* __restrict__ totals) {
+__global__ __launch_bounds__(64) void play_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
+                                                         ppenv_play_totals* __restrict__ totals) {
     const int32_t g = (int32_t)blockIdx.x;
     if (pp::play_frozen(totals[g].games, games_num)) return;     // the word the group's chunks tested: nothing wrote it in between
     const ppenv_play_partial* mine = partial + (size_t)g * parts;
@@ -174,8 +88,8 @@ __global__ __launch_bounds__(64) void play_group_totals_kernel(const ppenv_play_
     }
 }
 
-__global__ __launch_bounds__(kBlock) void play_group_reset_kernel(int32_t num_envs, int32_t rows, int32_t groups, float* __restrict__ cur_reward,
-                                                                  int32_t* __restrict__ cur_steps, ppenv_play_totals* __restrict__ totals) {
+__global__ __launch_bounds__(kBlock) void play_reset_kernel(int32_t num_envs, int32_t rows, int32_t groups, float* __restrict__ cur_reward,
+                                                            int32_t* __restrict__ cur_steps, ppenv_play_totals* __restrict__ totals) {
     const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (i < rows) cur_reward[i] = 0.0f;
     if (i < num_envs) cur_steps[i] = 0;
@@ -186,40 +100,73 @@ __global__ __launch_bounds__(kBlock) void play_group_reset_kernel(int32_t num_en
     }
 }
 
-bool group_sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents) {
+// What both pairs of entries require of the sizes; the plain ones are groups = 1 and have no group bound to break.
+bool sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents) {
     return groups >= 1 && groups <= PP_PLAY_GROUP_MAX && envs_per_group > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS &&
            (int64_t)envs_per_group * groups * num_agents <= INT32_MAX;
 }
 
+// The launches, after the entry's own validation.
+int launch_reset(int32_t envs_per_group, int32_t groups, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
+    const int32_t num_envs = envs_per_group * groups, rows = num_envs * num_agents;
+    hipLaunchKernelGGL(play_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, groups, cur_reward, cur_steps, totals);
+    return pp_launched("launching play_reset_kernel failed");
+}
+
+int launch_accumulate(const float* rew, const int64_t* done, int32_t envs_per_group, int32_t groups, int32_t num_agents, int64_t games_num, float* cur_reward,
+                      int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
+    const int32_t parts = blocks_of(envs_per_group);             // per group; groups * parts <= 2^31 / 256 workgroups
+    hipLaunchKernelGGL(play_rows_kernel, dim3((uint32_t)parts, (uint32_t)groups), dim3(kBlock), 0, (hipStream_t)stream, rew, done, envs_per_group, parts,
+                       num_agents, games_num, cur_reward, cur_steps, totals, partial);
+    if (int rc = pp_launched("launching play_rows_kernel failed")) return rc;
+    hipLaunchKernelGGL(play_totals_kernel, dim3(groups), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
+    return pp_launched("launching play_totals_kernel failed");
+}
+
 }  // namespace
 
+// ---- the plain entries (include/ppenv_play.h): one population, the G = 1 case ------------------------------------------------------------
+extern "C" size_t ppenv_play_partial_bytes(int32_t num_envs) {
+    return num_envs > 0 ? (size_t)blocks_of(num_envs) * sizeof(ppenv_play_partial) : 0;
+}
+
+extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
+    if (!sizes_ok(num_envs, 1, num_agents) || !cur_reward || !cur_steps || !totals) {
+        ppenv_set_error("ppenv_play_reset: NULL pointer, num_envs <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
+        return PPENV_EINVAL;
+    }
+    return launch_reset(num_envs, 1, num_agents, cur_reward, cur_steps, totals, stream);
+}
+
+extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int32_t num_envs, int32_t num_agents, int64_t games_num, float* cur_reward,
+                                     int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
+    if (!sizes_ok(num_envs, 1, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+        ppenv_set_error("ppenv_play_accumulate: NULL pointer, num_envs <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, or games_num < 1");
+        return PPENV_EINVAL;
+    }
+    return launch_accumulate(rew, done, num_envs, 1, num_agents, games_num, cur_reward, cur_steps, totals, partial, stream);
+}
+
+// ---- the grouped entries (include/ppenv_play_group.h): G populations of S envs, each with its own totals and its own freeze -------------
 extern "C" size_t pp_play_group_partial_bytes(int32_t envs_per_group, int32_t groups) {
-    return group_sizes_ok(envs_per_group, groups, 1) ? (size_t)groups * (size_t)blocks_of(envs_per_group) * sizeof(ppenv_play_partial) : 0;
+    return sizes_ok(envs_per_group, groups, 1) ? (size_t)groups * (size_t)blocks_of(envs_per_group) * sizeof(ppenv_play_partial) : 0;
 }
 
 extern "C" int pp_play_group_reset(int32_t envs_per_group, int32_t groups, int32_t num_agents, float* cur_reward, int32_t* cur_steps,
                                    ppenv_play_totals* totals, void* stream) {
-    if (!group_sizes_ok(envs_per_group, groups, num_agents) || !cur_reward || !cur_steps || !totals) {
+    if (!sizes_ok(envs_per_group, groups, num_agents) || !cur_reward || !cur_steps || !totals) {
         ppenv_set_error("pp_play_group_reset: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
         return PPENV_EINVAL;
     }
-    const int32_t num_envs = envs_per_group * groups, rows = num_envs * num_agents;
-    hipLaunchKernelGGL(play_group_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, groups, cur_reward, cur_steps,
-                       totals);
-    return pp_launched("launching play_group_reset_kernel failed");
+    return launch_reset(envs_per_group, groups, num_agents, cur_reward, cur_steps, totals, stream);
 }
 
 extern "C" int pp_play_group_accumulate(const float* rew, const int64_t* done, int32_t envs_per_group, int32_t groups, int32_t num_agents, int64_t games_num,
                                         float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
-    if (!group_sizes_ok(envs_per_group, groups, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+    if (!sizes_ok(envs_per_group, groups, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
         ppenv_set_error("pp_play_group_accumulate: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, "
                         "or games_num < 1");
         return PPENV_EINVAL;
     }
-    const int32_t parts = blocks_of(envs_per_group);             // per group; groups * parts <= 2^31 / 256 workgroups
-    hipLaunchKernelGGL(play_group_rows_kernel, dim3((uint32_t)groups * (uint32_t)parts), dim3(kBlock), 0, (hipStream_t)stream, rew, done, envs_per_group, parts,
-                       num_agents, games_num, cur_reward, cur_steps, totals, partial);
-    if (int rc = pp_launched("launching play_group_rows_kernel failed")) return rc;
-    hipLaunchKernelGGL(play_group_totals_kernel, dim3(groups), dim3(64), 0, (hipStream_t)stream, partial, parts, games_num, totals);
-    return pp_launched("launching play_group_totals_kernel failed");
+    return launch_accumulate(rew, done, envs_per_group, groups, num_agents, games_num, cur_reward, cur_steps, totals, partial, stream);
 }

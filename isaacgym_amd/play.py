@@ -25,9 +25,10 @@ Sweeps.  `Player(task, policy, sweep=Sweep.grid({"link_mass_scale": [0.7, 1.3], 
 every cell of a grid of physical-parameter scales in ONE pass: the envs are split into G equal groups (group g is envs [g * S, (g + 1) * S)),
 each group runs whole episodes under its cell's per-env tables (the domain-randomisation tables of dr.Randomizable.set_randomization, set before
 the first reset), and `GroupStats` keeps one totals struct and one freeze per group in the same two launches per control step, whatever G
-is (include/ppenv_play_group.h).  Groups see DIFFERENT serves that are identically distributed — the env RNG is keyed by the global env
-id, and there are no common random numbers across groups — which is why every group reports `reward_stderr` = reward_std / sqrt(games):
-two cells differ when their averages differ by more than a few standard errors, not when they differ at all.
+is (include/ppenv_play_group.h; `EpisodeStats` is its one-group case, and `Player.run` is one loop over the per-group totals).  Groups
+see DIFFERENT serves that are identically distributed — the env RNG is keyed by the global env id, and there are no common random numbers
+across groups — which is why every group reports `reward_stderr` = reward_std / sqrt(games): two cells differ when their averages differ
+by more than a few standard errors, not when they differ at all.
 
 Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), serve sweeps, common random
 numbers across groups, per-group outcome counts, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
@@ -98,81 +99,22 @@ def summarize(totals, num_agents=1):
     return out
 
 
-class EpisodeStats:
-    """ppenv_play_accumulate / ppenv_play_reset on torch tensors: `cur_reward` [num_envs * num_agents] f32, `cur_steps` [num_envs] i32 and
-    the totals struct, all on `device`.  Nothing here synchronises except read()."""
-
-    def __init__(self, num_envs, num_agents, games_num, device):
-        self.num_envs, self.num_agents, self.games_num = int(num_envs), int(num_agents), int(games_num)
-        if self.num_envs < 1 or self.num_agents not in (1, 2) or self.games_num < 1:
-            raise ValueError(f"EpisodeStats: num_envs {num_envs} (>= 1), num_agents {num_agents} (1 or 2), games_num {games_num} (>= 1)")
-        self.device = torch.device(device)
-        self.rows = self.num_envs * self.num_agents
-        L = self.L = _lib.lib()
-        dev = self.device
-        self.cur_reward = torch.zeros(self.rows, dtype=torch.float32, device=dev)
-        self.cur_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
-        self._totals = torch.zeros(C.sizeof(PlayTotals), dtype=torch.uint8, device=dev)
-        self._partial = torch.zeros(int(L.ppenv_play_partial_bytes(self.num_envs)), dtype=torch.uint8, device=dev)
-        o = PlayTotals
-        self._counts = self._totals[:o.reward.offset].view(torch.int64)                           # games, steps, launches
-        self._sums = self._totals[o.reward.offset:o.reward_min.offset].view(torch.float64)        # reward[2], reward_sq[2]
-        self._ext = self._totals[o.reward_min.offset:].view(torch.float32)                        # reward_min[2], reward_max[2]
-        self.reset()
-
-    def reset(self):
-        _lib.check(self.L.ppenv_play_reset(self.num_envs, self.num_agents, self.cur_reward.data_ptr(), self.cur_steps.data_ptr(),
-                                           self._totals.data_ptr(), _lib.stream(self.device)), self.L)
-
-    def accumulate(self, rew, done):
-        """One control step, after the env step: rew [rows] f32, done [rows] int64 (VecTask.step's rew_buf / reset_buf, or a [rows] slice
-        of larger buffers), contiguous, on this device.  Two launches, no synchronisation."""
-        if rew.dtype != torch.float32 or done.dtype != torch.int64 or rew.numel() != self.rows or done.numel() != self.rows or \
-                not rew.is_contiguous() or not done.is_contiguous() or rew.device != self.device or done.device != self.device:
-            raise ValueError(f"EpisodeStats.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
-        _lib.check(self.L.ppenv_play_accumulate(rew.data_ptr(), done.data_ptr(), self.num_envs, self.num_agents, self.games_num,
-                                                self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self._totals.data_ptr(),
-                                                self._partial.data_ptr(), _lib.stream(self.device)), self.L)
-
-    def totals(self):
-        """The totals as 0-dim device tensors (views: they change in place with every accumulate): games, steps, launches, agent 0's
-        reward / reward_sq / reward_min / reward_max, and the same four per agent under `per_agent`."""
-        A = MAX_AGENTS
-        agents = [dict(reward=self._sums[a], reward_sq=self._sums[A + a], reward_min=self._ext[a], reward_max=self._ext[A + a])
-                  for a in range(self.num_agents)]
-        return dict(games=self._counts[0], steps=self._counts[1], launches=self._counts[2], per_agent=agents, **agents[0])
-
-    def read(self):
-        """One host copy of the struct (the stream is waited for) -> totals_dict."""
-        raw = self._totals.cpu().numpy().tobytes()
-        return totals_dict(PlayTotals.from_buffer_copy(raw), self.num_agents)
-
-    def state_bytes(self):
-        """cur_reward, cur_steps and the totals as host bytes (the tests compare them)."""
-        return self.cur_reward.cpu().numpy().tobytes(), self.cur_steps.cpu().numpy().tobytes(), self._totals.cpu().numpy().tobytes()
-
-    def latch_outcome(self, live, latched):
-        """pp_ta_outcome_latch (include/ppenv_ta_outcome.h): latched = live (two pp_ta_outcome tensors) while the totals are not frozen.  One
-        launch, before the accumulate of the same control step: `latched` then stops with the totals."""
-        _lib.check(self.L.pp_ta_outcome_latch(live.data_ptr(), self._totals.data_ptr(), self.games_num, latched.data_ptr(), _lib.stream(self.device)),
-                   self.L)
-
-
 MAX_GROUPS = 1024                          # PP_PLAY_GROUP_MAX
 
 
 class GroupStats:
-    """The EpisodeStats of the grouped entries (include/ppenv_play_group.h): `groups` populations of `envs_per_group` envs, group g being
-    envs [g * S, (g + 1) * S) of the task, each with its own totals struct and its own freeze at games_num; two launches per
-    accumulate whatever the group count.  Group g's totals and its slices of cur_reward / cur_steps are byte for byte those of an
-    EpisodeStats(envs_per_group, num_agents, games_num) fed the group's slices.  Nothing here synchronises except read()."""
+    """pp_play_group_accumulate / pp_play_group_reset (include/ppenv_play_group.h) on torch tensors: `groups` populations of
+    `envs_per_group` envs, group g being envs [g * S, (g + 1) * S) of the task, each with its own totals struct and its own freeze at
+    games_num; `cur_reward` [num_envs * num_agents] f32, `cur_steps` [num_envs] i32 and the `groups` totals structs, all on `device`; two
+    launches per accumulate whatever the group count.  Group g's totals and its slices of cur_reward / cur_steps are byte for byte those of
+    an EpisodeStats(envs_per_group, num_agents, games_num) fed the group's slices.  Nothing here synchronises except read()."""
 
     def __init__(self, envs_per_group, groups, num_agents, games_num, device):
         self.envs_per_group, self.groups, self.num_agents, self.games_num = int(envs_per_group), int(groups), int(num_agents), int(games_num)
         if self.envs_per_group < 1 or not 1 <= self.groups <= MAX_GROUPS or self.num_agents not in (1, 2) or self.games_num < 1 or \
                 self.envs_per_group * self.groups * self.num_agents > 2 ** 31 - 1:
-            raise ValueError(f"GroupStats: envs_per_group {envs_per_group} (>= 1), groups {groups} (1..{MAX_GROUPS}), num_agents {num_agents} (1 or 2), "
-                             f"games_num {games_num} (>= 1), at most 2^31 - 1 rows")
+            raise ValueError(f"{type(self).__name__}: envs_per_group {envs_per_group} (>= 1), groups {groups} (1..{MAX_GROUPS}), num_agents {num_agents} "
+                             f"(1 or 2), games_num {games_num} (>= 1), at most 2^31 - 1 rows")
         self.device = torch.device(device)
         self.num_envs = self.envs_per_group * self.groups
         self.rows = self.num_envs * self.num_agents
@@ -189,22 +131,24 @@ class GroupStats:
                                               self._totals.data_ptr(), _lib.stream(self.device)), self.L)
 
     def accumulate(self, rew, done):
-        """One control step of every group, after the env step: rew [rows] f32, done [rows] int64 (all groups' rows, in env order),
-        contiguous, on this device.  Two launches, no synchronisation."""
+        """One control step of every group, after the env step: rew [rows] f32, done [rows] int64 (VecTask.step's rew_buf / reset_buf — all
+        groups' rows, in env order — or a [rows] slice of larger buffers), contiguous, on this device.  Two launches, no synchronisation."""
         if rew.dtype != torch.float32 or done.dtype != torch.int64 or rew.numel() != self.rows or done.numel() != self.rows or \
                 not rew.is_contiguous() or not done.is_contiguous() or rew.device != self.device or done.device != self.device:
-            raise ValueError(f"GroupStats.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
+            raise ValueError(f"{type(self).__name__}.accumulate: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
         _lib.check(self.L.pp_play_group_accumulate(rew.data_ptr(), done.data_ptr(), self.envs_per_group, self.groups, self.num_agents, self.games_num,
                                                    self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self._totals.data_ptr(),
                                                    self._partial.data_ptr(), _lib.stream(self.device)), self.L)
 
-    def read(self):
+    def read_groups(self):
         """One host copy of the `groups` structs (groups x 72 bytes; the stream is waited for) -> a list of totals_dict, in group order."""
         raw, n = self._totals.cpu().numpy().tobytes(), C.sizeof(PlayTotals)
         return [totals_dict(PlayTotals.from_buffer_copy(raw[g * n:(g + 1) * n]), self.num_agents) for g in range(self.groups)]
 
+    read = read_groups
+
     def state_bytes(self):
-        """cur_reward, cur_steps and the `groups` totals structs as host bytes."""
+        """cur_reward, cur_steps and the `groups` totals structs as host bytes (the tests compare them)."""
         return self.cur_reward.cpu().numpy().tobytes(), self.cur_steps.cpu().numpy().tobytes(), self._totals.cpu().numpy().tobytes()
 
     def group_state_bytes(self, g):
@@ -212,6 +156,38 @@ class GroupStats:
         cr, cs, tot = self.state_bytes()
         S, A, n = self.envs_per_group, self.num_agents, C.sizeof(PlayTotals)
         return cr[4 * A * S * g:4 * A * S * (g + 1)], cs[4 * S * g:4 * S * (g + 1)], tot[n * g:n * (g + 1)]
+
+
+class EpisodeStats(GroupStats):
+    """The accounting of one population: GroupStats with one group of num_envs envs — the same kernels, the same bytes — whose read() is
+    the one totals dict, plus the device views of the one struct and the outcome latch that follows its freeze."""
+
+    def __init__(self, num_envs, num_agents, games_num, device):
+        if int(num_envs) < 1 or int(num_agents) not in (1, 2) or int(games_num) < 1:
+            raise ValueError(f"EpisodeStats: num_envs {num_envs} (>= 1), num_agents {num_agents} (1 or 2), games_num {games_num} (>= 1)")
+        super().__init__(num_envs, 1, num_agents, games_num, device)
+        o = PlayTotals
+        self._counts = self._totals[:o.reward.offset].view(torch.int64)                           # games, steps, launches
+        self._sums = self._totals[o.reward.offset:o.reward_min.offset].view(torch.float64)        # reward[2], reward_sq[2]
+        self._ext = self._totals[o.reward_min.offset:].view(torch.float32)                        # reward_min[2], reward_max[2]
+
+    def totals(self):
+        """The totals as 0-dim device tensors (views: they change in place with every accumulate): games, steps, launches, agent 0's
+        reward / reward_sq / reward_min / reward_max, and the same four per agent under `per_agent`."""
+        A = MAX_AGENTS
+        agents = [dict(reward=self._sums[a], reward_sq=self._sums[A + a], reward_min=self._ext[a], reward_max=self._ext[A + a])
+                  for a in range(self.num_agents)]
+        return dict(games=self._counts[0], steps=self._counts[1], launches=self._counts[2], per_agent=agents, **agents[0])
+
+    def read(self):
+        """One host copy of the struct (the stream is waited for) -> totals_dict."""
+        return self.read_groups()[0]
+
+    def latch_outcome(self, live, latched):
+        """pp_ta_outcome_latch (include/ppenv_ta_outcome.h): latched = live (two pp_ta_outcome tensors) while the totals are not frozen.  One
+        launch, before the accumulate of the same control step: `latched` then stops with the totals."""
+        _lib.check(self.L.pp_ta_outcome_latch(live.data_ptr(), self._totals.data_ptr(), self.games_num, latched.data_ptr(), _lib.stream(self.device)),
+                   self.L)
 
 
 _AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
@@ -465,53 +441,25 @@ class Player:
         host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds); with
         outcomes=True also `outcomes` (outcomes_dict of the latched struct).  With a sweep: until EVERY group has counted games_num games;
         on_poll gets the groups' totals summed (sum_totals), the result is summarize() of that sum plus `groups`."""
-        if self.sweep is not None:
-            return self._run_sweep(on_poll)
-        self.start()
-        t0 = time.perf_counter()
-        tot = None
-        while self.steps_played < self.max_steps:
-            self.step()
-            tot = None
-            if self.steps_played % self.poll_every == 0:
-                tot = self.stats.read()
-                if on_poll is not None:
-                    on_poll(tot)
-                if tot["games"] >= self.games_num:
-                    break
-        if tot is None:
-            tot = self.stats.read()
-            if on_poll is not None:
-                on_poll(tot)
-        out = summarize(tot, self.num_agents)
-        out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
-        if self.outcome is not None:
-            out["outcomes"] = self.read_outcomes()
-        if self.recorder is not None:
-            out["captured_frames"] = self.recorder.captured
-        return out
-
-    def _run_sweep(self, on_poll):
         try:
             self.start()
             t0 = time.perf_counter()
-            per = None
-            while self.steps_played < self.max_steps:
+            while True:
                 self.step()
-                per = None
-                if self.steps_played % self.poll_every == 0:
-                    per = self.stats.read()
+                last = self.steps_played >= self.max_steps
+                if last or self.steps_played % self.poll_every == 0:
+                    per = self.stats.read_groups()
+                    tot = per[0] if self.sweep is None else sum_totals(per)
                     if on_poll is not None:
-                        on_poll(sum_totals(per))
-                    if all(t["games"] >= self.games_num for t in per):
+                        on_poll(tot)
+                    if last or all(t["games"] >= self.games_num for t in per):
                         break
-            if per is None:
-                per = self.stats.read()
-                if on_poll is not None:
-                    on_poll(sum_totals(per))
-            out = summarize(sum_totals(per), self.num_agents)
+            out = summarize(tot, self.num_agents)
             out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
-            out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num) for cell, t in zip(self.sweep.cells, per)]
+            if self.sweep is not None:
+                out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num) for cell, t in zip(self.sweep.cells, per)]
+            if self.outcome is not None:
+                out["outcomes"] = self.read_outcomes()
             if self.recorder is not None:
                 out["captured_frames"] = self.recorder.captured
             return out

@@ -2,8 +2,13 @@
 rl_games' loop on recorded sequences, the freeze, and the Player against the test's own host-synchronised rl_games-style loop (`.nonzero()`
 every step) on a second task built with the same seed — plain, under reset-time randomisation, on the 27-dof and the 4-actor task,
 with different polling intervals, stochastic, and through the CLI.  Bounds: tests/test_play_host.py's (integers, cur_reward and the
-extrema equal; a fp64 sum of `count` games within count x 2^-53 x sum|x| of the exact sum; integer rewards: equal).  The tasks run with
-env.episodeLength 12, so games finish within tens of steps.  Need a real MI355X."""
+extrema equal; a fp64 sum of `count` games within count x 2^-53 x sum|x| of the exact sum; integer rewards: equal); on float rewards the
+sum order itself is held by the recorded digests of tests/golden/play_state_digests.json.  The tasks run with env.episodeLength 12, so
+games finish within tens of steps.  Need a real MI355X."""
+import importlib.util
+import json
+import os
+
 import numpy as np
 import pytest
 
@@ -102,6 +107,66 @@ def test_accumulate_refuses_wrong_tensors(torch_cuda):
     for bad_r, bad_d in ((r[:8], d), (r, d.int()), (r.double(), d), (torch.zeros(32, device=DEV)[::2], d), (r.cpu(), d)):
         with pytest.raises(ValueError, match="accumulate"):
             st.accumulate(bad_r, bad_d)
+
+
+# ------------------------------------------------------------------------------------------------------- the recorded bits
+_TESTS = os.path.dirname(os.path.abspath(__file__))
+DIRECT = [(1, 65), (2, 129), (1, 257)]                   # shapes at which the plain C entries are driven as well
+
+
+@pytest.fixture(scope="module")
+def digests():
+    """(tools/play_state_digests.py as a module, the recorded cases of tests/golden/play_state_digests.json, its cases() by key)."""
+    spec = importlib.util.spec_from_file_location("play_state_digests", os.path.join(_TESTS, "..", "tools", "play_state_digests.py"))
+    tool = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(tool)
+    with open(os.path.join(_TESTS, "golden", "play_state_digests.json")) as fh:
+        recorded = json.load(fh)
+    cases = {key: (num_agents, num_envs, games_num, rews, dones) for key, num_agents, num_envs, games_num, rews, dones in tool.cases()}
+    assert recorded["steps"] == STEPS and set(recorded["cases"]) == set(cases) and len(cases) == 2 * (len(SHAPES) + 2)
+    return tool, recorded["cases"], cases
+
+
+class PlainEntries:
+    """ppenv_play_reset / ppenv_play_accumulate on the test's own tensors, with accumulate() and state_bytes() as EpisodeStats has them."""
+
+    def __init__(self, torch, num_envs, num_agents, games_num):
+        from isaacgym_amd import _lib
+        self.check, self.L, self.stream = _lib.check, _lib.lib(), _lib.stream(torch.device(DEV))
+        self.sizes, self.games_num = (num_envs, num_agents), games_num
+        self.cur_reward = torch.full((num_envs * num_agents,), 7.0, dtype=torch.float32, device=DEV)      # garbage: the reset must clear it
+        self.cur_steps = torch.full((num_envs,), 7, dtype=torch.int32, device=DEV)
+        self.totals = torch.full((72,), 0x55, dtype=torch.uint8, device=DEV)
+        self.partial = torch.zeros(self.L.ppenv_play_partial_bytes(num_envs), dtype=torch.uint8, device=DEV)
+        self.check(self.L.ppenv_play_reset(*self.sizes, self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self.totals.data_ptr(), self.stream), self.L)
+
+    def accumulate(self, rew, done):
+        assert rew.is_contiguous() and done.is_contiguous() and rew.numel() == done.numel() == self.cur_reward.numel()
+        self.check(self.L.ppenv_play_accumulate(rew.data_ptr(), done.data_ptr(), *self.sizes, self.games_num, self.cur_reward.data_ptr(),
+                                                self.cur_steps.data_ptr(), self.totals.data_ptr(), self.partial.data_ptr(), self.stream), self.L)
+
+    def state_bytes(self):
+        return tuple(t.cpu().numpy().tobytes() for t in (self.cur_reward, self.cur_steps, self.totals))
+
+
+@pytest.mark.parametrize("num_agents,num_envs", SHAPES + [(1, 1000), (2, 1000)])
+def test_state_digests_are_the_recorded_ones(torch_cuda, digests, num_agents, num_envs):
+    """Float rewards, never frozen and frozen half-way: sha256 of cur_reward, cur_steps and the totals after STEPS steps equal the digests
+    recorded on an MI355X from the commit that still had a kernel family of its own for the single accounting.  EpisodeStats (the grouped
+    entries with one group) and, at DIRECT, the plain C entries.  A digest that differs means the fp64 sum order moved: the file stays."""
+    torch = torch_cuda
+    from isaacgym_amd.play import EpisodeStats
+    tool, recorded, cases = digests
+    for name in ("never", "freeze"):
+        key = f"{num_agents}x{num_envs}_{name}"
+        A, N, games_num, rews, dones = cases[key]
+        assert (A, N, games_num) == (num_agents, num_envs, recorded[key]["games_num"]), key
+        want = {part: recorded[key][part] for part in tool.PARTS}
+        st = EpisodeStats(num_envs, num_agents, games_num, DEV)
+        assert tool.play(torch, st, rews, dones) == want, f"{key}: EpisodeStats"
+        assert (st.read()["launches"] < STEPS) == (name == "freeze"), key                   # the freeze fell inside the run
+        if (num_agents, num_envs) in DIRECT:
+            assert tool.play(torch, PlainEntries(torch, num_envs, num_agents, games_num), rews, dones) == want, f"{key}: the plain C entries"
 
 
 # ------------------------------------------------------------------------------------------------------- the Player

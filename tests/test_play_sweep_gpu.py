@@ -1,9 +1,9 @@
 """Sweeping physical parameters across env groups on the MI355X (isaacgym_amd.play: GroupStats, Player(sweep=); include/ppenv_play_group.h).
 
-The kernels: group g's totals, cur_reward and cur_steps must be BYTE FOR BYTE what the single accounting (EpisodeStats: ppenv_play_reset /
-ppenv_play_accumulate, pinned by tests/test_play_gpu.py against its host build and rl_games' loop) leaves on the same device when it is
-given the group's S envs and the group's slices of the recorded sequences — never frozen, and with a games_num the groups reach at
-different steps.  No tolerance anywhere: the sums have the same order.  The Player: the swept run against the test's own loop on a second
+The kernels: group g's totals, cur_reward and cur_steps must be BYTE FOR BYTE what the single accounting (EpisodeStats: the same kernels
+with one group, pinned by tests/test_play_gpu.py against its host build, rl_games' loop and the recorded digests) leaves on the same
+device when it is given the group's S envs and the group's slices of the recorded sequences — never frozen, and with a games_num the
+groups reach at different steps: a check of the group indexing.  No tolerance anywhere: the sums have the same order.  The Player: the swept run against the test's own loop on a second
 task of the same seed, which sets the same tables through task.env.set_randomization and feeds one EpisodeStats per group the slices.
 The tasks run with env.episodeLength 12.  Need a real MI355X."""
 import json
