@@ -9,7 +9,7 @@
  * Two launches per picture:
  *   pp_render_pose   render_pose_kernel: one workgroup per selected env, lane p places primitive p in world space and writes
  *                    posed[E][P] to global memory (callers and tests can read it).
- *   pp_render_rays   render_rays_kernel: grid = image tiles x selected envs, a 16 x 16 pixel tile per 256-lane workgroup (a wave
+ *   pp_render_rays   render_rays_kernel<1>: grid = image tiles x selected envs, a 16 x 16 pixel tile per 256-lane workgroup (a wave
  *                    owns a 16 x 4 strip).  The workgroup copies its env's posed primitives into LDS; every lane intersects its
  *                    ray with all of them and the ground plane, keeps the nearest hit, shades
  *                        albedo * (ambient + diffuse * max(n . l, 0) * shadow)
@@ -20,16 +20,16 @@
  *                    i, j = 0 .. s - 1, s = `samples` = 1, 2 or 4.  Each ray is shaded as above and its three channels are clamped to [0, 1];
  *                    the s^2 colours are added in ONE fixed order (a binary tree over k = j * s + i: ppenv_render_device.h,
  *                    render_aa_tree_sum), the sum is multiplied by the exact 1 / s^2 and channel = (int)(255 v + 0.5), alpha 255.
- *                    render_rays_aa_kernel: the same workgroup over a 16 x 16 tile of SUB-SAMPLES — s^2 consecutive lanes own a pixel, one
+ *                    render_rays_kernel<s>: the same workgroup over a 16 x 16 tile of SUB-SAMPLES — s^2 consecutive lanes own a pixel, one
  *                    ray each, added across lanes in that order; the pixel's first lane stores the 4 bytes.  samples = 1 launches
- *                    render_rays_kernel itself: the bytes of pp_render_rays.  RGBA only: a mean of depths or ids has no meaning.
+ *                    render_rays_kernel<1>: the bytes of pp_render_rays.  RGBA only: a mean of depths or ids has no meaning.
  * A recording (deferred capture): the posed list is a complete, camera-independent description of a frame, 80 bytes per primitive.
- *   pp_render_pose_anchor  instead of pp_render_pose: the same bytes into posed_out[count][P], plus anchor_out[count] as float4 — words 0 .. 2 of
+ *   pp_render_pose_anchor  instead of pp_render_pose (render_pose_kernel with an anchor array): the same bytes into posed_out[count][P], plus anchor_out[count] as float4 — words 0 .. 2 of
  *                    body row `anchor_row` of pose source `anchor_source` of that env, then 0 (zeros for anchor_row < 0 and for an env id out of
  *                    range).  The caller keeps a ring of such slots.
- *   pp_render_rays_frames  posed [F][E][P] + anchor [F][E] -> rgba [F, E, H, W, 4] in ONE launch, grid (image tiles, E, F): per workgroup what
- *                    pp_render_rays (samples 1) / pp_render_rays_aa (2, 4) do for one env of one picture, the same device functions called the
- *                    same way, so frame f is byte for byte the picture those entries draw from posed[f].  The one difference: a following camera
+ *   pp_render_rays_frames  posed [F][E][P] + anchor [F][E] -> rgba [F, E, H, W, 4] in ONE launch of the same render_rays_kernel<s>, grid (image
+ *                    tiles, E, F): per workgroup what pp_render_rays (samples 1) / pp_render_rays_aa (2, 4) do for one env of one picture (their
+ *                    grid is this one with F = 1), so frame f is byte for byte the picture those entries draw from posed[f].  The one difference: a following camera
  *                    (follow_row >= 0; follow_source is ignored) adds (anchor.x, anchor.y, 0) of that frame and env.  The scene's source[] is never
  *                    read and may be empty (num_sources 0): a replay has no task.  RGBA only.
  * Images are [E, H, W, 4] uint8; the optional outputs are [E, H, W] fp32 depth (distance along the ray, +inf for sky) and int32

@@ -113,6 +113,18 @@ def body_poses(robot, root_pos, root_quat, dof_pos=None):
     return np.stack([np.concatenate([pose[n][0], _rot_to_quat(pose[n][1])]) for n in urdf.G1_BODY_NAMES])
 
 
+def scene_header(num_envs, num_prims, sources, c):
+    """pp_render_scene: `sources` [(address, env stride, row stride, rows)] in floats; c: {name: value or array} of the header's constants."""
+    h = RenderScene()
+    h.num_envs, h.num_prims, h.num_sources, h.checker = int(num_envs), int(num_prims), len(sources), int(c["checker"])
+    for s, (base, es, rs, rows) in zip(h.source, sources):
+        s.base, s.env_stride, s.row_stride, s.rows = base, es, rs, rows
+    h.ground_z, h.checker_pitch, h.ambient, h.diffuse = (float(c[k]) for k in ("ground_z", "checker_pitch", "ambient", "diffuse"))
+    h.ground_rgb[0][:], h.ground_rgb[1][:] = ([float(v) for v in rgb] for rgb in c["ground_rgb"])
+    h.sky_rgb[:], h.light[:] = [float(v) for v in c["sky_rgb"]], [float(v) for v in c["light"]]
+    return h
+
+
 class Scene:
     """The primitives of one task's scene (host data) and, after from_task, their device copy and pose sources."""
 
@@ -147,9 +159,7 @@ class Scene:
         table, ball = scene.asset_geometry(cfg["scene"])
         if v == "TA":
             c = scene.build_ta_scene(1, table=table, ball=ball)
-            env_keys = ("episodeLength", "alphaVelocityReward", "powerCoefficient", "hitTableReward", "nothitTablePenalty", "crossNetRewardFloat",
-                        "diePenaltyFloat", "hitPaddleReward", "missPaddlePenaltyCoefficient")
-            params = scene.build_ta_params(1, env={k: cfg["env"][k] for k in env_keys if k in cfg["env"]})
+            params = scene.build_ta_params(1, env={k: cfg["env"][k] for k in scene.TA_ENV_KEYS if k in cfg["env"]})
             model = scene.build_ta_model()
             link_row = [urdf.G1_BODY_NAMES.index(n) for n in TA_LINK_NAMES]
             assert link_row == [model.link[i].body for i in range(scene.TA_NUM_LINKS)], "TA_LINK_NAMES does not follow scene.build_ta_model"
@@ -225,16 +235,7 @@ class Scene:
 
     def header_for(self, num_envs, sources):
         """pp_render_scene for pose tensors `sources`: [(address, env stride, row stride, rows)] in floats."""
-        h = RenderScene()
-        h.num_envs, h.num_prims, h.num_sources, h.checker = int(num_envs), len(self.prims), len(sources), int(self.checker)
-        for s, (base, es, rs, rows) in zip(h.source, sources):
-            s.base, s.env_stride, s.row_stride, s.rows = base, es, rs, rows
-        h.ground_z, h.checker_pitch = self.ground_z, self.checker_pitch
-        for k in range(2):
-            h.ground_rgb[k][:] = self.ground_rgb[k]
-        h.sky_rgb[:], h.light[:] = self.sky_rgb, self.light
-        h.ambient, h.diffuse = self.ambient, self.diffuse
-        return h
+        return scene_header(num_envs, len(self.prims), sources, vars(self))
 
     # ---- device
     @classmethod
@@ -323,11 +324,9 @@ class Camera:
 class Renderer:
     def __init__(self, task, envs=(0,), width=640, height=480, camera=None, depth=False, ids=False, samples=1):
         import torch
-        if samples not in (1, 2, 4):
-            raise ValueError(f"Renderer: samples (sub-samples per axis) must be 1, 2 or 4, got {samples!r}")
-        if samples > 1 and (depth or ids):
+        self.samples = _samples_ok("Renderer", samples)
+        if self.samples > 1 and (depth or ids):
             raise ValueError("Renderer: depth and ids need samples=1: a mean of depths or ids has no meaning")
-        self.samples = int(samples)
         envs = [int(e) for e in envs]
         if not 1 <= len(envs) <= RENDER_MAX_ENVS or min(envs) < 0 or max(envs) >= task.num_envs:
             raise ValueError(f"Renderer: 1 .. {RENDER_MAX_ENVS} env ids inside [0, {task.num_envs}), got {envs}")
@@ -372,6 +371,34 @@ def ring_schedule(calls, length, every):
     return len(rendered), rendered[-length:]
 
 
+class _Ring:
+    """The call arithmetic of Recorder and Trajectory, once (ring_schedule restates it): capture() call k (0-based) draws when k % every == 0, the
+    n-th drawn call into slot n % length; the kept slots are handed out oldest first."""
+
+    def __init__(self, who, length, every):
+        if int(length) < 1 or int(every) < 1:
+            raise ValueError(f"{who}: length {length} and every {every} must be positive")
+        self.length, self.every = int(length), int(every)
+        self.reset()
+
+    def reset(self, base=0):                  # the next capture() is call 0, control step `base`
+        self.calls, self.captured, self.base = 0, 0, int(base)
+
+    def step(self, draw):
+        """One capture() call: draw(slot) when it is a drawn one."""
+        if self.calls % self.every == 0:
+            draw(self.captured % self.length)
+            self.captured += 1
+        self.calls += 1
+
+    def oldest_first(self, slots):
+        """A tensor or a list over the slots -> its kept entries, oldest first: T = min(captured, length) of them."""
+        at = self.captured % self.length
+        if self.captured <= self.length:
+            return slots[:self.captured]
+        return slots[at:] + slots[:at] if isinstance(slots, list) else slots.roll(-at, 0) if at else slots
+
+
 class Recorder:
     """The last `length` rendered frames in a device ring [length, E, H, W, 4]; capture() once per control step renders every `every`-th call.
     deferred=True: capture() records into a Trajectory (`.trajectory`; None when eager) instead of casting rays, and frames() / save() first
@@ -379,33 +406,29 @@ class Recorder:
 
     def __init__(self, renderer, length=100, every=1, deferred=False):
         import torch
-        if int(length) < 1 or int(every) < 1:
-            raise ValueError(f"Recorder: length {length} and every {every} must be positive")
-        self.renderer, self.length, self.every = renderer, int(length), int(every)
+        own = _Ring("Recorder", length, every)
+        self.renderer, self.length, self.every = renderer, own.length, own.every
         nbytes = self.length * renderer.rgba.numel()
         if nbytes > MAX_RING_BYTES:
             raise ValueError(f"Recorder: a ring of {self.length} frames of {tuple(renderer.rgba.shape)} is {nbytes} bytes, more than "
                              f"{MAX_RING_BYTES} (2 GiB): shorten it, pick fewer envs or a smaller picture")
         self.ring = torch.zeros((self.length,) + tuple(renderer.rgba.shape), dtype=torch.uint8, device=renderer.device)
-        self.calls = self.captured = 0
         self.trajectory = Trajectory(renderer, self.length, self.every) if deferred else None
+        self._count = self.trajectory if deferred else own       # whose calls / captured these are
         self._drawn = 0                       # deferred: captured frames whose rays have been cast
+
+    calls = property(lambda self: self._count.calls)
+    captured = property(lambda self: self._count.captured)
 
     def reset(self, base=0):
         """Forget the frames: the next capture() is call 0 (a deferred recording numbers its steps from `base`)."""
-        self.calls = self.captured = self._drawn = 0
-        if self.trajectory is not None:
-            self.trajectory.reset(base)
+        self._drawn = 0
+        self._count.reset(base)
 
     def capture(self):
         if self.trajectory is not None:
-            self.trajectory.capture()
-            self.calls, self.captured = self.trajectory.calls, self.trajectory.captured
-            return
-        if self.calls % self.every == 0:
-            self.renderer.render(out=self.ring[self.captured % self.length])
-            self.captured += 1
-        self.calls += 1
+            return self.trajectory.capture()
+        self._count.step(lambda slot: self.renderer.render(out=self.ring[slot]))
 
     def flush(self):
         """Deferred: cast the rays of the captured frames not yet drawn into their ring slots (launches only; at most two slot ranges)."""
@@ -422,10 +445,7 @@ class Recorder:
     def frames(self):
         """The kept frames, oldest first: [T, E, H, W, 4] on the device, T = min(captured, length)."""
         self.flush()
-        if self.captured <= self.length:
-            return self.ring[:self.captured]
-        at = self.captured % self.length
-        return self.ring.roll(-at, 0) if at else self.ring
+        return self._count.oldest_first(self.ring)
 
     def save(self, path, fps=30):
         """The one host copy.  Envs side by side; *.gif (one file), *.png (numbered files <stem>_0000.png ...) through PIL, *.npy
@@ -463,68 +483,58 @@ def _frames_out(who, T, E, width, height, device):
     return torch.zeros((T, E, height, width, 4), dtype=torch.uint8, device=device)
 
 
+def _render_frames(who, L, header, posed, anchor, given, default):
+    """Trajectory.render and Replay.render: the kept frames posed [T, E, P, 20] + anchor [T, E, 4] -> a new uint8 [T, E, H, W, 4] on their device,
+    under (camera, width, height, samples) = `given`, where None `default`."""
+    camera, width, height, samples = (d if g is None else g for g, d in zip(given, default))
+    width, height, samples = int(width), int(height), _samples_ok(who, samples)
+    if width < 1 or height < 1:
+        raise ValueError(f"{who}: width x height must be positive, got {width} x {height}")
+    out = _frames_out(who, int(posed.shape[0]), int(posed.shape[1]), width, height, posed.device)
+    return cast_frames(L, header, camera.struct(width, height), posed.contiguous(), anchor.contiguous(), samples, out) if len(out) else out
+
+
 def _samples_ok(who, samples):
     if samples not in (1, 2, 4):
         raise ValueError(f"{who}: samples (sub-samples per axis) must be 1, 2 or 4, got {samples!r}")
     return int(samples)
 
 
-class Trajectory:
+class Trajectory(_Ring):
     """The posed primitives of the last `length` drawn control steps: a device ring posed [length, E, P, 20] (raw 32-bit words of
     pp_render_posed), anchor [length, E, 4] (x, y, z, 0 of the body a following camera follows) and, on the host, the control-step index of
-    every slot.  capture() has Recorder's call arithmetic (ring_schedule); a drawn call is scene.refresh() + pp_render_pose_anchor.
+    every slot.  capture() has Recorder's call arithmetic (_Ring; ring_schedule); a drawn call is scene.refresh() + pp_render_pose_anchor.
     The anchor is the renderer camera's follow body when it has one, else the first humanoid's root (SRC_ROOT, 0)."""
 
     def __init__(self, renderer, length=100, every=1):
         import torch
-        if int(length) < 1 or int(every) < 1:
-            raise ValueError(f"Trajectory: length {length} and every {every} must be positive")
-        self.renderer, self.length, self.every = renderer, int(length), int(every)
+        super().__init__("Trajectory", length, every)
+        self.renderer = renderer
         E, P = len(renderer.envs), max(len(renderer.scene.prims), 1)
         self.posed = torch.zeros((self.length, E, P, POSED_WORDS), dtype=torch.int32, device=renderer.device)
         self.anchor = torch.zeros((self.length, E, 4), dtype=torch.float32, device=renderer.device)
         self.steps = [0] * self.length
-        self.calls = self.captured = self.base = 0
-
-    def reset(self, base=0):
-        self.calls = self.captured = 0
-        self.base = int(base)
 
     def capture(self):
-        if self.calls % self.every == 0:
-            r = self.renderer
-            sc, slot = r.scene, self.captured % self.length
-            src, row = r.camera.follow if r.camera.follow is not None else (SRC_ROOT, 0)
-            sc.refresh()
-            _lib.check(r.L.pp_render_pose_anchor(C.byref(sc.header), sc.prims_dev.data_ptr(), r.env_ids.data_ptr(), len(r.envs), src, row,
-                                                 self.posed[slot].data_ptr(), self.anchor[slot].data_ptr(), _lib.stream(r.device)), r.L)
-            self.steps[slot] = self.base + self.calls
-            self.captured += 1
-        self.calls += 1
+        self.step(self._record)
+
+    def _record(self, slot):
+        r, sc = self.renderer, self.renderer.scene
+        src, row = r.camera.follow if r.camera.follow is not None else (SRC_ROOT, 0)
+        sc.refresh()
+        _lib.check(r.L.pp_render_pose_anchor(C.byref(sc.header), sc.prims_dev.data_ptr(), r.env_ids.data_ptr(), len(r.envs), src, row,
+                                             self.posed[slot].data_ptr(), self.anchor[slot].data_ptr(), _lib.stream(r.device)), r.L)
+        self.steps[slot] = self.base + self.calls
 
     def frames(self):
         """The kept slots, oldest first: (posed [T, E, P, 20], anchor [T, E, 4], [control-step index] * T), T = min(captured, length)."""
-        if self.captured <= self.length:
-            return self.posed[:self.captured], self.anchor[:self.captured], self.steps[:self.captured]
-        at = self.captured % self.length
-        if not at:
-            return self.posed, self.anchor, list(self.steps)
-        return self.posed.roll(-at, 0), self.anchor.roll(-at, 0), self.steps[at:] + self.steps[:at]
+        return self.oldest_first(self.posed), self.oldest_first(self.anchor), self.oldest_first(self.steps)
 
     def render(self, camera=None, width=None, height=None, samples=None):
         """The kept frames as pictures: uint8 [T, E, H, W, 4] on the device.  The defaults are the renderer's own camera, size and sample
         count: then frame t is byte for byte what Renderer.render() drew (or would have drawn) at that step.  Launches only."""
         r = self.renderer
-        camera = r.camera if camera is None else camera
-        width, height = int(r.width if width is None else width), int(r.height if height is None else height)
-        samples = _samples_ok("Trajectory.render", r.samples if samples is None else samples)
-        if width < 1 or height < 1:
-            raise ValueError(f"Trajectory.render: width x height must be positive, got {width} x {height}")
-        posed, anchor, _ = self.frames()
-        out = _frames_out("Trajectory.render", int(posed.shape[0]), len(r.envs), width, height, r.device)
-        if posed.shape[0]:
-            cast_frames(r.L, r.scene.header, camera.struct(width, height), posed.contiguous(), anchor.contiguous(), samples, out)
-        return out
+        return _render_frames("Trajectory.render", r.L, r.scene.header, *self.frames()[:2], (camera, width, height, samples), (r.camera, r.width, r.height, r.samples))
 
     def constants(self, fps=30):
         """What a file holds besides the frames (host data): the scene header's constants, the recording camera, the side view, the JSON."""
@@ -592,13 +602,7 @@ class Replay:
         self.steps, self.envs = [int(k) for k in data["steps"]], [int(e) for e in data["env_ids"]]
         self.width, self.height, self.samples = (int(v) for v in data["camera_size"])
         self.fps = float(self.meta.get("fps", 30))
-        h = self.header = RenderScene()
-        h.num_envs, h.num_prims, h.num_sources, h.checker = max(self.envs) + 1, int(self.meta["num_prims"]), 0, int(data["checker"])
-        h.ground_z, h.checker_pitch = float(data["ground_z"]), float(data["checker_pitch"])
-        for k in range(2):
-            h.ground_rgb[k][:] = [float(v) for v in data["ground_rgb"][k]]
-        h.sky_rgb[:], h.light[:] = [float(v) for v in data["sky_rgb"]], [float(v) for v in data["light"]]
-        h.ambient, h.diffuse = float(data["ambient"]), float(data["diffuse"])
+        self.header = scene_header(max(self.envs) + 1, self.meta["num_prims"], [], data)
 
     @classmethod
     def load(cls, path, device="cuda:0"):
@@ -617,15 +621,8 @@ class Replay:
 
     def render(self, camera=None, width=None, height=None, samples=None):
         """uint8 [T, E, H, W, 4] on the device; the defaults are the recording's camera, size and sample count."""
-        camera = self.camera() if camera is None else camera
-        width, height = int(self.width if width is None else width), int(self.height if height is None else height)
-        samples = _samples_ok("Replay.render", self.samples if samples is None else samples)
-        if width < 1 or height < 1:
-            raise ValueError(f"Replay.render: width x height must be positive, got {width} x {height}")
-        out = _frames_out("Replay.render", int(self.posed.shape[0]), len(self.envs), width, height, self.device)
-        if self.posed.shape[0]:
-            cast_frames(_lib.lib(), self.header, camera.struct(width, height), self.posed, self.anchor, samples, out)
-        return out
+        return _render_frames("Replay.render", _lib.lib(), self.header, self.posed, self.anchor, (camera, width, height, samples),
+                              (self.camera(), self.width, self.height, self.samples))
 
     def save(self, out, fps=None, **kw):
         """render(**kw) through save_frames -> the files written."""

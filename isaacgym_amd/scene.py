@@ -207,6 +207,11 @@ class TAParams(C.Structure):
     ]
 
 
+# the `env` keys of the 27-dof task's cfg that build_ta_params reads
+TA_ENV_KEYS = ("episodeLength", "alphaVelocityReward", "powerCoefficient", "hitTableReward", "nothitTablePenalty", "crossNetRewardFloat", "diePenaltyFloat",
+               "hitPaddleReward", "missPaddlePenaltyCoefficient")
+
+
 def build_ta_params(num_envs, env=None, seed=0, env_id_offset=0, is_train=True):
     """ppenv_ta_params from the HumanoidPingpongTiltNESSparse27DOFG1.yaml keys (defaults = the yaml's resolve_default values)."""
     e = dict(episodeLength=160, alphaVelocityReward=3000.0, powerCoefficient=0.002, hitTableReward=3000.0, nothitTablePenalty=-1000.0,

@@ -454,9 +454,7 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
 
     def create_sim(self):
         from .tensor_api import TAEnv
-        keys = ("episodeLength", "alphaVelocityReward", "powerCoefficient", "hitTableReward", "nothitTablePenalty", "crossNetRewardFloat",
-                "diePenaltyFloat", "hitPaddleReward", "missPaddlePenaltyCoefficient")
-        env = {k: self.cfg["env"][k] for k in keys if k in self.cfg["env"]}
+        env = {k: self.cfg["env"][k] for k in scene.TA_ENV_KEYS if k in self.cfg["env"]}
         if self.control_freq_inv != 1:
             raise NotImplementedError("controlFrequencyInv != 1 is not wired for the 27-dof task (its yaml has none; "
                                       "cfg/task/HumanoidPingpongTiltNESSparse27DOFG1.yaml)")

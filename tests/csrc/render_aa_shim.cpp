@@ -5,7 +5,7 @@
 
 extern "C" {
 
-// render_rays_aa_kernel on host memory, pixel by pixel: rgba [count, H, W] words.  -> 0, or -1 for samples other than 1, 2, 4
+// render_rays_kernel<S> on host memory, pixel by pixel: rgba [count, H, W] words.  -> 0, or -1 for samples other than 1, 2, 4
 int render_aa_shim_rays(const pp_render_scene* sc, const pp_render_camera* cam, const pp_render_posed* posed, const int32_t* env_ids, int32_t count,
                         int32_t samples, uint32_t* rgba) {
     if (!pp::render_samples_ok(samples)) return -1;

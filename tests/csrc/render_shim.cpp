@@ -20,7 +20,7 @@ void render_shim_pose(const pp_render_scene* sc, const pp_render_prim* prims, co
         }
 }
 
-// render_rays_kernel on host memory, pixel by pixel; shadow / parity [count, H, W] i32 are the shim's own extra outputs (may be NULL)
+// render_rays_kernel<1> on host memory, pixel by pixel; shadow / parity [count, H, W] i32 are the shim's own extra outputs (may be NULL)
 void render_shim_rays(const pp_render_scene* sc, const pp_render_camera* cam, const pp_render_posed* posed, const int32_t* env_ids, int32_t count,
                       uint32_t* rgba, float* depth, int32_t* ids, int32_t* shadow, int32_t* parity) {
     pp::RenderView view;

@@ -1,7 +1,8 @@
 """Pose trajectories on the MI355X (render.Trajectory / Replay / Recorder(deferred=True) / TrainingCapture(deferred=True, trajectories=True);
 pp_render_pose_anchor, pp_render_rays_frames).  The yardstick for every pixel is the eager pair pp_render_pose + pp_render_rays / pp_render_rays_aa
-(pinned by test_render_gpu.py and test_render_aa_gpu.py): every comparison here is torch.equal — the batched kernel calls the same device
-functions on the same posed words, so there is no tolerance to choose.  Need a real MI355X."""
+(pinned by test_render_gpu.py and test_render_aa_gpu.py): every comparison here is torch.equal — the batched launch is the eager launches'
+render_rays_kernel<S> on the same posed words (what differs is where `follow` is read and the grid's third axis), so there is no tolerance to
+choose; the bytes themselves are held by test_render_digests_gpu.py.  Need a real MI355X."""
 import ctypes as C
 import gc
 import os
