@@ -21,7 +21,7 @@ LIB_PATH = os.environ.get("PPENV_LIB", os.path.join(_PKG, "lib", "libppenv.so"))
 SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "ppenv_ta.hip"), os.path.join(_PKG, "csrc", "ppenv_ta_sim.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -29,13 +29,15 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter_device.h"), os.path.join(ROOT, "include", "ppenv_ppo_meter.h"),
            os.path.join(_PKG, "csrc", "ppenv_render_device.h"), os.path.join(ROOT, "include", "ppenv_render.h"),
            os.path.join(_PKG, "csrc", "ppenv_ta_outcome_device.h"), os.path.join(ROOT, "include", "ppenv_ta_outcome.h"),
+           os.path.join(_PKG, "csrc", "ppenv_serve_device.h"), os.path.join(ROOT, "include", "ppenv_serve.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
 # the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);
-# the ray caster's depth of a sky pixel is +inf
+# the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
-                "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
+                "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
 _lib = None
 
@@ -119,6 +121,23 @@ class TAOutcome(C.Structure):
     """ctypes mirror of pp_ta_outcome (include/ppenv_ta_outcome.h): 16 words of 8 bytes."""
     _fields_ = [("windows", C.c_uint64), ("envs", C.c_uint64), ("count", C.c_uint64 * 5), ("last_envs", C.c_uint64), ("last", C.c_uint64 * 5),
                 ("reserved", C.c_uint64 * 3)]
+
+
+SERVE_LAYOUT_SOA3, SERVE_LAYOUT_AOS5 = 0, 1                                              # PP_SERVE_LAYOUT_*
+SERVE_MAX_TILT_DEG = 57.0                                                               # PP_SERVE_MAX_TILT_DEG
+
+
+class ServeCell(C.Structure):
+    """ctypes mirror of pp_serve_cell (include/ppenv_serve.h)."""
+    _fields_ = [("speed_lo", C.c_float), ("speed_hi", C.c_float), ("tilt_lo_deg", C.c_float), ("tilt_hi_deg", C.c_float),
+                ("tilt_z_lo_deg", C.c_float), ("tilt_z_hi_deg", C.c_float), ("ball_y_lo", C.c_float), ("ball_y_hi", C.c_float),
+                ("ball_z_lo", C.c_float), ("ball_z_hi", C.c_float)]
+
+
+class ServePlan(C.Structure):
+    """ctypes mirror of pp_serve_plan."""
+    _fields_ = [("num_envs", C.c_int32), ("env_id_offset", C.c_int32), ("seed", C.c_uint64), ("form", C.c_int32), ("layout", C.c_int32),
+                ("reset_rows", C.c_int32), ("groups", C.c_int32), ("envs_per_group", C.c_int32), ("paired", C.c_int32), ("cells", C.c_void_p)]
 
 
 RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
@@ -373,6 +392,11 @@ def load(path):
     L.pp_ta_sim_set_outcome.argtypes = [vp, vp]
     L.pp_ta_post_physics_step_outcome.argtypes = [C.POINTER(scene.TAParams)] + [vp] * 16
     L.pp_ta_outcome_latch.argtypes = [vp, vp, i64, vp, vp]
+    # ---- include/ppenv_serve.h
+    L.pp_serve_plan_upload.argtypes = [C.POINTER(ServePlan), C.POINTER(ServeCell), vp, vp, vp]
+    L.pp_serve_fill.argtypes = [vp, i32, vp, vp, vp]
+    L.pp_serve_apply.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.pp_serve_apply_ids.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     return L
 
 

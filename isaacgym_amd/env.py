@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, scene
+from . import _lib, scene, serve
 from .dr import Randomizable
 
 
@@ -56,6 +56,8 @@ class PPEnv(Randomizable):
         self.ball = view(b.ball, 13 * n, torch.float32, (13, n))             # SoA [13][N]
         self.flags = view(b.flags, A * n, torch.int32, (n,) if A == 1 else (A, n))
         self.episode = view(b.episode, n, torch.int32, (n,))
+        self.serve_override = view(b.serve_override, 3 * n, torch.float32, (3, n))   # SoA [3][N]: read at a reset while the override is on
+        self.serve_plan = None
 
     def close(self):
         if getattr(self, "h", None) is not None and self.h:
@@ -194,6 +196,50 @@ class PPEnv(Randomizable):
         s = torch.as_tensor(serve, dtype=torch.float32).to(self.device).reshape(self.num_envs, 3).contiguous()
         _lib.check(self.L.ppenv_set_serve_override(self.h, s.data_ptr(), 1, _lib.stream(self.device)), self.L)
         torch.cuda.current_stream(self.device).synchronize()   # `s` must outlive the transpose kernel
+
+    def _config_of(self):
+        cfg = scene.Config()
+        _lib.check(self.L.ppenv_config_of(self.h, C.byref(cfg)), self.L)
+        return cfg
+
+    def serve_defaults(self):
+        """{serve axis: (lo, hi)}: the serve ranges the handle was created with (ppenv_config_of) — what a serve-plan cell does not name."""
+        cfg = self._config_of()
+        return {"serve_speed": (cfg.serve_speed_lo, cfg.serve_speed_hi), "serve_tilt": (cfg.serve_tilt_lo_deg, cfg.serve_tilt_hi_deg),
+                "serve_tilt_z": (cfg.serve_tilt_z_lo_deg, cfg.serve_tilt_z_hi_deg)}
+
+    def set_serve_plan(self, cells, paired=False, seed=None):
+        """A serve plan (include/ppenv_serve.h; serve.ServePlan): the envs are split into len(cells) equal groups, and from now on every reset
+        of an env of group g — in a step, reset_all or reset_idx — serves the ball its cell describes instead of the built-in draw.  A cell is
+        a dict of any of serve_speed, serve_tilt, serve_tilt_z, each a number (pinned) or (lo, hi); what it does not name is the handle's
+        configured range (ppenv_config_of).  paired: env i of every group is served the same sequence of balls.  seed: a STREAM seed, default
+        scene.stream_seed(the handle's seed, scene.STREAM_SERVES); the draws share nothing with the built-in serves, the noise or the tables.
+        The plan fills ppenv_buffers.serve_override with every env's serve 0 and switches the override on; the caller then launches
+        apply_serve_plan() once after every step.  The switch travels BY VALUE in the step kernel's arguments: a graph captured before this
+        call does not see it and must be captured again (one captured after it may hold step + apply_serve_plan).  -> the ServePlan (out, count, cells)."""
+        cfg = self._config_of()
+        seed = scene.stream_seed(cfg.seed, scene.STREAM_SERVES) if seed is None else seed
+        plan = serve.ServePlan(self.L, self.device, self.num_envs, cells, self.serve_defaults(), serve.AXES_7DOF, self.serve_override, form=cfg.variant,
+                               layout=_lib.SERVE_LAYOUT_SOA3, reset_rows=self.num_agents, seed=seed, env_id_offset=cfg.env_id_offset, paired=paired)
+        _lib.check(self.L.ppenv_set_serve_override(self.h, None, 1, _lib.stream(self.device)), self.L)
+        self.serve_plan = plan
+        return plan
+
+    def apply_serve_plan(self, env_ids=None):
+        """The per-step launch (pp_serve_apply on reset_buf), once after every step while a plan is set; env_ids: the id variant, after
+        reset_idx(env_ids) (all envs: an arange).  No synchronisation; capturable."""
+        if self.serve_plan is None:
+            raise _lib.PPEnvError("apply_serve_plan: no plan is set (set_serve_plan)")
+        if env_ids is None:
+            self.serve_plan.apply(self.reset_buf)
+        else:
+            self.serve_plan.apply_ids(env_ids)
+
+    def clear_serve_plan(self):
+        """The override off: the built-in serves are back, bit for bit (they are keyed by the envs' episode counters, which kept counting).
+        By value, like the switch on: a captured step must be captured again."""
+        _lib.check(self.L.ppenv_set_serve_override(self.h, None, 0, _lib.stream(self.device)), self.L)
+        self.serve_plan = None
 
     def get_state(self):
         n = self.L.ppenv_state_bytes(self.h)

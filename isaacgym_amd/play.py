@@ -5,6 +5,7 @@
                                                     average episode length) plus spread
     python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side --capture-deferred --capture-trajectory out.npz]
     python -m isaacgym_amd.play ... --sweep link_mass_scale=0.7:1.3:4 --sweep friction_scale=0.5,1.0 [--sweep-out cells.json]      one pass over the grid
+    python -m isaacgym_amd.play ... --sweep serve_speed=7.5:9:4 --sweep friction_scale=0.5,1.0 --paired                            serves swept too, every cell playing the same balls
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -25,13 +26,23 @@ Sweeps.  `Player(task, policy, sweep=Sweep.grid({"link_mass_scale": [0.7, 1.3], 
 every cell of a grid of physical-parameter scales in ONE pass: the envs are split into G equal groups (group g is envs [g * S, (g + 1) * S)),
 each group runs whole episodes under its cell's per-env tables (the domain-randomisation tables of dr.Randomizable.set_randomization, set before
 the first reset), and `GroupStats` keeps one totals struct and one freeze per group in the same two launches per control step, whatever G
-is (include/ppenv_play_group.h; `EpisodeStats` is its one-group case, and `Player.run` is one loop over the per-group totals).  Groups
-see DIFFERENT serves that are identically distributed — the env RNG is keyed by the global env id, and there are no common random numbers
-across groups — which is why every group reports `reward_stderr` = reward_std / sqrt(games): two cells differ when their averages differ
-by more than a few standard errors, not when they differ at all.
+is (include/ppenv_play_group.h; `EpisodeStats` is its one-group case, and `Player.run` is one loop over the per-group totals).  Unpaired
+groups see DIFFERENT serves that are identically distributed — the env RNG is keyed by the global env id — which is why every group
+reports `reward_stderr` = reward_std / sqrt(games): two cells differ when their averages differ by more than a few standard errors, not
+when they differ at all.
 
-Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), serve sweeps, common random
-numbers across groups, per-group outcome counts, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
+Serve sweeps and paired groups.  The axes `serve_speed`, `serve_tilt`, `serve_tilt_z` (degrees) and, on the 27-dof task, `ball_y`, `ball_z`
+sweep what the task is about — the served ball: a value is a number (pinned) or, in the Python API, a `(lo, hi)` range; what a cell does not
+name is the task's configured range.  They ride on a SERVE PLAN (include/ppenv_serve.h; VecTask.set_serve_plan): start() sets it before the
+first reset, so episode m of env e since start() is serve(e, m) of the plan's own random stream, and one more small launch per control step
+keeps every env's next serve on the device.  `Sweep(..., paired=True)` / `--paired` keys those draws by the env's index WITHIN its group:
+env i of every group is served the same sequence of balls (common random numbers), the serve noise two cells share cancels in their
+difference, and groups whose cells are equal are bitwise replicas of each other under deterministic play.  `reward_stderr` stays the
+unpaired one, so it is conservative for differences between paired cells.  The sampler's exploration noise (`--stochastic`) is keyed by
+row and is not paired.
+
+Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
+paired sampler noise, paired statistics (the standard error of a paired difference), anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
 `--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
 """
@@ -46,7 +57,7 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, serve
 from ._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ctypes mirror of ppenv_play_totals (bound in _lib.load)
 from ._lib import TA_OUTCOME_NAMES, TAOutcome
 from .dr import TABLE_NAMES
@@ -193,26 +204,41 @@ class EpisodeStats(GroupStats):
 _AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
 
 
+SERVE_AXES = serve.AXES_27DOF              # serve_speed, serve_tilt, serve_tilt_z; ball_y, ball_z (27-dof task only)
+
+
 def _axis(axis):
-    """'name' or 'name[row]' -> (table name, row or None); a name that is no table of set_randomization raises ValueError."""
+    """'name' or 'name[row]' -> (table name, row or None), or (serve axis, None); a name that is neither a table of set_randomization nor a
+    serve axis raises ValueError."""
+    if isinstance(axis, str) and axis in SERVE_AXES:
+        return axis, None
     m = _AXIS.match(axis) if isinstance(axis, str) else None
     if m is None or m.group(1) not in TABLE_NAMES:
-        raise ValueError(f"sweep axis {axis!r}: an axis is one of {', '.join(TABLE_NAMES)}, or one row of a table as name[row]")
+        raise ValueError(f"sweep axis {axis!r}: an axis is one of {', '.join(TABLE_NAMES)}, or one row of a table as name[row], or a serve axis: "
+                         f"{', '.join(SERVE_AXES)}")
     return m.group(1), None if m.group(2) is None else int(m.group(2))
 
 
 class Sweep:
-    """G cells of physical-parameter scales, one per group of envs.  A cell maps an axis to one scalar scale; an axis is a table of
+    """G cells of physical parameters, one per group of envs.  A cell maps an axis to one scalar scale; an axis is a table of
     dr.Randomizable.set_randomization (`friction_scale`: every row of it) or one row of one (`dof_stiffness_scale[5]`, which wins over
-    the plain axis of the same table in that row).  What a cell does not name stays 1.0."""
+    the plain axis of the same table in that row).  What a cell does not name stays 1.0.
+    A SERVE axis (SERVE_AXES: serve_speed, serve_tilt, serve_tilt_z in degrees; ball_y, ball_z on the 27-dof task) maps to a number — the
+    quantity is pinned, and may be negative — or a (lo, hi) range it is drawn from; what a cell does not name is the task's configured range.
+    paired: env i of every group is served the same sequence of balls (a serve plan keyed by the index within the group), with or
+    without a serve axis."""
 
-    def __init__(self, cells):
+    def __init__(self, cells, paired=False):
         self.cells = [dict(c) for c in cells]
+        self.paired = bool(paired)
         if not 1 <= len(self.cells) <= MAX_GROUPS:
             raise ValueError(f"a sweep has 1..{MAX_GROUPS} cells, not {len(self.cells)}")
         for cell in self.cells:
             for axis, v in cell.items():
-                _axis(axis)
+                if _axis(axis)[0] in SERVE_AXES:
+                    lo, hi = serve.value_range(axis, v)
+                    cell[axis] = lo if lo == hi else (lo, hi)
+                    continue
                 cell[axis] = float(v)
                 if not math.isfinite(cell[axis]) or cell[axis] < 0.0:
                     raise ValueError(f"sweep axis {axis!r}: the scale {v!r} is not a finite number >= 0")
@@ -221,17 +247,18 @@ class Sweep:
         return len(self.cells)
 
     @classmethod
-    def grid(cls, axes):
+    def grid(cls, axes, paired=False):
         """{axis: values, ...} -> the Cartesian product, the last axis fastest."""
         names = list(axes)
         values = [list(axes[k]) for k in names]
         if not names or any(len(v) == 0 for v in values):
             raise ValueError("Sweep.grid: at least one axis, and at least one value per axis")
-        return cls([dict(zip(names, combo)) for combo in itertools.product(*values)])
+        return cls([dict(zip(names, combo)) for combo in itertools.product(*values)], paired=paired)
 
     @classmethod
-    def parse(cls, specs):
-        """The CLI form, one 'AXIS=SPEC' per axis -> Sweep.grid: SPEC is `lo:hi:count` (an inclusive linspace) or a comma list taken as given."""
+    def parse(cls, specs, paired=False):
+        """The CLI form, one 'AXIS=SPEC' per axis -> Sweep.grid: SPEC is `lo:hi:count` (an inclusive linspace) or a comma list taken as given
+        (on a serve axis: pinned values)."""
         axes = {}
         for spec in specs:
             axis, eq, text = str(spec).partition("=")
@@ -252,7 +279,16 @@ class Sweep:
                 raise ValueError(f"--sweep {spec!r}: the axis {axis!r} is given twice")
             _axis(axis)
             axes[axis] = values
-        return cls.grid(axes)
+        return cls.grid(axes, paired=paired)
+
+    def serve_cells(self, defaults):
+        """The per-group cells of the serve plan for a task whose serve axes and configured ranges are `defaults` ({axis: (lo, hi)}: the env's
+        serve_defaults()) -> one {axis: (lo, hi)} per cell, or None when no cell names a serve axis and `paired` is false (no plan is needed).
+        A serve axis the task does not have (ball_y, ball_z on a 7-dof task) raises ValueError naming the axes it has."""
+        named = [{a: v for a, v in cell.items() if a in SERVE_AXES} for cell in self.cells]
+        if not self.paired and not any(named):
+            return None
+        return serve.resolve_cells(named, defaults, tuple(defaults))
 
     def tables(self, rows_by_name, num_envs):
         """The per-env tables of this sweep for an environment of num_envs envs whose tables have rows_by_name rows (its DR_TABLE_ROWS; 0: a
@@ -268,7 +304,7 @@ class Sweep:
             for g, cell in enumerate(self.cells):
                 for axis, v in cell.items():
                     name, row = _axis(axis)
-                    if (row is None) != plain:
+                    if (row is None) != plain or name in SERVE_AXES:
                         continue
                     if name not in rows_by_name:
                         raise ValueError(f"sweep axis {axis!r}: this environment's tables are {', '.join(rows_by_name)}")
@@ -301,10 +337,10 @@ def sum_totals(per_group):
     return out
 
 
-def group_summary(cell, totals, num_agents, games_num):
+def group_summary(cell, totals, num_agents, games_num, paired=False):
     """One entry of run()'s `groups`: the cell, summarize() of the group's totals, reward_stderr = reward_std / sqrt(games) (nan with no
-    game) and complete = games >= games_num."""
-    out = dict(cell=dict(cell))
+    game; the UNPAIRED standard error, conservative for a difference of paired cells), complete = games >= games_num and `paired`."""
+    out = dict(cell=dict(cell), paired=bool(paired))
     out.update(summarize(totals, num_agents))
     g = out["games"]
     out["reward_stderr"] = out["reward_std"] / math.sqrt(g) if g > 0 else float("nan")
@@ -313,7 +349,7 @@ def group_summary(cell, totals, num_agents, games_num):
 
 
 def cell_text(cell):
-    return " ".join(f"{k}={v:g}" for k, v in cell.items()) or "(plain)"
+    return " ".join(f"{k}={v:g}" if not isinstance(v, (tuple, list)) else f"{k}={v[0]:g}..{v[1]:g}" for k, v in cell.items()) or "(plain)"
 
 
 def group_line(g):
@@ -336,7 +372,13 @@ class Player:
     dict summed over the groups plus `groups` (one group_summary per cell, in cell order) and leaves the task as it found it: the
     randomisation cleared and the envs' episode counters (the RNG key of their serves) put back, so what is played on the task afterwards is
     what would have been played without the sweep.  Groups see different, identically distributed serves (the RNG is keyed by the global
-    env id): compare cells by `reward_stderr`.  Refused with a sweep: a task with `randomize: True` (its tables are the sweep's) and
+    env id): compare cells by `reward_stderr`.
+    A sweep with serve axes, or paired=True, also sets a serve plan (task.set_serve_plan) in start(), before the reset: episode m of env e
+    since start() is serve(e, m) of the plan, and task.step launches the plan's apply after every env step; end_sweep() clears it.  With
+    paired=True env i of every group is served the same sequence of balls — with no serve axis, from the configured ranges — so groups
+    whose cells are equal are bitwise replicas of each other under deterministic play; `reward_stderr` stays the unpaired one, conservative
+    for differences between paired cells; the sampler's exploration noise (deterministic=False) is keyed by row and is not paired.
+    Refused with a sweep: a task with `randomize: True` (its tables are the sweep's) and
     outcomes=True (the 27-dof counts are cross-env windows and cannot be split by group)."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
@@ -364,11 +406,13 @@ class Player:
         if sigma is not None:
             policy.sigma.fill_(math.exp(float(sigma)))
         self.sweep = sweep
-        self._tables = self._episode0 = None
+        self._tables = self._episode0 = self._serve_cells = None
         if sweep is None:
             self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
         else:
             self._tables = sweep.tables(self._dr_handle().DR_TABLE_ROWS, task.num_envs)
+            if sweep.paired or any(a in SERVE_AXES for cell in sweep.cells for a in cell):
+                self._serve_cells = sweep.serve_cells(task.env.serve_defaults())
             self.stats = GroupStats(task.num_envs // len(sweep), len(sweep), self.num_agents, self.games_num, sim)
         if recorder is not None and recorder.renderer.task is not task:
             raise ValueError("the recorder renders another task")
@@ -391,11 +435,13 @@ class Player:
         return env.episode if hasattr(env, "episode") else env.state.episode
 
     def end_sweep(self):
-        """The task as the sweep found it: the plain step kernel (clear_randomization) and the episode counters of before start().  run() calls
-        it at its end, also on an exception; a caller that drives start() / step() itself calls it when done."""
+        """The task as the sweep found it: the plain step kernel (clear_randomization), no serve plan, and the episode counters of before
+        start().  run() calls it at its end, also on an exception; a caller that drives start() / step() itself calls it when done."""
         if self.sweep is None:
             return
         self.task.env.clear_randomization()
+        if self._serve_cells is not None:
+            self.task.clear_serve_plan()
         if self._episode0 is not None:
             self._episode().copy_(self._episode0)
             self._episode0 = None
@@ -406,7 +452,10 @@ class Player:
         if self.sweep is not None:
             if self._episode0 is None:
                 self._episode0 = self._episode().clone()
-            self.task.env.set_randomization(**self._tables)           # before the reset: the first counted episode is already the cell's
+            if self._tables or self._serve_cells is None:             # (a sweep of serves alone keeps the plain step kernel)
+                self.task.env.set_randomization(**self._tables)       # before the reset: the first counted episode is already the cell's
+            if self._serve_cells is not None:                         # fill = serve 0; the reset below consumes it and leaves count 1
+                self.task.set_serve_plan(self._serve_cells, paired=self.sweep.paired)
         self.task.reset_idx()
         self.stats.reset()
         if self.outcome is not None:
@@ -457,7 +506,7 @@ class Player:
             out = summarize(tot, self.num_agents)
             out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
             if self.sweep is not None:
-                out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num) for cell, t in zip(self.sweep.cells, per)]
+                out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num, self.sweep.paired) for cell, t in zip(self.sweep.cells, per)]
             if self.outcome is not None:
                 out["outcomes"] = self.read_outcomes()
             if self.recorder is not None:
@@ -483,7 +532,10 @@ def parse_args(argv=None):
     ap.add_argument("--outcomes", action="store_true", help="27-dof task: print the reference's five outcome counts (TA:1164-1168) as rates of the envs")
     ap.add_argument("--sweep", action="append", default=None, metavar="AXIS=SPEC", help="play under a grid of physical-parameter scales in one pass (repeatable: "
                     "one axis each; the envs are split into one group per cell and --games is per cell): AXIS is dof_stiffness_scale, dof_damping_scale, "
-                    "link_mass_scale, restitution_scale or friction_scale, or one row of a table as NAME[ROW]; SPEC is lo:hi:count (inclusive) or v0,v1,...")
+                    "link_mass_scale, restitution_scale or friction_scale, or one row of a table as NAME[ROW], or a serve axis: serve_speed, serve_tilt, "
+                    "serve_tilt_z (degrees; may be negative), ball_y, ball_z (27-dof task); SPEC is lo:hi:count (inclusive) or v0,v1,...")
+    ap.add_argument("--paired", action="store_true", help="with --sweep: env i of every cell is served the same sequence of balls (common random numbers), "
+                    "so the serve noise cancels in the difference of two cells")
     ap.add_argument("--sweep-out", default=None, metavar="FILE.json", help="with --sweep: write the per-cell results (the result's `groups`) to FILE.json")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
@@ -500,6 +552,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.sweep_out and not args.sweep:
         ap.error("--sweep-out needs --sweep")
+    if args.paired and not args.sweep:
+        ap.error("--paired needs --sweep")
     if args.sweep:
         try:
             Sweep.parse(args.sweep)
@@ -540,7 +594,7 @@ def main(argv=None):
     task = isaacgym_amd.make(seed=args.seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
     recorder = make_recorder(task, args) if args.capture or args.capture_trajectory else None
-    sweep = Sweep.parse(args.sweep) if getattr(args, "sweep", None) else None
+    sweep = Sweep.parse(args.sweep, paired=getattr(args, "paired", False)) if getattr(args, "sweep", None) else None
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
                 max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep)
     last = dict(games=0, steps=0, reward=[0.0])

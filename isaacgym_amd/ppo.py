@@ -409,6 +409,9 @@ class PPOTrainer:
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if getattr(task, "randomize", False):
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
+        if getattr(task, "_serve_plan", None) is not None:
+            raise ValueError("a task with a serve plan set is not supported by PPOTrainer: the collector drives the env below VecTask.step, so the plan's "
+                             "per-step launch would not run; call task.clear_serve_plan() first")
         self.task, self.env = task, task.env
         env = self.env
         self.device = dev = torch.device(env.device)

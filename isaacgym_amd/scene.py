@@ -970,6 +970,7 @@ def _mix64(z):
 # RLGamesPolicy.act — hands mix64(seed ^ the salt of the family of draws) down instead: seeds that differ in any bit (seed + rank) give unrelated
 # streams, and one user seed given to a task, its randomisation plan and its trainer never yields one draw twice.
 STREAM_ENV, STREAM_TABLES, STREAM_SAMPLER = 0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0   # serve / reset draws + step noise; tables; exploration noise
+STREAM_SERVES = 0x082EFA98EC4E6C89                                                                       # the serve plan's draws (include/ppenv_serve.h)
 
 
 def stream_seed(seed, family_salt):

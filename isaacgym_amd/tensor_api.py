@@ -10,7 +10,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, scene
+from . import _lib, scene, serve
 from .dr import Randomizable
 
 
@@ -73,8 +73,8 @@ class TAState:
         else:
             check_outcome(outcome, self.device)
             self._ck(self.L.pp_ta_post_physics_step_outcome(*args, outcome.data_ptr(), _lib.stream(self.device)))
-        if ov is not None:
-            torch.cuda.current_stream(self.device).synchronize()   # keep `ov` alive until the kernel has read it
+        if ov is not None and ov.data_ptr() != reset_override.data_ptr():
+            torch.cuda.current_stream(self.device).synchronize()   # keep a converted copy alive until the kernel has read it
 
 
 class TASim(Randomizable):
@@ -161,7 +161,7 @@ class TASim(Randomizable):
             _lib.ptr(rb_states), dof_force.data_ptr(), pre_ball_vx.data_ptr(), _lib.ptr(ov), state.flags.data_ptr(),
             state.episode.data_ptr(), state.progress_buf.data_ptr(), obs.data_ptr(), rew.data_ptr(), reset.data_ptr(),
             state._any_reset.data_ptr(), _lib.stream(self.device)))
-        if ov is not None:
+        if ov is not None and ov.data_ptr() != reset_override.data_ptr():    # a converted copy must outlive the kernel; the caller's own tensor does
             torch.cuda.current_stream(self.device).synchronize()
 
     def set_outcome(self, t=None):
@@ -258,15 +258,18 @@ class TAEnv:
         self.reset_buf.fill_(1)   # upstream VecTask.allocate_buffers
         self.sim.reset_buf = self.reset_buf       # what sim.apply_reset_randomization reads
         self.outcome = None                       # enable_outcomes(): the pp_ta_outcome struct of this env
+        self.serve_plan = None                    # set_serve_plan(): the [N,5] reset rows the step consumes instead of its draws
 
     def step(self, actions, obs=None, rew=None, reset=None):
         """obs / rew / reset (fused mode only): tensors that receive this step's observations, rewards and reset flags instead of
         obs_buf / rew_buf / reset_buf — a rollout collector passes its horizon-major slices, so nothing is copied afterwards."""
         if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
+        ov = self.serve_plan.out if self.serve_plan is not None else None      # [N,5]: what an env that resets in this step is served
         if self.fused:
             self.sim.step(self.state, actions, self.initial_rb_states, self.root_states, self.dof_states,
-                          self._rb_states if self.materialize_rb else None, self.dof_force_tensor, self.pre_ball_vx, obs=obs, rew=rew, reset=reset)
+                          self._rb_states if self.materialize_rb else None, self.dof_force_tensor, self.pre_ball_vx,
+                          reset_override=ov, obs=obs, rew=rew, reset=reset)
             if obs is not None or rew is not None or reset is not None:
                 return ({"obs": self.obs_buf if obs is None else obs}, self.rew_buf if rew is None else rew,
                         self.reset_buf if reset is None else reset, {})
@@ -274,7 +277,7 @@ class TAEnv:
             assert obs is None and rew is None and reset is None, "output slices need the fused step"
             self.sim.simulate(actions, self.root_states, self.dof_states, self._rb_states, self.dof_force_tensor, self.pre_ball_vx)
             self.state.post_physics_step(self._rb_states, self.initial_rb_states, self.root_states, self.dof_states, self.dof_force_tensor, self.pre_ball_vx,
-                                         outcome=self.outcome)
+                                         reset_override=ov, outcome=self.outcome)
         return {"obs": self.obs_buf}, self.rew_buf, self.reset_buf, {}
 
     @property
@@ -333,6 +336,38 @@ class TAEnv:
     def set_gravity(self, gravity_z):
         self.sim.set_gravity(gravity_z)
 
+    def serve_defaults(self):
+        """{serve axis: (lo, hi)}: the task's own ranges (`params`) — what a serve-plan cell does not name."""
+        p = self.params
+        return {"serve_speed": (p.serve_speed_lo, p.serve_speed_hi), "serve_tilt": (p.serve_tilt_lo_deg, p.serve_tilt_hi_deg),
+                "serve_tilt_z": (p.serve_tilt_z_lo_deg, p.serve_tilt_z_hi_deg), "ball_y": (p.ball_y_lo, p.ball_y_hi), "ball_z": (p.ball_z_lo, p.ball_z_hi)}
+
+    def set_serve_plan(self, cells, paired=False, seed=None):
+        """A serve plan (include/ppenv_serve.h; PPEnv.set_serve_plan has the contract): a cell is a dict of any of serve_speed, serve_tilt,
+        serve_tilt_z, ball_y, ball_z, each a number (pinned) or (lo, hi); what it does not name is the task's range (`params`).  While it
+        is set, `step` hands the plan's [N,5] buffer (ball y, z, v_x, v_y, v_z) to the kernel as its reset_override — a pointer argument of
+        every launch — and reset_idx takes the listed envs' rows from it; apply_serve_plan() follows every step.  seed: a STREAM seed,
+        default scene.stream_seed(the task's seed, scene.STREAM_SERVES).  -> the ServePlan (out, count, cells)."""
+        p, defaults = self.params, self.serve_defaults()
+        seed = scene.stream_seed(p.seed, scene.STREAM_SERVES) if seed is None else seed
+        out = torch.zeros((self.num_envs, 5), dtype=torch.float32, device=self.device)
+        self.serve_plan = serve.ServePlan(self.sim.L, self.device, self.num_envs, cells, defaults, serve.AXES_27DOF, out, form=scene.VARIANT_TN,
+                                          layout=_lib.SERVE_LAYOUT_AOS5, reset_rows=1, seed=seed, env_id_offset=p.env_id_offset, paired=paired)
+        return self.serve_plan
+
+    def apply_serve_plan(self, env_ids=None):
+        """The per-step launch (pp_serve_apply on reset_buf); env_ids: the id variant, after reset_idx(env_ids) (all envs: an arange)."""
+        if self.serve_plan is None:
+            raise _lib.PPEnvError("apply_serve_plan: no plan is set (set_serve_plan)")
+        if env_ids is None:
+            self.serve_plan.apply(self.reset_buf)
+        else:
+            self.serve_plan.apply_ids(env_ids)
+
+    def clear_serve_plan(self):
+        """The task's own keyed draws are back, bit for bit (they are keyed by the envs' episode counters, which kept counting)."""
+        self.serve_plan = None
+
     def reset_idx(self, env_ids=None):
         """_reset_idx (TA:965-1028) outside a step, for the listed env ids (None: all).  A rare host-driven path: plain torch
         indexing on the task's own tensors with the draws of each env's next episode (the same keyed draws the kernel uses)."""
@@ -346,7 +381,10 @@ class TAEnv:
         dev_ids = ids.to(self.device)
         st = self.state
         ep = (st.episode[dev_ids].to(torch.int64) + 1).cpu()
-        ov = scene.ta_reset_draws(self.params, ids, ep).to(self.device)               # y, z, vx, vy, vz (TA:976-979)
+        if self.serve_plan is not None:
+            ov = self.serve_plan.out[dev_ids]                                         # the plan's rows, gathered on the device
+        else:
+            ov = scene.ta_reset_draws(self.params, ids, ep).to(self.device)           # y, z, vx, vy, vz (TA:976-979)
         init = torch.tensor([[self.params.init_root[a][k] for k in range(7)] for a in range(3)], dtype=torch.float32, device=self.device)
         rows = torch.zeros((ids.numel(), 3, 13), dtype=torch.float32, device=self.device)
         rows[:, :, 0:7] = init

@@ -85,6 +85,7 @@ class VecTask:
         if self.randomize_apply_at not in ("step", "reset"):
             raise ValueError(f"task.randomization_params.apply_at must be 'step' or 'reset', got {self.randomize_apply_at!r}")
         self._dr_reset = False
+        self._serve_plan = None            # set_serve_plan(): the ServePlan whose per-step launch step() then issues
         self.stats_every = int(config.get("stats_every", 40))                       # TT:763: the reference prints the means every 40 steps
 
         self.sim = self.create_sim()       # the reference's VecTask.__init__ calls back create_sim (TT:325)
@@ -139,6 +140,8 @@ class VecTask:
         if self.randomize:                   # upstream applies them from _reset_idx (TT:849-850); here once per step, gated by `frequency`
             self.apply_randomizations(self.randomization_params)
         self.env.step(actions)              # action clamp (clipActions) happens inside the kernel
+        if self._serve_plan is not None:    # the envs this step reset have consumed their serve: their next one (one launch, no sync)
+            self.env.apply_serve_plan()
         if self._dr_reset:                  # randomize_buf += 1; the envs this step reset redraw their table columns (one launch, no sync)
             self.env.apply_reset_randomization()
         self.control_steps += 1
@@ -252,8 +255,27 @@ class VecTask:
             self.env.reset_idx(env_ids)
         self._reset_idx_randomization(env_ids)
 
+    def set_serve_plan(self, cells, paired=False):
+        """A serve plan on the task's environment (PPEnv.set_serve_plan / TAEnv.set_serve_plan: one cell of serve ranges per equal group of
+        envs; `paired`: env i of every group is served the same sequence of balls), keyed by the serve-plan stream of cfg["seed"]
+        (scene.STREAM_SERVES) and the task's env_id_offset.  From now on step() launches env.apply_serve_plan() right after the env's step
+        and reset_idx() its id variant after the reset; with no plan neither runs anything new.  Episode m of env e since a
+        set_serve_plan() + reset_idx() is serve(e, m).  -> the ServePlan."""
+        seed = scene.stream_seed(int((self.cfg or {}).get("seed", 0)), scene.STREAM_SERVES)
+        self._serve_plan = self.env.set_serve_plan(cells, paired=paired, seed=seed)
+        return self._serve_plan
+
+    def clear_serve_plan(self):
+        """The task's built-in serves again (env.clear_serve_plan); nothing is launched per step any more."""
+        if self._serve_plan is not None:
+            self.env.clear_serve_plan()
+            self._serve_plan = None
+
     def _reset_idx_randomization(self, env_ids):
-        """_reset_idx's apply_randomizations (TT:849-850) for a reset from outside a step: the listed envs (None: all) count as resetting."""
+        """_reset_idx's apply_randomizations (TT:849-850) for a reset from outside a step: the listed envs (None: all) count as resetting.
+        With a serve plan set they have also consumed their serve."""
+        if self._serve_plan is not None:
+            self.env.apply_serve_plan(torch.arange(self.num_envs, device=self.device) if env_ids is None else env_ids)
         if self._dr_reset:
             self.env.apply_reset_randomization(torch.arange(self.num_envs, device=self.device) if env_ids is None else env_ids)
 
@@ -485,6 +507,8 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
         if self.randomize:                  # as the 7-dof tasks: once per step, gated by `frequency` (upstream: from _reset_idx, TA's reset path)
             self.apply_randomizations(self.randomization_params)
         self.env.step(actions)              # the clipActions clamp happens inside the kernel
+        if self._serve_plan is not None:
+            self.env.apply_serve_plan()
         if self._dr_reset:
             self.env.apply_reset_randomization()
         self.control_steps += 1

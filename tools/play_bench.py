@@ -5,6 +5,7 @@ accounting (the eager, non-graph step of tools/rollout_bench.py through the VecT
     python tools/play_bench.py --task HumanoidPingpongTiltG1 --num-envs 4096
     rocprofv3 --kernel-trace --stats -d out -o play -- python tools/play_bench.py --num-envs 4096 --repeats 1      # the launches' own time
     python tools/play_bench.py --num-envs 4096 --sweep-groups 16      # the same loops under Player(sweep=): 16 groups, the grouped accounting
+    python tools/play_bench.py --num-envs 4096 --serve-plan 16        # ... under a paired sweep of 16 equal cells: a serve plan, one more launch per task.step
 """
 import argparse
 import json
@@ -27,7 +28,11 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--poll-every", type=int, default=64)
     ap.add_argument("--sweep-groups", type=int, default=0, help="G > 0: play under a sweep of G cells (friction_scale 0.5 .. 1.5), G groups of num_envs / G envs")
+    ap.add_argument("--serve-plan", type=int, default=0, help="G > 0: play under a paired sweep of G equal cells (Sweep([{}] * G, paired=True)): every task.step "
+                    "of the three loops also launches the serve plan's apply")
     args = ap.parse_args()
+    if args.serve_plan > 0 and args.sweep_groups > 0:
+        ap.error("--serve-plan and --sweep-groups are two runs")
     import torch
     import isaacgym_amd
     from isaacgym_amd.play import Player
@@ -40,6 +45,10 @@ def main():
     if args.sweep_groups > 0:
         from isaacgym_amd.play import Sweep
         sweep["sweep"] = Sweep.parse([f"friction_scale=0.5:1.5:{args.sweep_groups}"])
+    if args.serve_plan > 0:
+        from isaacgym_amd.play import Sweep
+        sweep["sweep"] = Sweep([{} for _ in range(args.serve_plan)], paired=True)
+    groups = max(args.sweep_groups, args.serve_plan)
     pl = Player(task, policy, games_num=1 << 40, poll_every=args.poll_every, **sweep)       # never frozen: every step pays the full accounting
     pl.start()
 
@@ -69,11 +78,11 @@ def main():
         for k, fn in loops.items():
             us[k].append(timed(fn, args.steps))
     tot = pl.stats.read()
-    if args.sweep_groups > 0:
+    if groups > 0:
         from isaacgym_amd.play import sum_totals
         tot = sum_totals(tot)
-        tot["launches"] //= args.sweep_groups
-    out = {"task": args.task, "num_envs": args.num_envs, "sweep_groups": args.sweep_groups, "rows": pl.stats.rows, "steps": args.steps, "repeats": args.repeats,
+        tot["launches"] //= groups
+    out = {"task": args.task, "num_envs": args.num_envs, "sweep_groups": args.sweep_groups, "serve_plan": args.serve_plan, "rows": pl.stats.rows, "steps": args.steps, "repeats": args.repeats,
            "poll_every": args.poll_every, "games": tot["games"], "launches": tot["launches"]}
     for k, v in us.items():
         out[f"{k}_us"] = round(statistics.median(v), 2)
