@@ -49,10 +49,23 @@ struct DevBuffers {
     float* serve;
 };
 
-// State stores of the step kernels are non-temporal: nothing in the launch reads the state again, so it may stream out.
+// State stores of the step kernels (4 or 8 bytes per lane into the [field][N] arrays) are non-temporal: nothing in the launch reads the
+// state again, so it may stream out; the next launch reads it, and a non-temporal store keeps the line in the L2 it will be read from.
 // Measured at N = 16384 / 65536: plain 13.03 / 19.50 us, non-temporal 12.92 / 19.18 us, system scope 13.13 / 20.28 us.
+// Measured again with the observation tile written through (profiles/r11_a_ab.txt; N = 16384): the same stores as relaxed
+// agent-scope atomic stores (write-through, 4 bytes per lane) 11.44 against 11.44 us; the ball wave's rows transposed through LDS and
+// written through in 16-byte pieces 12.68 against 11.43 us.  Neither is in the build.
 template <class V>
 __device__ __forceinline__ void st_state(V* p, V v) { __builtin_nontemporal_store(v, p); }
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+// One 16-byte write-through store (global_store_dwordx4 ... sc1) for output that nobody on this chip reads back soon: the line leaves the
+// XCD's L2 while the other workgroups still compute, instead of staying dirty there until the end of the launch writes it back with the
+// next launch waiting behind it.  `p` is 16-byte aligned.  The asm statement is not in the compiler's count of outstanding stores, which
+// nothing here waits on; the s_nop keeps the next instruction off the data registers until the store has read them.
+__device__ __forceinline__ void st_through16(float* p, f4v v) {
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
 
 // ------------------------------------------------------------- SoA state <-> registers
 template <int A>
@@ -127,14 +140,13 @@ struct DRTables {
 // obs rows of one workgroup: LDS [kBlock][kObsStride] -> obs_buf[base*80 ...], 16 B per lane, contiguous
 __device__ __forceinline__ void flush_obs(const float* s_obs, float* obs, int base, int nvalid, int lane) {
     const int total = nvalid * PPENV_NUM_OBS;   // multiple of 4; a float4 never straddles rows (80 % 4 == 0)
-    float4* dst = reinterpret_cast<float4*>(obs + (size_t)base * PPENV_NUM_OBS);
+    float* dst = obs + (size_t)base * PPENV_NUM_OBS;
     for (int k = lane * 4; k < total; k += kBlock * 4) {
         int r = k / PPENV_NUM_OBS, c = k - r * PPENV_NUM_OBS;
         const float* src = &s_obs[r * kObsStride + c];
-        // non-temporal: the env never reads obs_buf back, so the rows need not displace its state in L2
-        typedef float f4v __attribute__((ext_vector_type(4)));
+        // write-through: the env never reads obs_buf back, so the rows neither displace its state in L2 nor wait there for the launch's end
         f4v val = {src[0], src[1], src[2], src[3]};
-        __builtin_nontemporal_store(val, reinterpret_cast<f4v*>(&dst[k >> 2]));
+        st_through16(dst + k, val);
     }
 }
 
@@ -226,7 +238,6 @@ template <int C0, int C1>
 __device__ __forceinline__ void flush_obs_cols(const float* s_obs, float* obs, int t0, int nrows, size_t g0, int gstep, int lane) {
     constexpr int per_row = (C1 - C0) / 4;
     const int total = nrows * per_row;
-    typedef float f4v __attribute__((ext_vector_type(4)));
     if (nrows == kBlock) {
         // full workgroup (every one but a ragged last): the trip count is a constant, so all LDS reads of the flush are in
         // flight before the first store instead of one read-wait-store round trip per iteration
@@ -242,7 +253,7 @@ __device__ __forceinline__ void flush_obs_cols(const float* s_obs, float* obs, i
         for (int it = 0; it < per_row; it++) {
             const int k = it * kBlock + lane;
             const int r = k / per_row, c = C0 + 4 * (k - r * per_row);
-            __builtin_nontemporal_store(val[it], reinterpret_cast<f4v*>(obs + ((g0 + (size_t)r * gstep) * PPENV_NUM_OBS + c)));
+            st_through16(obs + ((g0 + (size_t)r * gstep) * PPENV_NUM_OBS + c), val[it]);
         }
         return;
     }
@@ -250,7 +261,7 @@ __device__ __forceinline__ void flush_obs_cols(const float* s_obs, float* obs, i
         int r = k / per_row, c = C0 + 4 * (k - r * per_row);
         const float* src = &s_obs[(t0 + r) * kObsStride + c];
         f4v val = {src[0], src[1], src[2], src[3]};
-        __builtin_nontemporal_store(val, reinterpret_cast<f4v*>(obs + ((g0 + (size_t)r * gstep) * PPENV_NUM_OBS + c)));
+        st_through16(obs + ((g0 + (size_t)r * gstep) * PPENV_NUM_OBS + c), val);
     }
 }
 

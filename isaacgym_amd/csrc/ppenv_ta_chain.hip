@@ -507,9 +507,17 @@ constexpr bool geo_owners_ok() {   // every shape, the paddle and the bound cent
 }
 static_assert(geo_owners_ok(), "collision shapes must ride on the pelvis, the waist chain or the right arm");
 
-// The full-workgroup flush leaves the CU with non-temporal stores
+// The 16-byte pieces of the flush (observation tile, dof / force / root rows of a full workgroup) leave the CU written through
+// (global_store_dwordx4 ... sc1): they are on their way to memory while the other workgroups still compute, instead of staying dirty in
+// the XCD's L2 for the ball wave's fence ahead of the ticket and the end of the launch to write back (30.30 -> 29.25 us at 4096 envs,
+// DESIGN.md §6).  Nothing in the launch reads these bytes, and the ticket orders the flag words only, which are not stored here.  The asm
+// statement is not in the compiler's count of outstanding stores, which nothing waits on; the s_nop keeps the next instruction off the
+// data registers until the store has read them.
 template <class V>
-__device__ __forceinline__ void flush_store(V v, V* p) { __builtin_nontemporal_store(v, p); }
+__device__ __forceinline__ void flush_store(V v, V* p) {
+    static_assert(sizeof(V) == 16, "16-byte pieces only");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+}
 // ---- the kernel -------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ Frame torso_frame(const Shared& S, int e) {
     Frame f;
@@ -1080,7 +1088,7 @@ __global__ __launch_bounds__(kWaves * 64) void ta_chain_kernel(const TAScal P, c
             }
             const int nvec = nvalid * PPENV_TA_NUM_OBS / 4, rem = nvalid * PPENV_TA_NUM_OBS - 4 * nvec;   // a ragged block need not be a multiple of 4
             for (int t = tid; t < nvec; t += kThreads)
-                __builtin_nontemporal_store(reinterpret_cast<const f4v*>(S.u.obs)[t], reinterpret_cast<f4v*>(dobs) + t);
+                flush_store(reinterpret_cast<const f4v*>(S.u.obs)[t], reinterpret_cast<f4v*>(dobs) + t);
             if (tid < rem) dobs[4 * nvec + tid] = S.u.obs[4 * nvec + tid];
             for (int t = tid; t < nvalid * 2 * NDOF; t += kThreads) __builtin_nontemporal_store(S.dof[t], &a.dof_states[(size_t)e0 * 2 * NDOF + t]);
             for (int t = tid; t < nvalid * NDOF; t += kThreads) __builtin_nontemporal_store(S.act[t], &a.dof_force[(size_t)e0 * NDOF + t]);
