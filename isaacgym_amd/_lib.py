@@ -21,7 +21,8 @@ LIB_PATH = os.environ.get("PPENV_LIB", os.path.join(_PKG, "lib", "libppenv.so"))
 SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "ppenv_ta.hip"), os.path.join(_PKG, "csrc", "ppenv_ta_sim.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_play_pair.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -30,14 +31,17 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_render_device.h"), os.path.join(ROOT, "include", "ppenv_render.h"),
            os.path.join(_PKG, "csrc", "ppenv_ta_outcome_device.h"), os.path.join(ROOT, "include", "ppenv_ta_outcome.h"),
            os.path.join(_PKG, "csrc", "ppenv_serve_device.h"), os.path.join(ROOT, "include", "ppenv_serve.h"),
+           os.path.join(_PKG, "csrc", "ppenv_play_pair_device.h"), os.path.join(ROOT, "include", "ppenv_play_pair.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
 # the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);
-# the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign
+# the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign;
+# the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
-                "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
+                "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
 _lib = None
 
@@ -106,6 +110,12 @@ class PlayTotals(C.Structure):
     _fields_ = [("games", C.c_int64), ("steps", C.c_int64), ("launches", C.c_int64),
                 ("reward", C.c_double * MAX_AGENTS), ("reward_sq", C.c_double * MAX_AGENTS),
                 ("reward_min", C.c_float * MAX_AGENTS), ("reward_max", C.c_float * MAX_AGENTS)]
+
+
+class PlayPairTotals(C.Structure):
+    """ctypes mirror of pp_play_pair_totals (include/ppenv_play_pair.h)."""
+    _fields_ = [("pairs", C.c_int64), ("steps_diff", C.c_int64), ("diff", C.c_double * MAX_AGENTS), ("diff_sq", C.c_double * MAX_AGENTS),
+                ("cell", C.c_double * MAX_AGENTS), ("base", C.c_double * MAX_AGENTS)]
 
 
 class PPOMeter(C.Structure):
@@ -376,6 +386,12 @@ def load(path):
     L.pp_play_group_partial_bytes.argtypes = [i32, i32]
     L.pp_play_group_reset.argtypes = [i32, i32, i32, vp, vp, vp, vp]
     L.pp_play_group_accumulate.argtypes = [vp, vp, i32, i32, i32, i64, vp, vp, vp, vp, vp]
+    # ---- include/ppenv_play_pair.h
+    L.pp_play_pair_ret_bytes.restype = L.pp_play_pair_len_bytes.restype = sz
+    L.pp_play_pair_ret_bytes.argtypes = L.pp_play_pair_len_bytes.argtypes = [i32, i32, i32, i32]
+    L.pp_play_pair_reset.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.pp_play_pair_record.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    L.pp_play_pair_reduce.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     # ---- include/ppenv_ppo_meter.h
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]

@@ -6,6 +6,8 @@
     python -m isaacgym_amd.play --task ... --checkpoint runs/.../nn/<task>.pth [--capture out.gif --capture-envs 0,1 --capture-samples 2 --camera side --capture-deferred --capture-trajectory out.npz]
     python -m isaacgym_amd.play ... --sweep link_mass_scale=0.7:1.3:4 --sweep friction_scale=0.5,1.0 [--sweep-out cells.json]      one pass over the grid
     python -m isaacgym_amd.play ... --sweep serve_speed=7.5:9:4 --sweep friction_scale=0.5,1.0 --paired                            serves swept too, every cell playing the same balls
+    python -m isaacgym_amd.play ... --sweep friction_scale=0.5,1.0 --paired --paired-diff --baseline 1 [--paired-out diff.json]    every cell minus cell 1, on the same balls
+    python -m isaacgym_amd.play ... --against other.pth [--against third.pth] [--sweep friction_scale=0.5,1.0]                     checkpoints A/B on the same balls
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -41,8 +43,14 @@ difference, and groups whose cells are equal are bitwise replicas of each other 
 unpaired one, so it is conservative for differences between paired cells.  The sampler's exploration noise (`--stochastic`) is keyed by
 row and is not paired.
 
+Paired differences and checkpoint A/B.  `Player(..., sweep=Sweep(..., paired=True), paired_diff=True, baseline=0)` records the return of
+the first M episodes of every env on the device (include/ppenv_play_pair.h) and reports, per cell, the mean of
+return(cell, env i, episode m) - return(baseline, env i, episode m) over the pairs (i, m) with ITS OWN standard error — the error bar
+pairing was built to shrink.  `policy` may be a sequence, one policy per cell: two checkpoints play the same balls in one run
+(`--against other.pth`), the cells being checkpoints x sweep cells and the baseline of each the same physics under `--checkpoint`.
+
 Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
-paired sampler noise, paired statistics (the standard error of a paired difference), anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
+paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
 `--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
 """
@@ -59,6 +67,7 @@ import torch
 
 from . import _lib, serve
 from ._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ctypes mirror of ppenv_play_totals (bound in _lib.load)
+from ._lib import PlayPairTotals             # ... and of pp_play_pair_totals
 from ._lib import TA_OUTCOME_NAMES, TAOutcome
 from .dr import TABLE_NAMES
 
@@ -199,6 +208,107 @@ class EpisodeStats(GroupStats):
         launch, before the accumulate of the same control step: `latched` then stops with the totals."""
         _lib.check(self.L.pp_ta_outcome_latch(live.data_ptr(), self._totals.data_ptr(), self.games_num, latched.data_ptr(), _lib.stream(self.device)),
                    self.L)
+
+
+def pair_totals_dict(t, num_agents=MAX_AGENTS):
+    """PlayPairTotals -> a Python dict (the per-agent sums as lists of num_agents; the struct's `cell` and `base` are cell_sum and base_sum)."""
+    return dict(pairs=int(t.pairs), steps_diff=int(t.steps_diff), diff=list(t.diff)[:num_agents], diff_sq=list(t.diff_sq)[:num_agents],
+                cell_sum=list(t.cell)[:num_agents], base_sum=list(t.base)[:num_agents])
+
+
+def pair_summary(cell, baseline, totals, num_agents=1):
+    """One entry of run()'s paired_diff["cells"] from a pair_totals_dict: over the n = pairs pairs (env i, episode m) both cells played,
+    diff = sum(d) / n with d = return(cell) - return(baseline), diff_stderr = sqrt((sum(d^2) - sum(d)^2 / n) / (n - 1) / n) — the standard
+    error of the mean of the paired differences, nan for n < 2 — cell_mean and base_mean the two means over the SAME pairs (not the
+    av_reward of `groups`, which is over the first games to finish), steps_diff the mean difference of the episode lengths; agent 0's
+    figures at the top, all agents' under per_agent.  With no pair the means are nan."""
+    n = int(totals["pairs"])
+    per_agent = []
+    for a in range(num_agents):
+        sd, sq = totals["diff"][a], totals["diff_sq"][a]
+        mean = sd / n if n > 0 else float("nan")
+        stderr = math.sqrt(max(sq - sd * sd / n, 0.0) / (n - 1) / n) if n >= 2 else float("nan")
+        per_agent.append(dict(diff=mean, diff_stderr=stderr, cell_mean=totals["cell_sum"][a] / n if n > 0 else float("nan"),
+                              base_mean=totals["base_sum"][a] / n if n > 0 else float("nan")))
+    out = dict(cell=int(cell), baseline=int(baseline), pairs=n)
+    out.update(per_agent[0])
+    out["steps_diff"] = totals["steps_diff"] / n if n > 0 else float("nan")
+    out["per_agent"] = per_agent
+    return out
+
+
+class PairStats:
+    """pp_play_pair_reset / _record / _reduce (include/ppenv_play_pair.h) on torch tensors: for `groups` cells of `envs_per_group` envs
+    that are served the same balls, the returns and lengths of the first `episodes` episodes of every env, and read(): per cell the fp64
+    sums of the paired difference against cell baseline[g].  baseline: one cell index for all cells, or a sequence of `groups` of them.
+    One launch per record(), nothing here synchronises except read() (one more launch and one host copy of groups x 80 bytes)."""
+
+    def __init__(self, envs_per_group, groups, num_agents, episodes, baseline, device):
+        self.envs_per_group, self.groups, self.num_agents, self.episodes = S, G, A, M = int(envs_per_group), int(groups), int(num_agents), int(episodes)
+        if S < 1 or not 1 <= G <= MAX_GROUPS or A not in (1, 2) or M < 1 or S * G * M * A > 2 ** 31 - 1:
+            raise ValueError(f"PairStats: envs_per_group {envs_per_group} (>= 1), groups {groups} (1..{MAX_GROUPS}), num_agents {num_agents} (1 or 2), "
+                             f"episodes {episodes} (>= 1), at most 2^31 - 1 table entries")
+        self.baseline = baseline_cells(baseline, G)
+        self.device = dev = torch.device(device)
+        self.num_envs, self.rows = S * G, S * G * A
+        self.L = _lib.lib()
+        self.cur_reward = torch.zeros(self.rows, dtype=torch.float32, device=dev)
+        self.cur_steps = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self.count = torch.zeros(self.num_envs, dtype=torch.int32, device=dev)
+        self.ret = torch.zeros((G, S, M, A), dtype=torch.float32, device=dev)
+        self.len = torch.zeros((G, S, M), dtype=torch.int32, device=dev)
+        assert self.ret.numel() * 4 == self.L.pp_play_pair_ret_bytes(S, G, A, M) and self.len.numel() * 4 == self.L.pp_play_pair_len_bytes(S, G, A, M)
+        self._baseline = torch.tensor(self.baseline, dtype=torch.int32, device=dev)
+        self._out = torch.zeros(G * C.sizeof(PlayPairTotals), dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def _sizes(self):
+        return self.envs_per_group, self.groups, self.num_agents, self.episodes
+
+    def _state(self):
+        return self.cur_reward.data_ptr(), self.cur_steps.data_ptr(), self.count.data_ptr(), self.ret.data_ptr(), self.len.data_ptr()
+
+    def reset(self):
+        _lib.check(self.L.pp_play_pair_reset(*self._sizes(), *self._state(), _lib.stream(self.device)), self.L)
+
+    def record(self, rew, done):
+        """One control step, after the env step: rew [rows] f32, done [rows] int64 as for GroupStats.accumulate.  One launch."""
+        if rew.dtype != torch.float32 or done.dtype != torch.int64 or rew.numel() != self.rows or done.numel() != self.rows or \
+                not rew.is_contiguous() or not done.is_contiguous() or rew.device != self.device or done.device != self.device:
+            raise ValueError(f"PairStats.record: rew must be float32 and done int64, contiguous [{self.rows}] on {self.device}")
+        _lib.check(self.L.pp_play_pair_record(rew.data_ptr(), done.data_ptr(), *self._sizes(), *self._state(), _lib.stream(self.device)), self.L)
+
+    def reduce(self):
+        """The reduce launch alone: the `groups` structs as host bytes (the stream is waited for)."""
+        _lib.check(self.L.pp_play_pair_reduce(*self._sizes(), self._baseline.data_ptr(), self.count.data_ptr(), self.ret.data_ptr(), self.len.data_ptr(),
+                                              self._out.data_ptr(), _lib.stream(self.device)), self.L)
+        return self._out.cpu().numpy().tobytes()
+
+    def read(self):
+        """-> a list of pair_totals_dict, in cell order, each with its `cell` and `baseline` index."""
+        raw, n = self.reduce(), C.sizeof(PlayPairTotals)
+        return [dict(pair_totals_dict(PlayPairTotals.from_buffer_copy(raw[g * n:(g + 1) * n]), self.num_agents), cell=g, baseline=self.baseline[g])
+                for g in range(self.groups)]
+
+    def state_bytes(self):
+        """cur_reward, cur_steps, count, ret and len as host bytes (the tests compare them)."""
+        return tuple(t.cpu().numpy().tobytes() for t in (self.cur_reward, self.cur_steps, self.count, self.ret, self.len))
+
+
+def baseline_cells(baseline, groups):
+    """An int (one baseline cell for all) or a sequence of `groups` cell indices -> the list of `groups` indices; ValueError for an
+    index outside 0 .. groups - 1 or a sequence of another length."""
+    if isinstance(baseline, (int, np.integer)):
+        cells = [int(baseline)] * groups
+    else:
+        cells = list(baseline)
+        if len(cells) != groups or any(not isinstance(b, (int, np.integer)) for b in cells):
+            raise ValueError(f"baseline: one cell index, or a sequence of {groups} of them (one per cell), not {baseline!r}")
+        cells = [int(b) for b in cells]
+    bad = [b for b in cells if not 0 <= b < groups]
+    if bad:
+        raise ValueError(f"baseline: cell {bad[0]} is outside 0..{groups - 1}")
+    return cells
 
 
 _AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
@@ -358,6 +468,13 @@ def group_line(g):
             f"min {g['reward_min']:.6g} max {g['reward_max']:.6g}" + ("" if g["complete"] else " (incomplete)"))
 
 
+def pair_line(p, groups, full):
+    """The CLI's line for one entry of paired_diff["cells"]; groups: the result's `groups` (the cells' texts), full: the S * M pairs a
+    complete cell has."""
+    return (f"cell {p['cell']} {cell_text(groups[p['cell']]['cell'])}: vs cell {p['baseline']}: pairs {p['pairs']} diff {p['diff']:.6g} +- {p['diff_stderr']:.3g} "
+            f"(cell {p['cell_mean']:.6g}, base {p['base_mean']:.6g}) steps diff {p['steps_diff']:.6g}" + ("" if p["pairs"] == full else " (incomplete)"))
+
+
 class Player:
     """rl_games' BasePlayer.run on a task from isaacgym_amd.make(...) (any of the five registry names; the 4-actor task has two rows per
     env) under an RLGamesPolicy.  The defaults are rl_games' player defaults.
@@ -379,10 +496,20 @@ class Player:
     whose cells are equal are bitwise replicas of each other under deterministic play; `reward_stderr` stays the unpaired one, conservative
     for differences between paired cells; the sampler's exploration noise (deterministic=False) is keyed by row and is not paired.
     Refused with a sweep: a task with `randomize: True` (its tables are the sweep's) and
-    outcomes=True (the 27-dof counts are cross-env windows and cannot be split by group)."""
+    outcomes=True (the 27-dof counts are cross-env windows and cannot be split by group).
+    paired_diff: with a paired sweep, a PairStats (include/ppenv_play_pair.h) records the first pair_episodes episodes of EVERY env —
+    default ceil(games_num / S), S the envs per cell — in one more launch per control step, and run() ends at the first poll at which every
+    group is frozen AND every cell has all S * pair_episodes pairs (or at max_steps).  The group totals freeze on their own, so `groups`
+    and the summed figures are byte for byte those of the run without paired_diff; only steps_played and seconds may grow.  The result
+    gains `paired_diff` = dict(episodes, complete, cells=[pair_summary of cell g against cell baseline[g]]); baseline: one cell index for
+    all cells, or one per cell.  A cell against itself gives diff 0.0 and diff_stderr 0.0.
+    policy: one RLGamesPolicy, or a sequence of len(sweep) of them — cell g is then played by policy[g] on its rows
+    [A * S * g, A * S * (g + 1)); consecutive cells holding the same object are forwarded in one act().  `policy` stays the first one,
+    `policies` is the list; sigma is applied to each, start() zeroes each one's draw counter.  Under deterministic=False the exploration
+    noise is keyed by row and by each policy's own counter: it is NOT paired, neither across cells nor across checkpoints."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
-                 outcomes=False, sweep=None):
+                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -391,20 +518,34 @@ class Player:
                 raise ValueError("outcomes=True with a sweep: the 27-dof outcome counts are cross-env reset windows and cannot be split by group")
             if getattr(task, "randomize", False):
                 raise ValueError("a sweep on a task with randomize: True: the sweep sets the task's randomisation tables itself; set task.randomize=False")
+        per_cell = isinstance(policy, (list, tuple))
+        if per_cell and (sweep is None or len(policy) != len(sweep)):
+            raise ValueError("a sequence of policies is one policy per cell of a sweep: " +
+                             ("there is no sweep" if sweep is None else f"the sweep has {len(sweep)} cells, the sequence {len(policy)} policies"))
+        if paired_diff:
+            if sweep is None or not sweep.paired:
+                raise ValueError("paired_diff=True needs a sweep with paired=True: without common serves, episode m of env i is a different ball in every cell")
+            self._baseline = baseline_cells(baseline, len(sweep))
+            if pair_episodes is not None and (int(pair_episodes) != pair_episodes or int(pair_episodes) < 1):
+                raise ValueError(f"pair_episodes: {pair_episodes!r} is not a positive integer")
+        self.policies = list(policy) if per_cell else [policy]
         rl, sim = torch.device(task.rl_device), torch.device(task.device)
         if rl != sim or sim.type != "cuda":
             raise ValueError(f"Player needs rl_device == sim_device on a GPU (no per-step copies): rl_device is {rl}, sim_device is {sim}")
-        if torch.device(policy.device) != sim:
-            raise ValueError(f"the policy lives on {policy.device}, the task on {sim}")
-        if policy.net.num_obs != task.num_obs or policy.net.num_actions != task.num_actions:
-            raise ValueError(f"the policy maps {policy.net.num_obs} observations to {policy.net.num_actions} actions, the task has "
-                             f"{task.num_obs} and {task.num_actions}")
-        self.task, self.policy = task, policy
+        for p in self.policies:
+            if torch.device(p.device) != sim:
+                raise ValueError(f"the policy lives on {p.device}, the task on {sim}")
+            if p.net.num_obs != task.num_obs or p.net.num_actions != task.num_actions:
+                raise ValueError(f"the policy maps {p.net.num_obs} observations to {p.net.num_actions} actions, the task has "
+                                 f"{task.num_obs} and {task.num_actions}")
+        self.task, self.policy = task, self.policies[0]
         self.games_num, self.poll_every, self.max_steps = int(games_num), int(poll_every), int(max_steps)
         self.deterministic, self.seed = bool(deterministic), int(seed)
         self.num_agents = int(getattr(task, "num_agents", 1))
+        self._distinct = list({id(p): p for p in self.policies}.values())
         if sigma is not None:
-            policy.sigma.fill_(math.exp(float(sigma)))
+            for p in self._distinct:
+                p.sigma.fill_(math.exp(float(sigma)))
         self.sweep = sweep
         self._tables = self._episode0 = self._serve_cells = None
         if sweep is None:
@@ -414,6 +555,20 @@ class Player:
             if sweep.paired or any(a in SERVE_AXES for cell in sweep.cells for a in cell):
                 self._serve_cells = sweep.serve_cells(task.env.serve_defaults())
             self.stats = GroupStats(task.num_envs // len(sweep), len(sweep), self.num_agents, self.games_num, sim)
+        self.pairs = None
+        if paired_diff:
+            S = task.num_envs // len(sweep)
+            self.pair_episodes = int(pair_episodes) if pair_episodes is not None else -(-self.games_num // S)
+            self.pairs = PairStats(S, len(sweep), self.num_agents, self.pair_episodes, self._baseline, sim)
+        self._runs = self._cell_actions = None
+        if per_cell:                                                      # runs of consecutive cells that hold the same object: (policy, first row, end row)
+            w, runs = self.num_agents * (task.num_envs // len(sweep)), []
+            for g, p in enumerate(self.policies):
+                if runs and runs[-1][0] is p:
+                    runs[-1][2] = w * (g + 1)
+                else:
+                    runs.append([p, w * g, w * (g + 1)])
+            self._runs = [tuple(r) for r in runs]
         if recorder is not None and recorder.renderer.task is not task:
             raise ValueError("the recorder renders another task")
         self.recorder = recorder
@@ -461,19 +616,37 @@ class Player:
         if self.outcome is not None:
             self.outcome.zero_()
             self._latched.zero_()
-        self.policy._counter = 0
+        if self.pairs is not None:
+            self.pairs.reset()
+        for p in self._distinct:
+            p._counter = 0
         self._obs = self.task.reset()["obs"]
         self.steps_played = 0
 
+    def _act_per_cell(self):
+        """Every run of cells under its own policy, into ONE [rows, num_actions] tensor: a policy owns its output buffer and may serve
+        several runs, so each result is copied out before the next act()."""
+        if self._cell_actions is None:
+            self._cell_actions = torch.empty((self._obs.shape[0], self.task.num_actions), dtype=torch.float32, device=self._obs.device)
+        for p, r0, r1 in self._runs:
+            a, _ = p.act(self._obs[r0:r1], deterministic=self.deterministic, seed=self.seed)
+            self._cell_actions[r0:r1].copy_(a)
+        return self._cell_actions
+
     def step(self):
-        """One control step: policy -> task.step -> accumulate.  No host read."""
+        """One control step: policy -> task.step -> accumulate (-> record, with paired_diff).  No host read."""
         if self._obs is None:
             self.start()
-        self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
+        if self._runs is None:
+            self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
+        else:
+            self.actions = self._act_per_cell()
         obs, rew, done, _ = self.task.step(self.actions)
         if self.outcome is not None:
             self.stats.latch_outcome(self.outcome, self._latched)
         self.stats.accumulate(rew, done)
+        if self.pairs is not None:
+            self.pairs.record(rew, done)
         if self.recorder is not None:
             self.recorder.capture()
         self._obs = obs["obs"]
@@ -489,10 +662,12 @@ class Player:
         """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
         host read.  -> dict(games, av_reward, av_steps, reward_std, reward_min, reward_max, per_agent=[...], steps_played, seconds); with
         outcomes=True also `outcomes` (outcomes_dict of the latched struct).  With a sweep: until EVERY group has counted games_num games;
-        on_poll gets the groups' totals summed (sum_totals), the result is summarize() of that sum plus `groups`."""
+        on_poll gets the groups' totals summed (sum_totals), the result is summarize() of that sum plus `groups`.  With paired_diff:
+        until also every cell has all its pairs; the result gains `paired_diff`."""
         try:
             self.start()
             t0 = time.perf_counter()
+            full = self.pairs.envs_per_group * self.pairs.episodes if self.pairs is not None else 0
             while True:
                 self.step()
                 last = self.steps_played >= self.max_steps
@@ -501,12 +676,19 @@ class Player:
                     tot = per[0] if self.sweep is None else sum_totals(per)
                     if on_poll is not None:
                         on_poll(tot)
-                    if last or all(t["games"] >= self.games_num for t in per):
+                    frozen = all(t["games"] >= self.games_num for t in per)
+                    if self.pairs is not None and (last or frozen):      # the reduce is idempotent: launched only where the answer is needed
+                        pairs = self.pairs.read()
+                        frozen = frozen and all(p["pairs"] == full for p in pairs)
+                    if last or frozen:
                         break
             out = summarize(tot, self.num_agents)
             out.update(steps_played=self.steps_played, seconds=time.perf_counter() - t0)
             if self.sweep is not None:
                 out["groups"] = [group_summary(cell, t, self.num_agents, self.games_num, self.sweep.paired) for cell, t in zip(self.sweep.cells, per)]
+            if self.pairs is not None:
+                out["paired_diff"] = dict(episodes=self.pair_episodes, complete=all(p["pairs"] == full for p in pairs),
+                                          cells=[pair_summary(p["cell"], p["baseline"], p, self.num_agents) for p in pairs])
             if self.outcome is not None:
                 out["outcomes"] = self.read_outcomes()
             if self.recorder is not None:
@@ -537,6 +719,13 @@ def parse_args(argv=None):
     ap.add_argument("--paired", action="store_true", help="with --sweep: env i of every cell is served the same sequence of balls (common random numbers), "
                     "so the serve noise cancels in the difference of two cells")
     ap.add_argument("--sweep-out", default=None, metavar="FILE.json", help="with --sweep: write the per-cell results (the result's `groups`) to FILE.json")
+    ap.add_argument("--paired-diff", action="store_true", help="with --sweep ... --paired: per cell, the mean of return(cell) - return(baseline cell) over the "
+                    "same balls (env i, episode m of both cells), with its own standard error")
+    ap.add_argument("--baseline", type=int, default=None, metavar="INDEX", help="with --paired-diff: the baseline cell, in the order the cells are printed (default 0)")
+    ap.add_argument("--paired-out", default=None, metavar="FILE.json", help="with --paired-diff or --against: write the result's `paired_diff` to FILE.json")
+    ap.add_argument("--against", action="append", default=None, metavar="PATH", help="another checkpoint to play on the same balls (repeatable): the cells become "
+                    "checkpoints x sweep cells, --checkpoint's first (without --sweep: one cell per checkpoint); implies --paired and --paired-diff, the "
+                    "baseline of every cell being the same sweep cell under --checkpoint; --num-envs must be a multiple of the cell count")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -554,6 +743,18 @@ def parse_args(argv=None):
         ap.error("--sweep-out needs --sweep")
     if args.paired and not args.sweep:
         ap.error("--paired needs --sweep")
+    if args.against:
+        if args.baseline is not None:
+            ap.error("--baseline does not go with --against: the baseline of every cell is the same sweep cell under --checkpoint")
+        if args.outcomes:
+            ap.error("--against plays the checkpoints as the cells of a sweep, and --outcomes cannot be split by cell")
+    else:
+        if args.paired_diff and not (args.sweep and args.paired):
+            ap.error("--paired-diff needs --sweep ... --paired: without common serves, episode m of env i is a different ball in every cell")
+        if args.baseline is not None and not args.paired_diff:
+            ap.error("--baseline needs --paired-diff")
+        if args.paired_out and not args.paired_diff:
+            ap.error("--paired-out needs --paired-diff or --against")
     if args.sweep:
         try:
             Sweep.parse(args.sweep)
@@ -595,8 +796,20 @@ def main(argv=None):
     policy = RLGamesPolicy.load(args.checkpoint, task.device)
     recorder = make_recorder(task, args) if args.capture or args.capture_trajectory else None
     sweep = Sweep.parse(args.sweep, paired=getattr(args, "paired", False)) if getattr(args, "sweep", None) else None
+    against = getattr(args, "against", None) or []
+    paired_diff, baseline = bool(getattr(args, "paired_diff", False)), getattr(args, "baseline", None) or 0
+    if against:                           # checkpoints x sweep cells, checkpoint-major; cell (k, c) against (0, c)
+        paths = [args.checkpoint] + list(against)
+        cells = sweep.cells if sweep is not None else [{}]
+        nets = [policy] + [RLGamesPolicy.load(p, task.device) for p in against]
+        policy = [net for net in nets for _ in cells]
+        baseline = [c for _ in nets for c in range(len(cells))]
+        sweep, paired_diff = Sweep(cells * len(nets), paired=True), True
+        for k, p in enumerate(paths):
+            print(f"checkpoint {k}: {p}", flush=True)
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
-                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep)
+                max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep, paired_diff=paired_diff,
+                baseline=baseline)
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -615,12 +828,20 @@ def main(argv=None):
         print("\n".join(outcome_lines(res["outcomes"])) if res["outcomes"]["windows"] > 0 else "no env has reset: no outcome window yet")
     for a, p in enumerate(res["per_agent"]):
         print(f"agent {a}: games {res['games']} reward std {p['reward_std']:.6g} min {p['reward_min']:.6g} max {p['reward_max']:.6g} (av {p['av_reward']:.6g})")
-    for g in res.get("groups", ()):
-        print(group_line(g))
+    per_ckpt = len(res.get("groups", ())) // (1 + len(against))               # with --against: cell index -> checkpoint index
+    for i, g in enumerate(res.get("groups", ())):
+        print((f"checkpoint {i // per_ckpt} " if against else "") + group_line(g))
+    if "paired_diff" in res:
+        for p in res["paired_diff"]["cells"]:
+            print(pair_line(p, res["groups"], res["paired_diff"]["episodes"] * (task.num_envs // len(res["groups"]))))
     if getattr(args, "sweep_out", None):
         with open(args.sweep_out, "w") as fh:
             json.dump(res["groups"], fh, indent=1)
         print(f"wrote {args.sweep_out}")
+    if getattr(args, "paired_out", None):
+        with open(args.paired_out, "w") as fh:
+            json.dump(res["paired_diff"], fh, indent=1)
+        print(f"wrote {args.paired_out}")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
     if recorder is not None and args.capture_trajectory:
         print(f"saved {recorder.trajectory.save(args.capture_trajectory, fps=args.capture_fps)} (trajectory)", flush=True)
