@@ -22,7 +22,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_play_pair.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -32,16 +32,19 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_ta_outcome_device.h"), os.path.join(ROOT, "include", "ppenv_ta_outcome.h"),
            os.path.join(_PKG, "csrc", "ppenv_serve_device.h"), os.path.join(ROOT, "include", "ppenv_serve.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair_device.h"), os.path.join(ROOT, "include", "ppenv_play_pair.h"),
+           os.path.join(_PKG, "csrc", "ppenv_play_act_device.h"), os.path.join(ROOT, "include", "ppenv_play_act.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
 # the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);
 # the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign;
-# the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN
+# the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN;
+# the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
-                "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
+                "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
 _lib = None
 
@@ -116,6 +119,41 @@ class PlayPairTotals(C.Structure):
     """ctypes mirror of pp_play_pair_totals (include/ppenv_play_pair.h)."""
     _fields_ = [("pairs", C.c_int64), ("steps_diff", C.c_int64), ("diff", C.c_double * MAX_AGENTS), ("diff_sq", C.c_double * MAX_AGENTS),
                 ("cell", C.c_double * MAX_AGENTS), ("base", C.c_double * MAX_AGENTS)]
+
+
+PLAY_ACT_MAX_DOF, PLAY_ACT_FIELDS = 32, 10                                               # PP_PLAY_ACT_MAX_DOF, PP_PLAY_ACT_FIELDS
+
+
+class PlayActLimit(C.Structure):
+    """ctypes mirror of pp_play_act_limit (include/ppenv_play_act.h)."""
+    _fields_ = [("lower", C.c_float), ("upper", C.c_float), ("effort", C.c_float), ("vel_limit", C.c_float)]
+
+
+class PlayActThresholds(C.Structure):
+    """ctypes mirror of pp_play_act_thresholds."""
+    _fields_ = [("effort_frac", C.c_float), ("vel_frac", C.c_float), ("limit_margin", C.c_float), ("action_clip", C.c_float)]
+
+
+class PlayActInput(C.Structure):
+    """ctypes mirror of pp_play_act_input: value (e, d) = p[e * env_stride + d * dof_stride], strides in elements."""
+    _fields_ = [("p", C.c_void_p), ("env_stride", C.c_int64), ("dof_stride", C.c_int64)]
+
+
+class PlayActInputs(C.Structure):
+    """ctypes mirror of pp_play_act_inputs."""
+    _fields_ = [("q", PlayActInput), ("qd", PlayActInput), ("tau", PlayActInput), ("action", PlayActInput)]
+
+
+class PlayActGroup(C.Structure):
+    """ctypes mirror of pp_play_act_group."""
+    _fields_ = [("games", C.c_int64), ("samples", C.c_int64), ("launches", C.c_int64), ("energy", C.c_double), ("energy_sq", C.c_double)]
+
+
+class PlayActJoint(C.Structure):
+    """ctypes mirror of pp_play_act_joint."""
+    _fields_ = [("c_effort", C.c_int64), ("c_vel", C.c_int64), ("c_limit", C.c_int64), ("c_clip", C.c_int64),
+                ("abs_tau", C.c_double), ("tau_sq", C.c_double), ("power", C.c_double),
+                ("max_abs_tau", C.c_float), ("max_abs_vel", C.c_float), ("max_exc", C.c_float), ("reserved", C.c_float)]
 
 
 class PPOMeter(C.Structure):
@@ -392,6 +430,11 @@ def load(path):
     L.pp_play_pair_reset.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.pp_play_pair_record.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
     L.pp_play_pair_reduce.argtypes = [i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    # ---- include/ppenv_play_act.h
+    L.pp_play_act_state_bytes.restype = L.pp_play_act_partial_bytes.restype = sz
+    L.pp_play_act_state_bytes.argtypes = L.pp_play_act_partial_bytes.argtypes = [i32, i32, i32]
+    L.pp_play_act_reset.argtypes = [i32, i32, i32, vp, vp, vp, vp]
+    L.pp_play_act_accumulate.argtypes = [C.POINTER(PlayActInputs), vp, i32, i32, i32, i32, i64, vp, C.POINTER(PlayActThresholds), vp, vp, vp, vp, vp]
     # ---- include/ppenv_ppo_meter.h
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]

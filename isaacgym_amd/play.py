@@ -9,6 +9,8 @@
     python -m isaacgym_amd.play ... --sweep friction_scale=0.5,1.0 --paired --paired-diff --baseline 1 [--paired-out diff.json]    every cell minus cell 1, on the same balls
     python -m isaacgym_amd.play ... --against other.pth [--against third.pth] [--sweep friction_scale=0.5,1.0]                     checkpoints A/B on the same balls
 
+    python -m isaacgym_amd.play ... --actuators --sweep link_mass_scale=0.7:1.3:3 [--actuators-out act.json]                       per cell, a per-joint table: torque, speed, limits, energy
+
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
 (`all_done_indices[::num_agents]`: an env of the two-agent task counts once, on agent 0's row), their returns and lengths go into the
@@ -48,6 +50,13 @@ the first M episodes of every env on the device (include/ppenv_play_pair.h) and 
 return(cell, env i, episode m) - return(baseline, env i, episode m) over the pairs (i, m) with ITS OWN standard error — the error bar
 pairing was built to shrink.  `policy` may be a sequence, one policy per cell: two checkpoints play the same balls in one run
 (`--against other.pth`), the cells being checkpoints x sweep cells and the baseline of each the same physics under `--checkpoint`.
+
+Actuator usage.  `Player(..., actuators=True)` / `--actuators` answers how the return is earned on the robot: per joint and per cell the mean,
+rms and peak drive torque against the effort limit, the peak speed against the velocity limit, the share of samples at a position limit,
+the mechanical energy of a game (the reward's power term sum |tau * qd|, times the control dt) and the share of raw actions at clipActions.
+`ActuatorStats` (include/ppenv_play_act.h) reads the env's own joint tensors and the policy's own action tensor where they lie — the 7-dof
+SoA planes, the 27-dof AoS rows — in two launches per control step, under the totals' freeze; an env that has just finished is not
+sampled (its tensors already hold the next episode's reset state), so a game of L steps gives L - 1 samples.
 
 Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
 paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
@@ -311,6 +320,166 @@ def baseline_cells(baseline, groups):
     return cells
 
 
+ACT_THRESHOLDS = dict(effort_frac=0.98, vel_frac=0.98, limit_margin=0.02)     # Player(actuators=True)'s; action_clip is the task's clipActions
+ACT_INT_FIELDS, ACT_SUM_FIELDS, ACT_MAX_FIELDS = ("c_effort", "c_vel", "c_limit", "c_clip"), ("abs_tau", "tau_sq", "power"), ("max_abs_tau", "max_abs_vel", "max_exc")
+
+
+def act_totals_dict(group, joints):
+    """A PlayActGroup and its D PlayActJoint -> a Python dict: games, samples, launches, energy, energy_sq and, per joint field, a list of D."""
+    out = dict(games=int(group.games), samples=int(group.samples), launches=int(group.launches), energy=float(group.energy), energy_sq=float(group.energy_sq))
+    for k in ACT_INT_FIELDS:
+        out[k] = [int(getattr(j, k)) for j in joints]
+    for k in ACT_SUM_FIELDS + ACT_MAX_FIELDS:
+        out[k] = [float(getattr(j, k)) for j in joints]
+    return out
+
+
+def sum_act_totals(per_group):
+    """A list of act_totals_dict -> one over all groups: counts and sums added in group order, the maxima merged."""
+    D = len(per_group[0]["abs_tau"])
+    out = dict(games=0, samples=0, launches=0, energy=0.0, energy_sq=0.0, **{k: [0] * D for k in ACT_INT_FIELDS}, **{k: [0.0] * D for k in ACT_SUM_FIELDS},
+               max_abs_tau=[0.0] * D, max_abs_vel=[0.0] * D, max_exc=[-math.inf] * D)
+    for t in per_group:
+        for k in ("games", "samples", "launches", "energy", "energy_sq"):
+            out[k] += t[k]
+        for d in range(D):
+            for k in ACT_INT_FIELDS + ACT_SUM_FIELDS:
+                out[k][d] += t[k][d]
+            for k in ACT_MAX_FIELDS:
+                out[k][d] = max(out[k][d], t[k][d])
+    return out
+
+
+def actuator_summary(totals, limits, names, control_dt):
+    """One entry of run()'s actuators["total"] / ["groups"] from an act_totals_dict.  With n = games and s = samples (a game of L control
+    steps gives L - 1): energy_per_game [J] = control_dt * energy / n, energy_stderr = control_dt * sqrt((energy_sq - energy^2 / n) / (n - 1) / n)
+    (nan for n < 2), mean_power [W] = energy / s — the power term sum_d |tau * qd| averaged over the samples — and `per_joint`, one dict per
+    joint: tau_mean_abs, tau_rms, tau_peak [N m], tau_peak_frac = tau_peak / effort, vel_peak [rad / s], vel_peak_frac = vel_peak / vel_limit,
+    excursion_max [rad] = the largest of max(lower - q, q - upper) (positive: beyond the limit; -inf with no sample), power_mean [W], and the
+    rates over the samples at_effort, at_vel_limit, at_pos_limit, action_clip.  The per-sample figures are nan with no sample."""
+    n, s, nan = int(totals["games"]), int(totals["samples"]), float("nan")
+    e, esq, dt = totals["energy"], totals["energy_sq"], float(control_dt)
+    out = dict(games=n, samples=s, energy_per_game=dt * e / n if n > 0 else nan,
+               energy_stderr=dt * math.sqrt(max(esq - e * e / n, 0.0) / (n - 1) / n) if n >= 2 else nan, mean_power=e / s if s > 0 else nan)
+    rate = (lambda v: v / s) if s > 0 else (lambda v: nan)
+    out["per_joint"] = [dict(joint=names[d], tau_mean_abs=rate(totals["abs_tau"][d]), tau_rms=math.sqrt(rate(totals["tau_sq"][d])) if s > 0 else nan,
+                             tau_peak=totals["max_abs_tau"][d], tau_peak_frac=totals["max_abs_tau"][d] / float(limits[d][2]), at_effort=rate(totals["c_effort"][d]),
+                             vel_peak=totals["max_abs_vel"][d], vel_peak_frac=totals["max_abs_vel"][d] / float(limits[d][3]), at_vel_limit=rate(totals["c_vel"][d]),
+                             at_pos_limit=rate(totals["c_limit"][d]), excursion_max=totals["max_exc"][d], power_mean=rate(totals["power"][d]),
+                             action_clip=rate(totals["c_clip"][d])) for d in range(len(names))]
+    return out
+
+
+def actuator_table(entry, title=""):
+    """The CLI's table for one entry of actuators["groups"] (or its total): a head line, then one row per joint."""
+    lines = [f"actuators {title}: games {entry['games']} samples {entry['samples']} energy/game {entry['energy_per_game']:.6g} +- {entry['energy_stderr']:.3g} J "
+             f"mean power {entry['mean_power']:.6g} W",
+             f"  {'joint':<28}{'|tau| mean':>11}{'rms':>9}{'peak':>9}{'/effort':>8}{'at eff':>8}{'vel peak':>10}{'/limit':>8}{'at vel':>8}{'at pos':>8}"
+             f"{'exc max':>9}{'power':>9}{'act clip':>9}"]
+    for j in entry["per_joint"]:
+        lines.append(f"  {j['joint']:<28}{j['tau_mean_abs']:>11.4g}{j['tau_rms']:>9.4g}{j['tau_peak']:>9.4g}{j['tau_peak_frac']:>8.3f}{j['at_effort']:>8.3f}"
+                     f"{j['vel_peak']:>10.4g}{j['vel_peak_frac']:>8.3f}{j['at_vel_limit']:>8.3f}{j['at_pos_limit']:>8.3f}{j['excursion_max']:>9.3g}"
+                     f"{j['power_mean']:>9.4g}{j['action_clip']:>9.3f}")
+    return "\n".join(lines)
+
+
+def actuator_limits(task):
+    """The joints' limits from the numbers the step kernels themselves run with -> (float32 [D, 4]: lower, upper, effort, vel_limit; the D
+    joint names).  A 7-dof task: the `joint` entries of its native config (ppenv_joint), once per humanoid — the 4-actor task's 14 dofs are
+    h1/..., h2/...; the 27-dof task: links 1..27 (ppenv_ta_link) of the model its simulation was created with.  Names are scene.G1_RIGHT_ARM's
+    / urdf.ta_dof_joint_names() where they fit, else dof<i>."""
+    from . import scene, urdf
+    if hasattr(task, "native_config"):
+        joints = list(task.native_config.joint)
+        names = [s["name"][:-5] + "_joint" if s["name"].endswith("_link") else s["name"] for s in scene.G1_RIGHT_ARM]
+        A = int(getattr(task, "num_agents", 1))
+    else:
+        joints = list(task.env.sim.model.link)[1:]
+        names, A = urdf.ta_dof_joint_names(), 1
+    if len(names) != len(joints):
+        names = [f"dof{i}" for i in range(len(joints))]
+    table = np.array([[j.lower, j.upper, j.effort, j.vel_limit] for j in joints] * A, np.float32)
+    if A > 1:
+        names = [f"h{a + 1}/{n}" for a in range(A) for n in names]
+    return table, list(names)
+
+
+def control_dt_of(task):
+    """Seconds per control step: the native config's dt (controlFrequencyInv already folded in), the 27-dof simulation's scene dt."""
+    return float(task.native_config.dt if hasattr(task, "native_config") else task.env.sim.scene.dt)
+
+
+class ActuatorStats:
+    """pp_play_act_reset / pp_play_act_accumulate (include/ppenv_play_act.h) on torch tensors: per joint, torque / speed / position / power /
+    action usage of `groups` populations of `envs_per_group` envs with `num_dofs` joints each, folded into per-group totals when an env
+    finishes a game, each group freezing on its own at games_num.  limits: [D, 4] (lower, upper, effort, vel_limit); thresholds:
+    dict(effort_frac, vel_frac, limit_margin, action_clip).  Two launches per accumulate, nothing here synchronises except read() /
+    state_bytes()."""
+
+    def __init__(self, envs_per_group, groups, num_dofs, games_num, limits, thresholds, device, num_agents=1):
+        self.envs_per_group, self.groups, self.num_dofs, self.games_num, self.num_agents = S, G, D, _, A = \
+            int(envs_per_group), int(groups), int(num_dofs), int(games_num), int(num_agents)
+        if S < 1 or not 1 <= G <= MAX_GROUPS or A not in (1, 2) or not 1 <= D <= _lib.PLAY_ACT_MAX_DOF or D % A or self.games_num < 1 or S * G * A > 2 ** 31 - 1:
+            raise ValueError(f"ActuatorStats: envs_per_group {envs_per_group} (>= 1), groups {groups} (1..{MAX_GROUPS}), num_agents {num_agents} (1 or 2), "
+                             f"num_dofs {num_dofs} (1..{_lib.PLAY_ACT_MAX_DOF}, a multiple of num_agents), games_num {games_num} (>= 1), at most 2^31 - 1 rows")
+        lim = np.ascontiguousarray(limits, np.float32)
+        if lim.shape != (D, 4):
+            raise ValueError(f"ActuatorStats: limits must be [{D}, 4] (lower, upper, effort, vel_limit), not {list(lim.shape)}")
+        self.thresholds = {k: float(thresholds[k]) for k in ("effort_frac", "vel_frac", "limit_margin", "action_clip")}
+        self._thr = _lib.PlayActThresholds(**self.thresholds)
+        self.device = dev = torch.device(device)
+        self.num_envs = S * G
+        L = self.L = _lib.lib()
+        self.limits = lim
+        self._limits = torch.from_numpy(lim).to(dev)
+        self._state = torch.zeros(int(L.pp_play_act_state_bytes(S, G, D)), dtype=torch.uint8, device=dev)
+        self._group = torch.zeros(G * C.sizeof(_lib.PlayActGroup), dtype=torch.uint8, device=dev)
+        self._joint = torch.zeros(G * D * C.sizeof(_lib.PlayActJoint), dtype=torch.uint8, device=dev)
+        self._partial = torch.zeros(int(L.pp_play_act_partial_bytes(S, G, D)), dtype=torch.uint8, device=dev)
+        self.reset()
+
+    def reset(self):
+        _lib.check(self.L.pp_play_act_reset(self.envs_per_group, self.groups, self.num_dofs, self._state.data_ptr(), self._group.data_ptr(),
+                                            self._joint.data_ptr(), _lib.stream(self.device)), self.L)
+
+    def _input(self, name, t):
+        """A float32 tensor holding value (e, d) -> PlayActInput: a [N, D] view with ANY strides (env.dof_pos.T, dof_states[..., 0]) is
+        taken by its strides; a contiguous tensor of N * D elements in another shape (the [A * N, D / A] actions) is read row-major."""
+        N, D = self.num_envs, self.num_dofs
+        if t is None:
+            return _lib.PlayActInput(None, 0, 0)
+        if t.dtype != torch.float32 or t.device != self.device or t.numel() != N * D or not (tuple(t.shape) == (N, D) or t.is_contiguous()):
+            raise ValueError(f"ActuatorStats.accumulate: {name} must be float32 on {self.device}, a [{N}, {D}] view or contiguous with {N * D} elements")
+        es, ds = t.stride() if tuple(t.shape) == (N, D) else (D, 1)
+        return _lib.PlayActInput(t.data_ptr(), es, ds)
+
+    def accumulate(self, q, qd, tau, action, done):
+        """One control step, after the env step: joint positions, velocities, drive torques and (or None) the policy's raw actions as
+        tensors holding value (env, dof) — see _input — and done [num_agents * N] int64 (VecTask.step's reset_buf).  Two launches, no
+        synchronisation, no copy."""
+        if done.dtype != torch.int64 or done.numel() != self.num_envs * self.num_agents or not done.is_contiguous() or done.device != self.device:
+            raise ValueError(f"ActuatorStats.accumulate: done must be int64, contiguous [{self.num_envs * self.num_agents}] on {self.device}")
+        ins = _lib.PlayActInputs(self._input("q", q), self._input("qd", qd), self._input("tau", tau), self._input("action", action))
+        _lib.check(self.L.pp_play_act_accumulate(C.byref(ins), done.data_ptr(), self.envs_per_group, self.groups, self.num_agents, self.num_dofs, self.games_num,
+                                                 self._limits.data_ptr(), C.byref(self._thr), self._state.data_ptr(), self._group.data_ptr(),
+                                                 self._joint.data_ptr(), self._partial.data_ptr(), _lib.stream(self.device)), self.L)
+
+    def read(self):
+        """One host copy of the totals (the stream is waited for) -> a list of act_totals_dict, in group order."""
+        _, graw, jraw = self.state_bytes(state=False)
+        D, ng, nj = self.num_dofs, C.sizeof(_lib.PlayActGroup), C.sizeof(_lib.PlayActJoint)
+        return [act_totals_dict(_lib.PlayActGroup.from_buffer_copy(graw[g * ng:(g + 1) * ng]),
+                                [_lib.PlayActJoint.from_buffer_copy(jraw[(g * D + d) * nj:(g * D + d + 1) * nj]) for d in range(D)]) for g in range(self.groups)]
+
+    def state_bytes(self, state=True):
+        """The running state, the G group structs and the G * D joint structs as host bytes (the tests compare them)."""
+        return (self._state.cpu().numpy().tobytes() if state else b"", self._group.cpu().numpy().tobytes(), self._joint.cpu().numpy().tobytes())
+
+    def partial_bytes(self):
+        """The last launch's per-chunk partials as host bytes: G * parts group structs, then G * parts * D joint structs."""
+        return self._partial.cpu().numpy().tobytes()
+
+
 _AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
 
 
@@ -506,10 +675,16 @@ class Player:
     policy: one RLGamesPolicy, or a sequence of len(sweep) of them — cell g is then played by policy[g] on its rows
     [A * S * g, A * S * (g + 1)); consecutive cells holding the same object are forwarded in one act().  `policy` stays the first one,
     `policies` is the list; sigma is applied to each, start() zeroes each one's draw counter.  Under deterministic=False the exploration
-    noise is keyed by row and by each policy's own counter: it is NOT paired, neither across cells nor across checkpoints."""
+    noise is keyed by row and by each policy's own counter: it is NOT paired, neither across cells nor across checkpoints.
+    actuators: True, or a dict overriding some of the thresholds effort_frac 0.98, vel_frac 0.98, limit_margin 0.02 rad, action_clip = the
+    task's clipActions — an ActuatorStats (include/ppenv_play_act.h) reads, after every env step and in two more launches, the env's own
+    joint positions / velocities / drive torques and the policy's raw actions where they lie, and sums per joint and per cell how the
+    return was earned: torque against the effort limit, speed against the velocity limit, position against the joint limits, mechanical
+    energy per game.  It counts the same games under the same freeze as the totals.  The result gains `actuators` (read_actuators());
+    every other key, `groups` included, is what it is without the option, and what is played does not change."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
-                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None):
+                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None, actuators=False):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -560,8 +735,26 @@ class Player:
             S = task.num_envs // len(sweep)
             self.pair_episodes = int(pair_episodes) if pair_episodes is not None else -(-self.games_num // S)
             self.pairs = PairStats(S, len(sweep), self.num_agents, self.pair_episodes, self._baseline, sim)
+        self.act = None
+        if actuators:
+            if actuators is not True and not isinstance(actuators, dict):
+                raise ValueError(f"actuators: True, or a dict of thresholds ({', '.join(ACT_THRESHOLDS)}, action_clip), not {actuators!r}")
+            thr = dict(ACT_THRESHOLDS, action_clip=float(task.clip_actions))
+            given = actuators if isinstance(actuators, dict) else {}
+            unknown = [k for k in given if k not in thr]
+            if unknown:
+                raise ValueError(f"actuators: unknown threshold {unknown[0]!r}; the thresholds are {', '.join(thr)}")
+            thr.update({k: float(v) for k, v in given.items()})
+            self._act_limits, self._act_names = actuator_limits(task)
+            G = 1 if sweep is None else len(sweep)
+            self.act = ActuatorStats(task.num_envs // G, G, len(self._act_names), self.games_num, self._act_limits, thr, sim, num_agents=self.num_agents)
+            env = task.env
+            if hasattr(env, "dof_states"):                                # the 27-dof AoS tensors; else the 7-dof SoA planes, as [N, D] views
+                self._act_inputs = (env.dof_states[..., 0], env.dof_states[..., 1], env.dof_force_tensor)
+            else:
+                self._act_inputs = (env.dof_pos.T, env.dof_vel.T, env.dof_force.T)
         self._runs = self._cell_actions = None
-        if per_cell:                                                      # runs of consecutive cells that hold the same object: (policy, first row, end row)
+        if per_cell:                                                     # runs of consecutive cells that hold the same object: (policy, first row, end row)
             w, runs = self.num_agents * (task.num_envs // len(sweep)), []
             for g, p in enumerate(self.policies):
                 if runs and runs[-1][0] is p:
@@ -618,6 +811,8 @@ class Player:
             self._latched.zero_()
         if self.pairs is not None:
             self.pairs.reset()
+        if self.act is not None:
+            self.act.reset()
         for p in self._distinct:
             p._counter = 0
         self._obs = self.task.reset()["obs"]
@@ -647,6 +842,8 @@ class Player:
         self.stats.accumulate(rew, done)
         if self.pairs is not None:
             self.pairs.record(rew, done)
+        if self.act is not None:                                          # the env's own tensors and the policy's own output: no copy, no refresh
+            self.act.accumulate(*self._act_inputs, self.actions, done)
         if self.recorder is not None:
             self.recorder.capture()
         self._obs = obs["obs"]
@@ -657,6 +854,17 @@ class Player:
         if self._latched is None:
             return None
         return outcomes_dict(TAOutcome.from_buffer_copy(self._latched.cpu().numpy().tobytes()))
+
+    def read_actuators(self):
+        """One host copy of the actuator totals -> run()'s `actuators`: dict(thresholds, joints = the names, control_dt, total =
+        actuator_summary of every group summed, groups = one actuator_summary per cell with its `cell`); None with actuators off."""
+        if self.act is None:
+            return None
+        per, dt = self.act.read(), control_dt_of(self.task)
+        cells = self.sweep.cells if self.sweep is not None else [{}]
+        return dict(thresholds=dict(self.act.thresholds), joints=list(self._act_names), control_dt=dt,
+                    total=actuator_summary(sum_act_totals(per), self._act_limits, self._act_names, dt),
+                    groups=[dict(cell=dict(c), **actuator_summary(t, self._act_limits, self._act_names, dt)) for c, t in zip(cells, per)])
 
     def run(self, on_poll=None):
         """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
@@ -693,6 +901,8 @@ class Player:
                 out["outcomes"] = self.read_outcomes()
             if self.recorder is not None:
                 out["captured_frames"] = self.recorder.captured
+            if self.act is not None:
+                out["actuators"] = self.read_actuators()
             return out
         finally:
             self.end_sweep()
@@ -726,6 +936,13 @@ def parse_args(argv=None):
     ap.add_argument("--against", action="append", default=None, metavar="PATH", help="another checkpoint to play on the same balls (repeatable): the cells become "
                     "checkpoints x sweep cells, --checkpoint's first (without --sweep: one cell per checkpoint); implies --paired and --paired-diff, the "
                     "baseline of every cell being the same sweep cell under --checkpoint; --num-envs must be a multiple of the cell count")
+    ap.add_argument("--actuators", action="store_true", help="per joint and per cell: torque against the effort limit, speed against the velocity limit, "
+                    "position against the joint limits, mechanical energy per game and raw actions at clipActions, summed on the device; one table per cell")
+    ap.add_argument("--actuators-out", default=None, metavar="FILE.json", help="with --actuators: write the result's `actuators` to FILE.json")
+    ap.add_argument("--effort-frac", type=float, default=None, help=f"with --actuators: at the effort limit means |tau| >= this x effort (default {ACT_THRESHOLDS['effort_frac']})")
+    ap.add_argument("--vel-frac", type=float, default=None, help=f"with --actuators: at the velocity limit means |qd| >= this x the limit (default {ACT_THRESHOLDS['vel_frac']})")
+    ap.add_argument("--limit-margin", type=float, default=None, help="with --actuators: at a position limit means within this many rad of it, or beyond "
+                    f"(default {ACT_THRESHOLDS['limit_margin']})")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -743,6 +960,11 @@ def parse_args(argv=None):
         ap.error("--sweep-out needs --sweep")
     if args.paired and not args.sweep:
         ap.error("--paired needs --sweep")
+    if not args.actuators:
+        for flag, v in (("--actuators-out", args.actuators_out), ("--effort-frac", args.effort_frac), ("--vel-frac", args.vel_frac),
+                        ("--limit-margin", args.limit_margin)):
+            if v is not None:
+                ap.error(f"{flag} needs --actuators")
     if args.against:
         if args.baseline is not None:
             ap.error("--baseline does not go with --against: the baseline of every cell is the same sweep cell under --checkpoint")
@@ -761,6 +983,15 @@ def parse_args(argv=None):
         except ValueError as e:
             ap.error(str(e))
     return args
+
+
+def actuator_option(args):
+    """Player's `actuators` from the --actuators, --effort-frac, --vel-frac and --limit-margin options: False, True, or the dict of the
+    thresholds that were given."""
+    if not getattr(args, "actuators", False):
+        return False
+    given = {k: getattr(args, k, None) for k in ACT_THRESHOLDS}
+    return {k: v for k, v in given.items() if v is not None} or True
 
 
 def make_renderer(task, args):
@@ -809,7 +1040,7 @@ def main(argv=None):
             print(f"checkpoint {k}: {p}", flush=True)
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
                 max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep, paired_diff=paired_diff,
-                baseline=baseline)
+                baseline=baseline, actuators=actuator_option(args))
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -834,6 +1065,13 @@ def main(argv=None):
     if "paired_diff" in res:
         for p in res["paired_diff"]["cells"]:
             print(pair_line(p, res["groups"], res["paired_diff"]["episodes"] * (task.num_envs // len(res["groups"]))))
+    if "actuators" in res:
+        for g in res["actuators"]["groups"]:
+            print(actuator_table(g, "cell " + cell_text(g["cell"])))
+        if getattr(args, "actuators_out", None):
+            with open(args.actuators_out, "w") as fh:
+                json.dump(res["actuators"], fh, indent=1)
+            print(f"wrote {args.actuators_out}")
     if getattr(args, "sweep_out", None):
         with open(args.sweep_out, "w") as fh:
             json.dump(res["groups"], fh, indent=1)
