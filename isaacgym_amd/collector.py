@@ -42,7 +42,7 @@ class RolloutCollector:
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0):
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
-        n, dev, a = getattr(env, "num_rows", env.num_envs), env.device, net.num_actions        # actor rows: A * N for the 4-actor variant
+        n, dev, a = env.num_rows, env.device, net.num_actions        # actor rows: A * N for the 4-actor variant
         z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
         self.obs = z(self.h + 1, n, env.obs_buf.shape[1])
         self.head = z(self.h + 1, n, a + 1)                     # mu | value, as the heads launch writes them

@@ -1,5 +1,5 @@
-"""Per-env domain randomisation of an environment handle.  `Randomizable` is the surface PPEnv and TASim share: the tables a caller
-hands over, the noise amplitudes, and the reset-time plan.  `ResetRandomizer` is reset-time randomisation drawn on the device
+"""Per-env domain randomisation of an environment handle, and `NativeEnv`: the surface every task's env has (PPEnv, TAEnv), stated once.
+`Randomizable` is the surface PPEnv and TASim share: the tables a caller hands over, the noise amplitudes, and the reset-time plan.  `ResetRandomizer` is reset-time randomisation drawn on the device
 (include/ppenv_dr.h): the tables, the uploaded plan and the state block of one environment handle, and the two launches.  The reference's rule — an env's actor parameters are redrawn when THAT env
 resets (tasks/humanoid_pingpong_3_actor_tilt.py:849-850, 1025; upstream VecTask.apply_randomizations) — without a host round trip.
 torch owns the memory, as it owns the environments' arenas; the library rewrites table columns in place."""
@@ -58,11 +58,18 @@ class ResetRandomizer:
 
 
 class Randomizable:
-    """The randomisation surface of an environment handle (PPEnv, TASim), which has `L`, `h`, `device` and `num_envs`.  The host class
+    """The randomisation surface of a native handle (PPEnv, TASim), which has `L`, `h`, `device` and `num_envs`.  The host class
     supplies what differs: DR_TABLE_ROWS, DR_SETTER, the seed / env-id offset / reset_rows its set_reset_randomization passes on, and
     the `reset_buf` apply_reset_randomization reads."""
     DR_TABLE_ROWS = None      # {set_randomization name: rows of that table, 0 for a per-env scalar [N]}, in the order of scene.Randomization's pointers
     DR_SETTER = None          # the C setter: "ppenv_set_randomization" / "ppenv_ta_sim_set_randomization"
+    _dr = None                # set_randomization's tables, kept alive here
+
+    @property
+    def dr_tables(self):
+        """The tables the step reads now, in the order of DR_TABLE_ROWS (None: that one is not randomised), or None with no randomisation
+        set.  Read-only: set_randomization replaces them."""
+        return self._dr
 
     def set_randomization(self, dof_stiffness_scale=None, dof_damping_scale=None, link_mass_scale=None, restitution_scale=None,
                           friction_scale=None, action_noise_sigma=0.0, observation_noise_sigma=0.0):
@@ -110,3 +117,35 @@ class Randomizable:
         _lib.check(getattr(self.L, self.DR_SETTER)(self.h, None), self.L)
         self._dr = None
         self.reset_randomization = None
+
+
+class NativeEnv:
+    """What every `task.env` is — PPEnv (the three 7-dof tasks, the 4-actor task) and TAEnv (the 27-dof task) — to the code above it
+    (VecTask, Player, PPOTrainer, RolloutCollector, the renderer).  The tasks differ below this surface, not in it:
+
+    L, device                       the bound library, the torch device
+    num_envs, num_agents, num_rows  num_rows = num_envs * num_agents: the rows of obs_buf / rew_buf / reset_buf / progress_buf
+    num_dofs                        joints per env (7 * num_agents; 27)
+    obs_buf, rew_buf, reset_buf, progress_buf
+    episode, flags                  the per-env episode counter and flag words the step writes (the tensors themselves, no copy)
+    status                          the device status word, 0 = healthy; read without synchronising
+    DR_TABLE_ROWS, dr_tables        table name -> rows, and the tables set now (dr.Randomizable)
+    set_randomization, set_reset_randomization, reset_randomization, set_noise_sigmas, apply_reset_randomization, clear_randomization
+                                    dr.Randomizable's, on the handle that owns the tables
+    set_gravity(z), base_gravity_z  base_gravity_z: the task's own gravity, what a randomised gravity scales or offsets; set_gravity
+                                    does not change it
+    control_dt                      seconds per control step, read when asked
+    joint_limits()                  (float32 [num_dofs, 4]: lower, upper, effort, vel_limit; the joint names) of the model the step runs
+    joint_views()                   (q, qd, tau) as [num_envs, num_dofs] float32 views of the env's own tensors, any strides
+    step(actions), reset_all(), reset_idx(env_ids)
+    set_serve_plan, apply_serve_plan, clear_serve_plan, serve_defaults, serve_plan   (include/ppenv_serve.h)"""
+
+    def apply_serve_plan(self, env_ids=None):
+        """The per-step launch (pp_serve_apply on reset_buf), once after every step while a plan is set; env_ids: the id variant, after
+        reset_idx(env_ids) (all envs: an arange).  No synchronisation; capturable."""
+        if self.serve_plan is None:
+            raise _lib.PPEnvError("apply_serve_plan: no plan is set (set_serve_plan)")
+        if env_ids is None:
+            self.serve_plan.apply(self.reset_buf)
+        else:
+            self.serve_plan.apply_ids(env_ids)

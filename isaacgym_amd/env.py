@@ -11,14 +11,15 @@ import numpy as np
 import torch
 
 from . import _lib, scene, serve
-from .dr import Randomizable
+from .dr import NativeEnv, Randomizable
 
 
-class PPEnv(Randomizable):
+class PPEnv(NativeEnv, Randomizable):
     def __init__(self, config, device=None, library=None):
         """library: a libppenv build other than the default one (_lib.load of _lib.build_for_arm_model's output: another arm
         model compiled in); the handle then only ever talks to that build."""
         self.config = config
+        self.base_gravity_z = float(config.gravity_z)
         self.L = library if library is not None else _lib.lib()   # raises when the HIP extension is missing: no fallback
         if not torch.cuda.is_available():
             raise _lib.PPEnvError("no ROCm GPU visible to PyTorch; the native environment runs on an MI355X only")
@@ -146,6 +147,17 @@ class PPEnv(Randomizable):
         return int(self.L.ppenv_status(self.h))
 
     @property
+    def control_dt(self):
+        """Seconds per control step: the config's dt as it is now (a task folds controlFrequencyInv into it before it creates the handle)."""
+        return float(self.config.dt)
+
+    def joint_limits(self):
+        return scene.joint_limits(self.config, self.num_agents)
+
+    def joint_views(self):
+        return self.dof_pos.T, self.dof_vel.T, self.dof_force.T
+
+    @property
     def step_kernel_name(self):
         """The kernel ppenv_step launches for this handle now, as rocprofv3's kernel trace names it (ppenv_step_kernel_name)."""
         return self.L.ppenv_step_kernel_name(self.h).decode()
@@ -224,16 +236,6 @@ class PPEnv(Randomizable):
         _lib.check(self.L.ppenv_set_serve_override(self.h, None, 1, _lib.stream(self.device)), self.L)
         self.serve_plan = plan
         return plan
-
-    def apply_serve_plan(self, env_ids=None):
-        """The per-step launch (pp_serve_apply on reset_buf), once after every step while a plan is set; env_ids: the id variant, after
-        reset_idx(env_ids) (all envs: an arange).  No synchronisation; capturable."""
-        if self.serve_plan is None:
-            raise _lib.PPEnvError("apply_serve_plan: no plan is set (set_serve_plan)")
-        if env_ids is None:
-            self.serve_plan.apply(self.reset_buf)
-        else:
-            self.serve_plan.apply_ids(env_ids)
 
     def clear_serve_plan(self):
         """The override off: the built-in serves are back, bit for bit (they are keyed by the envs' episode counters, which kept counting).

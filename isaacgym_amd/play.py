@@ -385,28 +385,13 @@ def actuator_table(entry, title=""):
 
 def actuator_limits(task):
     """The joints' limits from the numbers the step kernels themselves run with -> (float32 [D, 4]: lower, upper, effort, vel_limit; the D
-    joint names).  A 7-dof task: the `joint` entries of its native config (ppenv_joint), once per humanoid — the 4-actor task's 14 dofs are
-    h1/..., h2/...; the 27-dof task: links 1..27 (ppenv_ta_link) of the model its simulation was created with.  Names are scene.G1_RIGHT_ARM's
-    / urdf.ta_dof_joint_names() where they fit, else dof<i>."""
-    from . import scene, urdf
-    if hasattr(task, "native_config"):
-        joints = list(task.native_config.joint)
-        names = [s["name"][:-5] + "_joint" if s["name"].endswith("_link") else s["name"] for s in scene.G1_RIGHT_ARM]
-        A = int(getattr(task, "num_agents", 1))
-    else:
-        joints = list(task.env.sim.model.link)[1:]
-        names, A = urdf.ta_dof_joint_names(), 1
-    if len(names) != len(joints):
-        names = [f"dof{i}" for i in range(len(joints))]
-    table = np.array([[j.lower, j.upper, j.effort, j.vel_limit] for j in joints] * A, np.float32)
-    if A > 1:
-        names = [f"h{a + 1}/{n}" for a in range(A) for n in names]
-    return table, list(names)
+    joint names): the env's joint_limits() (scene.joint_limits, scene.ta_joint_limits)."""
+    return task.env.joint_limits()
 
 
 def control_dt_of(task):
-    """Seconds per control step: the native config's dt (controlFrequencyInv already folded in), the 27-dof simulation's scene dt."""
-    return float(task.native_config.dt if hasattr(task, "native_config") else task.env.sim.scene.dt)
+    """Seconds per control step (the env's control_dt: controlFrequencyInv already folded in)."""
+    return task.env.control_dt
 
 
 class ActuatorStats:
@@ -691,7 +676,7 @@ class Player:
         if sweep is not None:
             if outcomes:
                 raise ValueError("outcomes=True with a sweep: the 27-dof outcome counts are cross-env reset windows and cannot be split by group")
-            if getattr(task, "randomize", False):
+            if task.randomize:
                 raise ValueError("a sweep on a task with randomize: True: the sweep sets the task's randomisation tables itself; set task.randomize=False")
         per_cell = isinstance(policy, (list, tuple))
         if per_cell and (sweep is None or len(policy) != len(sweep)):
@@ -716,7 +701,7 @@ class Player:
         self.task, self.policy = task, self.policies[0]
         self.games_num, self.poll_every, self.max_steps = int(games_num), int(poll_every), int(max_steps)
         self.deterministic, self.seed = bool(deterministic), int(seed)
-        self.num_agents = int(getattr(task, "num_agents", 1))
+        self.num_agents = int(task.num_agents)
         self._distinct = list({id(p): p for p in self.policies}.values())
         if sigma is not None:
             for p in self._distinct:
@@ -726,7 +711,7 @@ class Player:
         if sweep is None:
             self.stats = EpisodeStats(task.num_envs, self.num_agents, self.games_num, sim)
         else:
-            self._tables = sweep.tables(self._dr_handle().DR_TABLE_ROWS, task.num_envs)
+            self._tables = sweep.tables(task.env.DR_TABLE_ROWS, task.num_envs)
             if sweep.paired or any(a in SERVE_AXES for cell in sweep.cells for a in cell):
                 self._serve_cells = sweep.serve_cells(task.env.serve_defaults())
             self.stats = GroupStats(task.num_envs // len(sweep), len(sweep), self.num_agents, self.games_num, sim)
@@ -748,11 +733,7 @@ class Player:
             self._act_limits, self._act_names = actuator_limits(task)
             G = 1 if sweep is None else len(sweep)
             self.act = ActuatorStats(task.num_envs // G, G, len(self._act_names), self.games_num, self._act_limits, thr, sim, num_agents=self.num_agents)
-            env = task.env
-            if hasattr(env, "dof_states"):                                # the 27-dof AoS tensors; else the 7-dof SoA planes, as [N, D] views
-                self._act_inputs = (env.dof_states[..., 0], env.dof_states[..., 1], env.dof_force_tensor)
-            else:
-                self._act_inputs = (env.dof_pos.T, env.dof_vel.T, env.dof_force.T)
+            self._act_inputs = task.env.joint_views()                     # the 27-dof AoS tensors, the 7-dof SoA planes: [N, D] views
         self._runs = self._cell_actions = None
         if per_cell:                                                     # runs of consecutive cells that hold the same object: (policy, first row, end row)
             w, runs = self.num_agents * (task.num_envs // len(sweep)), []
@@ -773,15 +754,6 @@ class Player:
         self.actions = None
         self._obs = None
 
-    def _dr_handle(self):
-        """The handle that owns the randomisation tables: the 7-dof / 4-actor env itself, the 27-dof env's simulation."""
-        env = self.task.env
-        return env if hasattr(env, "DR_TABLE_ROWS") else env.sim
-
-    def _episode(self):
-        env = self.task.env
-        return env.episode if hasattr(env, "episode") else env.state.episode
-
     def end_sweep(self):
         """The task as the sweep found it: the plain step kernel (clear_randomization), no serve plan, and the episode counters of before
         start().  run() calls it at its end, also on an exception; a caller that drives start() / step() itself calls it when done."""
@@ -791,7 +763,7 @@ class Player:
         if self._serve_cells is not None:
             self.task.clear_serve_plan()
         if self._episode0 is not None:
-            self._episode().copy_(self._episode0)
+            self.task.env.episode.copy_(self._episode0)
             self._episode0 = None
         self._obs = None
 
@@ -799,7 +771,7 @@ class Player:
         """Every env to the start of an episode, the accounting to zero, the action-draw counter to zero (a run is a function of the seed)."""
         if self.sweep is not None:
             if self._episode0 is None:
-                self._episode0 = self._episode().clone()
+                self._episode0 = self.task.env.episode.clone()
             if self._tables or self._serve_cells is None:             # (a sweep of serves alone keeps the plain step kernel)
                 self.task.env.set_randomization(**self._tables)       # before the reset: the first counted episode is already the cell's
             if self._serve_cells is not None:                         # fill = serve 0; the reset below consumes it and leaves count 1

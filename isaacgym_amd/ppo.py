@@ -407,15 +407,15 @@ class PPOTrainer:
 
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
-        if getattr(task, "randomize", False):
+        if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
-        if getattr(task, "_serve_plan", None) is not None:
+        if task._serve_plan is not None:
             raise ValueError("a task with a serve plan set is not supported by PPOTrainer: the collector drives the env below VecTask.step, so the plan's "
                              "per-step launch would not run; call task.clear_serve_plan() first")
         self.task, self.env = task, task.env
         env = self.env
         self.device = dev = torch.device(env.device)
-        self.rows = getattr(env, "num_rows", env.num_envs)                  # actor rows: num_envs x num_agents (T4: 2 actors per env)
+        self.rows = env.num_rows                  # actor rows: num_envs x num_agents (T4: 2 actors per env)
         cfg.check(self.rows)
         self.num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
         self.seed = int(seed)

@@ -245,7 +245,7 @@ class Scene:
         name = {v: k for k, v in scene.TASK_VARIANTS.items()}[task.VARIANT]
         self = cls.from_config(name, task.cfg)
         self.task, dev, n = task, task.device, task.num_envs
-        self.L = task.env.L if hasattr(task.env, "L") else task.env.sim.L
+        self.L = task.env.L
         self.rb = torch.zeros((n, self.source_rows[0], 13), dtype=torch.float32, device=dev)      # the renderer's own: no env tensor is written
         if task.VARIANT == "TA":
             self.root = task.env.root_states                                                         # used as it is

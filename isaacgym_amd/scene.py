@@ -679,6 +679,33 @@ def pd_action_offset_scale(config):
     return 0.5 * (hi + lo), 0.5 * (hi - lo)
 
 
+def _limit_table(joints):
+    return np.array([[j.lower, j.upper, j.effort, j.vel_limit] for j in joints], np.float32)
+
+
+def joint_limits(config, num_agents=1):
+    """The 7-dof and 4-actor tasks' joint limits, from the numbers the step kernel runs with: the `joint` entries of a ppenv_config, once
+    per humanoid -> (float32 [7 * num_agents, 4]: lower, upper, effort, vel_limit; the joint names).  Names are G1_RIGHT_ARM's, a link's
+    `_link` read as `_joint`, else dof<i>; the 4-actor task's 14 dofs are h1/..., h2/..."""
+    joints = list(config.joint)
+    names = [s["name"][:-5] + "_joint" if s["name"].endswith("_link") else s["name"] for s in G1_RIGHT_ARM]
+    if len(names) != len(joints):
+        names = [f"dof{i}" for i in range(len(joints))]
+    if num_agents > 1:
+        names = [f"h{a + 1}/{n}" for a in range(num_agents) for n in names]
+    return _limit_table(joints * num_agents), names
+
+
+def ta_joint_limits(model):
+    """The 27-dof task's: links 1..27 (ppenv_ta_link) of a ppenv_ta_model -> (float32 [27, 4], the names: urdf.ta_dof_joint_names()
+    where they fit, else dof<i>)."""
+    from . import urdf
+    joints, names = list(model.link)[1:], urdf.ta_dof_joint_names()
+    if len(names) != len(joints):
+        names = [f"dof{i}" for i in range(len(joints))]
+    return _limit_table(joints), list(names)
+
+
 def initial_root_states(config):
     """[3, 13] initial actor root states (humanoid, table, ball) in the reference's layout (TT:173-183)."""
     out = np.zeros((NUM_ACTORS, 13), dtype=np.float32)

@@ -11,7 +11,7 @@ import ctypes as C
 import torch
 
 from . import _lib, scene, serve
-from .dr import Randomizable
+from .dr import NativeEnv, Randomizable
 
 
 OUTCOME_WORDS = C.sizeof(_lib.TAOutcome) // 8      # pp_ta_outcome as an int64 tensor: 16 words
@@ -216,11 +216,14 @@ class TASim(Randomizable):
         self._ck(self.L.ppenv_ta_forward_kinematics(self.h, n, root_states.data_ptr(), dof_states.data_ptr(), rb_states.data_ptr(), _lib.stream(self.device)))
 
 
-class TAEnv:
+class TAEnv(NativeEnv):
     """HumanoidPingpongTiltNESSparse27DOF (tasks/humanoid_pingpong_3_actor_all_dof.py:65) as a native task: the tensors the
     reference class wraps (TA:161-251) live here, `step` = pre_physics_step + simulate + post_physics_step in one launch
     (ppenv_ta_step) plus the tiny count-flag clear; `fused=False` keeps the two launches (ppenv_ta_simulate +
-    ppenv_ta_post_physics_step).  Surface: obs_buf [N,313], rew_buf, reset_buf, progress_buf, 27 actions."""
+    ppenv_ta_post_physics_step).  Surface: dr.NativeEnv's, with obs_buf [N,313] and 27 actions; the randomisation calls go to `sim`, which
+    owns the tables."""
+    DR_TABLE_ROWS = TASim.DR_TABLE_ROWS
+    base_gravity_z = scene.TA_GRAVITY_Z       # the task's own (TA:383-385); sim.scene.gravity_z is what set_gravity last wrote
 
     def __init__(self, num_envs, device="cuda:0", seed=0, env_id_offset=0, env=None, fused=True, materialize_rb=None, share_initial_rb=True,
                  scene_cfg=None, model=None, library=None):
@@ -232,9 +235,11 @@ class TAEnv:
         self.device = torch.device(device)
         n = self.num_envs = int(num_envs)
         self.num_obs, self.num_actions, self.num_agents = scene.TA_NUM_OBS, scene.TA_NUM_DOF, 1
+        self.num_rows, self.num_dofs = n, scene.TA_NUM_DOF
         self.params = scene.build_ta_params(n, env=env, seed=seed, env_id_offset=env_id_offset)
         self.sim = TASim(n, device=self.device, scene_cfg=scene_cfg, model=model, library=library)
         self.state = TAState(self.params, device=self.device, library=library)
+        self.L, self.episode, self.flags = self.sim.L, self.state.episode, self.state.flags
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)
         self.root_states, self.dof_states = z(n, 3, 13), z(n, 27, 2)          # TA:187-193, 237-240
         self._rb_states, self.dof_force_tensor, self.pre_ball_vx = z(n, 42, 13), z(n, 27), z(n)
@@ -336,6 +341,27 @@ class TAEnv:
     def set_gravity(self, gravity_z):
         self.sim.set_gravity(gravity_z)
 
+    @property
+    def dr_tables(self):
+        return self.sim.dr_tables
+
+    @property
+    def status(self):
+        return self.sim.status
+
+    @property
+    def control_dt(self):
+        return float(self.sim.scene.dt)
+
+    def joint_limits(self):
+        return scene.ta_joint_limits(self.sim.model)
+
+    def joint_views(self):
+        return self.dof_states[..., 0], self.dof_states[..., 1], self.dof_force_tensor
+
+    def reset_all(self):
+        self.reset_idx(None)
+
     def serve_defaults(self):
         """{serve axis: (lo, hi)}: the task's own ranges (`params`) — what a serve-plan cell does not name."""
         p = self.params
@@ -354,15 +380,6 @@ class TAEnv:
         self.serve_plan = serve.ServePlan(self.sim.L, self.device, self.num_envs, cells, defaults, serve.AXES_27DOF, out, form=scene.VARIANT_TN,
                                           layout=_lib.SERVE_LAYOUT_AOS5, reset_rows=1, seed=seed, env_id_offset=p.env_id_offset, paired=paired)
         return self.serve_plan
-
-    def apply_serve_plan(self, env_ids=None):
-        """The per-step launch (pp_serve_apply on reset_buf); env_ids: the id variant, after reset_idx(env_ids) (all envs: an arange)."""
-        if self.serve_plan is None:
-            raise _lib.PPEnvError("apply_serve_plan: no plan is set (set_serve_plan)")
-        if env_ids is None:
-            self.serve_plan.apply(self.reset_buf)
-        else:
-            self.serve_plan.apply_ids(env_ids)
 
     def clear_serve_plan(self):
         """The task's own keyed draws are back, bit for bit (they are keyed by the envs' episode counters, which kept counting)."""

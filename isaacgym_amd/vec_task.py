@@ -44,7 +44,9 @@ def _parse_device(sim_device):
 
 
 class VecTask:
-    VARIANT = None   # 'T3' | 'TT' | 'TN', set by subclasses
+    VARIANT = None   # 'T3' | 'TT' | 'TN' | 'T4' | 'TA', set by subclasses
+    NUM_AGENTS = 1   # rl_games multi-agent convention: batch rows = num_envs * num_agents
+    DR_DOF_ROWS = DR_MASS_ROWS = scene.NUM_DOF   # rows of the env's dof and link-mass randomisation tables (its DR_TABLE_ROWS)
 
     def __init__(self, config, rl_device, sim_device, graphics_device_id=-1, headless=True, virtual_screen_capture=False,
                  force_render=False):
@@ -62,7 +64,7 @@ class VecTask:
         self._renderer = None
 
         self.num_envs = int(env_cfg["numEnvs"])
-        self.num_agents = int(getattr(self, "NUM_AGENTS", 1))   # rl_games multi-agent convention: batch rows = num_envs * num_agents
+        self.num_agents = self.NUM_AGENTS
         self.num_observations = self.num_obs = int(env_cfg["numObservations"])
         self.num_states = int(env_cfg.get("numStates", 0))
         self.num_actions = self.num_acts = int(env_cfg["numActions"])
@@ -84,7 +86,7 @@ class VecTask:
         self.randomize_apply_at = self.randomization_params.get("apply_at", "step")
         if self.randomize_apply_at not in ("step", "reset"):
             raise ValueError(f"task.randomization_params.apply_at must be 'step' or 'reset', got {self.randomize_apply_at!r}")
-        self._dr_reset = False
+        self._dr_reset, self._dr_gen = False, None
         self._serve_plan = None            # set_serve_plan(): the ServePlan whose per-step launch step() then issues
         self.stats_every = int(config.get("stats_every", 40))                       # TT:763: the reference prints the means every 40 steps
 
@@ -124,8 +126,7 @@ class VecTask:
         """apply_at: "reset" — the actor-parameter tables of randomization_params become a device plan of the environment
         (set_reset_randomization); `randomize_buf` is from now on the buffer the kernel maintains: control steps since the env's last
         redraw (TT:1025), zeroed for exactly the envs that redraw."""
-        plan = scene.reset_randomization_plan(self.randomization_params, dof_rows=getattr(self, "DR_DOF_ROWS", scene.NUM_DOF),
-                                              mass_rows=getattr(self, "DR_MASS_ROWS", scene.NUM_DOF))
+        plan = scene.reset_randomization_plan(self.randomization_params, dof_rows=self.DR_DOF_ROWS, mass_rows=self.DR_MASS_ROWS)
         if not plan["tables"]:
             return
         # the tables' own stream of the task's seed: not the serve's, not the noise's, and unrelated to seed + 1's
@@ -176,9 +177,9 @@ class VecTask:
             return
         self.first_randomization, self.last_rand_step = False, self.last_step
         n, dev = self.num_envs, self.device
-        gen = getattr(self, "_dr_gen", None)
-        if gen is None:
-            gen = self._dr_gen = torch.Generator(device=dev).manual_seed(int(self.cfg.get("seed", 0)) + 7919)
+        if self._dr_gen is None:
+            self._dr_gen = torch.Generator(device=dev).manual_seed(int(self.cfg.get("seed", 0)) + 7919)
+        gen = self._dr_gen
 
         def sched(p):
             if p.get("schedule") == "linear":
@@ -206,7 +207,7 @@ class VecTask:
             kw["observation_noise_sigma"] = float(obs["range"][1]) * sched(obs)
         g = (dr_params.get("sim_params") or {}).get("gravity")
         if g:      # one value per simulation; the 27-dof task re-uploads its scene constants (ppenv_ta_sim_set_gravity)
-            base = self.native_config.gravity_z if hasattr(self, "native_config") else scene.TA_GRAVITY_Z
+            base = self.env.base_gravity_z
             dz = float(sample(g, (1,)).item()) if g.get("operation") == "additive" else 0.0
             self.env.set_gravity(min(base + dz, 0.0) if g.get("operation") == "additive" else base * float(sample(g, (1,)).item()))
         if self.randomize_apply_at == "reset":       # the actor parameters are drawn on the device, per env, at reset time (_set_reset_randomization);
@@ -218,7 +219,7 @@ class VecTask:
         hum = ((dr_params.get("actor_params") or {}).get("humanoid") or {})
         mass = (hum.get("rigid_body_properties") or {}).get("mass")
         if mass:
-            kw["link_mass_scale"] = sample(mass, (getattr(self, "DR_MASS_ROWS", scene.NUM_DOF), n))
+            kw["link_mass_scale"] = sample(mass, (self.DR_MASS_ROWS, n))
         shape = hum.get("rigid_shape_properties") or {}
         if shape.get("friction"):
             kw["friction_scale"] = sample(shape["friction"], (n,))
@@ -226,9 +227,9 @@ class VecTask:
             kw["restitution_scale"] = sample(shape["restitution"], (n,))
         dof = hum.get("dof_properties") or {}
         if dof.get("stiffness"):
-            kw["dof_stiffness_scale"] = sample(dof["stiffness"], (getattr(self, "DR_DOF_ROWS", scene.NUM_DOF), n))
+            kw["dof_stiffness_scale"] = sample(dof["stiffness"], (self.DR_DOF_ROWS, n))
         if dof.get("damping"):
-            kw["dof_damping_scale"] = sample(dof["damping"], (getattr(self, "DR_DOF_ROWS", scene.NUM_DOF), n))
+            kw["dof_damping_scale"] = sample(dof["damping"], (self.DR_DOF_ROWS, n))
         self.env.set_randomization(**kw)
         self.randomize_buf.zero_()
 
@@ -343,7 +344,7 @@ class _HumanoidPingpongBase(VecTask):
         self.initial_speed_range = tuple(cfg["scene"]["serve_speed"])
         self.tilt_angle_range = tuple(cfg["scene"]["serve_tilt"])
         self.tilt_z_angle_range = tuple(cfg["scene"]["serve_tilt_z"])
-        A = int(getattr(self, "NUM_AGENTS", 1))
+        A = self.NUM_AGENTS
         self.actors_per_env, self.dofs_per_env = A + 2, A * scene.NUM_DOF                    # T4:125-126
         self.num_humanoid_bodies = 40
         self.rigid_bodies_per_env = A * self.num_humanoid_bodies + 2                          # T4:127
@@ -503,21 +504,10 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
     # the 27-dof tree: 27 dofs, 28 links (link 0 = the pelvis) — the table shapes of ppenv_ta_randomization
     DR_DOF_ROWS, DR_MASS_ROWS = scene.TA_NUM_DOF, scene.TA_NUM_LINKS
 
-    def step(self, actions):
-        if self.randomize:                  # as the 7-dof tasks: once per step, gated by `frequency` (upstream: from _reset_idx, TA's reset path)
-            self.apply_randomizations(self.randomization_params)
-        self.env.step(actions)              # the clipActions clamp happens inside the kernel
-        if self._serve_plan is not None:
-            self.env.apply_serve_plan()
-        if self._dr_reset:
-            self.env.apply_reset_randomization()
-        self.control_steps += 1
-        self.last_step = self.control_steps
-        if self.stats_every > 0 and self.control_steps % self.stats_every == 0:   # TA:860-866 prints the same two means every 40 steps
-            self.extras["reward_mean"] = self.rew_buf.mean()
-            self.extras["progress_mean"] = self.progress_buf.float().mean()
-        self.extras["time_outs"] = self.timeout_buf if self.rl_device == self.device else self.timeout_buf.to(self.rl_device)
-        return self._obs_dict(), self._to_rl(self.rew_buf), self._to_rl(self.reset_buf), self.extras
+    def _export_means(self):
+        """TA:860-866 prints the same two means every 40 steps; here two torch reductions on the task's own buffers."""
+        self.extras["reward_mean"] = self.rew_buf.mean()
+        self.extras["progress_mean"] = self.progress_buf.float().mean()
 
     def enable_outcomes(self):
         """The five head-counts the reference prints whenever an env resets (TA:1161-1175: fell down, close to the paddle, hit the paddle,
@@ -527,9 +517,3 @@ class HumanoidPingpongTiltNESSparse27DOF(VecTask):
         self.outcomes = self.env.enable_outcomes()
         self.extras["outcomes"] = self.outcomes
         return self.outcomes
-
-    def reset_idx(self, env_ids=None):
-        """_reset_idx (TA:965-1028) for the listed envs (None: all): root states, dof states, ball y / z and serve of the env's
-        next episode, progress 0, the four sticky flags cleared.  Like the reference's, it leaves obs_buf to the next step."""
-        self.env.reset_idx(env_ids)
-        self._reset_idx_randomization(env_ids)

@@ -337,7 +337,7 @@ def test_default_mode_is_the_per_step_host_redraw(torch_cuda, name):
             want[1] = sample(hum["dof_properties"]["damping"], (dof_rows, n), last_step)
         task.step(a)
         last_step = t + 1
-    dr = task.env._dr if name == "HumanoidPingpongTiltG1" else task.env.sim._dr
+    dr = task.env.dr_tables
     for got, w in zip(dr, want):
         assert torch.equal(got, w)
     assert not bool(task.randomize_buf.any())

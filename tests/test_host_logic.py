@@ -102,6 +102,22 @@ def test_bad_cfg_raises_like_the_reference():
         scene.build_config("TT", cfg=cfg)
 
 
+def test_task_classes_state_their_agents_and_table_rows():
+    """What VecTask reads from its class instead of probing: NUM_AGENTS, and the rows of the dof and link-mass randomisation tables, which
+    are those of the class's env (its DR_TABLE_ROWS)."""
+    from isaacgym_amd import vec_task
+    from isaacgym_amd.env import PPEnv
+    from isaacgym_amd.tasks import isaacgym_task_map
+    from isaacgym_amd.tensor_api import TAEnv
+    assert vec_task.VecTask.NUM_AGENTS == 1 and vec_task.Humanoid12PingpongTilt.NUM_AGENTS == 2
+    classes = [vec_task.VecTask] + list(isaacgym_task_map.values())
+    assert len(classes) == 6
+    for cls in classes:
+        rows = (TAEnv if cls is vec_task.HumanoidPingpongTiltNESSparse27DOF else PPEnv).DR_TABLE_ROWS
+        assert cls.DR_DOF_ROWS == rows["dof_stiffness_scale"] == rows["dof_damping_scale"] and cls.DR_MASS_ROWS == rows["link_mass_scale"], cls
+    assert (vec_task.HumanoidPingpongTiltNESSparse27DOF.DR_DOF_ROWS, vec_task.HumanoidPingpongTiltNESSparse27DOF.DR_MASS_ROWS) == (27, 28)
+
+
 def test_product_never_imports_the_oracle():
     """The product path must not route through oracle/ or the tests' host shim."""
     roots = [os.path.join(ROOT, d) for d in ("isaacgym_amd", "isaacgymenvs", "isaacgym", "include")]

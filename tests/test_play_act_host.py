@@ -231,25 +231,29 @@ def test_python_refusals():
 
 def test_actuator_limits_reproduces_the_config_numbers():
     cfg = scene.build_config("TT", num_envs=4)
-    table, names = play.actuator_limits(types.SimpleNamespace(native_config=cfg, num_agents=1))
+    table, names = scene.joint_limits(cfg, 1)
     assert table.dtype == np.float32 and table.shape == (scene.NUM_DOF, 4) and len(names) == scene.NUM_DOF
     for d, j in enumerate(cfg.joint):
         assert list(table[d]) == [np.float32(j.lower), np.float32(j.upper), np.float32(j.effort), np.float32(j.vel_limit)]
     assert names[0] == "right_shoulder_pitch_joint" and all(n.endswith("_joint") for n in names)
     assert [float(v) for v in table[0, 2:]] == [scene.G1_RIGHT_ARM[0]["effort"], scene.G1_RIGHT_ARM[0]["vel"]]
-    t4, n4 = play.actuator_limits(types.SimpleNamespace(native_config=scene.build_config("T4", num_envs=4), num_agents=2))
+    t4, n4 = scene.joint_limits(scene.build_config("T4", num_envs=4), 2)
     assert t4.shape == (14, 4) and np.array_equal(t4[:7], t4[7:]) and np.array_equal(t4[:7], table)
     assert n4[:7] == ["h1/" + n for n in names] and n4[7:] == ["h2/" + n for n in names]
     model = scene.build_ta_model()
     model.link[5].effort = 123.5                                                # a model of the caller's: ITS numbers, not the stock ones
-    ta, na = play.actuator_limits(types.SimpleNamespace(env=types.SimpleNamespace(sim=types.SimpleNamespace(model=model))))
+    ta, na = scene.ta_joint_limits(model)
     assert ta.shape == (scene.TA_NUM_DOF, 4) and ta[4, 2] == np.float32(123.5)
     for d in range(scene.TA_NUM_DOF):
         k = model.link[d + 1]
         assert list(ta[d]) == [np.float32(k.lower), np.float32(k.upper), np.float32(k.effort), np.float32(k.vel_limit)]
     from isaacgym_amd import urdf
     assert na == urdf.ta_dof_joint_names()
-    assert play.control_dt_of(types.SimpleNamespace(native_config=cfg)) == float(cfg.dt)
+    from isaacgym_amd.env import PPEnv
+    assert PPEnv.control_dt.fget(types.SimpleNamespace(config=cfg)) == float(cfg.dt)        # the 7-dof env's control_dt on this config
+    env = types.SimpleNamespace(control_dt=float(cfg.dt), joint_limits=lambda: (table, names))
+    got = play.actuator_limits(types.SimpleNamespace(env=env))
+    assert play.control_dt_of(types.SimpleNamespace(env=env)) == float(cfg.dt) and got[0] is table and got[1] is names
 
 
 def _totals(games, samples, D=2, scale=1.0):

@@ -60,7 +60,7 @@ GRID = {"friction_scale": [0.5, 1.0], "serve_speed": [6.5, 9.0]}
 def manual_streams(torch, task, policy, sweep, steps):
     """The swept run by hand, in the shape of test_play_serve_sweep_gpu.manual_loop -> the [steps, rows] rew and done it produced."""
     env = task.env
-    tables = sweep.tables((env if hasattr(env, "DR_TABLE_ROWS") else env.sim).DR_TABLE_ROWS, task.num_envs)
+    tables = sweep.tables(env.DR_TABLE_ROWS, task.num_envs)
     if tables:
         task.env.set_randomization(**tables)
     task.set_serve_plan(sweep.serve_cells(task.env.serve_defaults()), paired=sweep.paired)

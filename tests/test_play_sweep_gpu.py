@@ -140,13 +140,11 @@ N_ENVS = 128
 
 
 def rows_of(task):
-    env = task.env
-    return (env if hasattr(env, "DR_TABLE_ROWS") else env.sim).DR_TABLE_ROWS
+    return task.env.DR_TABLE_ROWS
 
 
 def randomization_of(task):
-    env = task.env
-    return (env if hasattr(env, "DR_TABLE_ROWS") else env.sim)._dr
+    return task.env.dr_tables
 
 
 def manual_loop(torch, task, policy, sweep, games_num, steps):

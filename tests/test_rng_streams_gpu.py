@@ -266,8 +266,7 @@ def _recovered_noise(task, n, seed, steps=4):
         oc, on = (e.obs_buf.cpu().numpy().astype(np.float64).reshape(n, width) for e in (clean, noisy))
         ref, ids = gauss64(env_stream_seed(seed), np.arange(n)[:, None], ep[:, None], prog[:, None], base + np.arange(width)[None, :], ta=task == "TA", draw_ids=True)
         out.append(((on - oc) / SIGMA, 2.0 ** -24 * (np.abs(oc) + np.abs(on)) / SIGMA, ref, ids, oc))
-    st = clean.sim.status if task == "TA" else clean.status
-    assert st == 0
+    assert clean.status == 0
     clean.close(); noisy.close()
     return out
 

@@ -197,8 +197,7 @@ def test_paired_groups_with_equal_cells_are_replicas(torch_cuda, name, S):
 
 # ------------------------------------------------------------------------------------------------------ 9. clear
 def episode_of(task):
-    env = task.env
-    return env.episode if hasattr(env, "episode") else env.state.episode
+    return task.env.episode
 
 
 @pytest.mark.parametrize("name", [TT, TA])

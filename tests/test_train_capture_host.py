@@ -169,7 +169,7 @@ def test_the_collector_calls_on_step_after_every_env_step():
             calls.append("forward")
 
     class Env:
-        num_envs, device, obs_buf = 2, torch.device("cpu"), torch.zeros(2, 5)
+        num_envs, num_rows, device, obs_buf = 2, 2, torch.device("cpu"), torch.zeros(2, 5)
 
         def step(self, actions, obs=None, rew=None, reset=None):
             calls.append("step")

@@ -12,7 +12,7 @@ import isaacgym_amd  # noqa: E402
 
 for name, n in (("HumanoidPingpongTiltG1", 16384), ("HumanoidPingpongTiltG1", 4096), ("Humanoid12PingpongTiltG1", 8192), ("HumanoidPingpongTiltNESSparse27DOFG1", 4096)):
     task = isaacgym_amd.make(seed=1, task=name, num_envs=n, sim_device="cuda:0", rl_device="cuda:0")
-    acts = [(torch.rand(task.num_envs * getattr(task, "num_agents", 1), task.num_actions, device="cuda:0") * 2 - 1) for _ in range(8)]
+    acts = [(torch.rand(task.num_envs * task.num_agents, task.num_actions, device="cuda:0") * 2 - 1) for _ in range(8)]
     task.reset()
     for s in range(200):
         task.step(acts[s & 7])
