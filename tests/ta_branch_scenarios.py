@@ -8,6 +8,7 @@ group (env % 5): paddle, net, table, below, humanoid displaced.  The ball is AIM
 0 / 1 / 2 — every 7th env in each step — so an env's paying branch and its reset fall into the same step.  Inside a (group, env % 7) class
 the case (which side of a threshold, which gate closed) cycles with the env's index, so that every cell of `CELLS` is reached by its
 share of the envs whatever the seed; the sticky bits a case does not fix are drawn independently with probability 1/2.
+(The humanoid here stands at rest: ball contacts with a MOVING humanoid are the suite of tests/ta_ball_contact_scenarios.py.)
 
 Everything here is decided from the ORACLE's tensors: `classify` (which cells an env-step is in), `near_threshold` (which env-steps lie
 within the comparison tolerance of a branch threshold and are set aside, as ball_switch_probe sets aside the contact switches) and
