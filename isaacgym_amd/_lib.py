@@ -22,7 +22,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ta_chain.hip"), os.path.join(_PKG, "csrc", "ppenv_policy.hip"), os.path.join(_PKG, "csrc", "ppenv_policy_bwd.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_play_delay.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -33,6 +34,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_serve_device.h"), os.path.join(ROOT, "include", "ppenv_serve.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair_device.h"), os.path.join(ROOT, "include", "ppenv_play_pair.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_act_device.h"), os.path.join(ROOT, "include", "ppenv_play_act.h"),
+           os.path.join(_PKG, "csrc", "ppenv_play_delay_device.h"), os.path.join(ROOT, "include", "ppenv_play_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -122,6 +124,7 @@ class PlayPairTotals(C.Structure):
 
 
 PLAY_ACT_MAX_DOF, PLAY_ACT_FIELDS = 32, 10                                               # PP_PLAY_ACT_MAX_DOF, PP_PLAY_ACT_FIELDS
+PLAY_DELAY_MAX, PLAY_DELAY_MAX_WIDTH = 15, 512                                           # PP_PLAY_DELAY_MAX, PP_PLAY_DELAY_MAX_WIDTH
 
 
 class PlayActLimit(C.Structure):
@@ -435,6 +438,11 @@ def load(path):
     L.pp_play_act_state_bytes.argtypes = L.pp_play_act_partial_bytes.argtypes = [i32, i32, i32]
     L.pp_play_act_reset.argtypes = [i32, i32, i32, vp, vp, vp, vp]
     L.pp_play_act_accumulate.argtypes = [C.POINTER(PlayActInputs), vp, i32, i32, i32, i32, i64, vp, C.POINTER(PlayActThresholds), vp, vp, vp, vp, vp]
+    # ---- include/ppenv_play_delay.h
+    L.pp_play_delay_ring_bytes.restype = sz
+    L.pp_play_delay_ring_bytes.argtypes = [i32, i32, i32]
+    L.pp_play_delay_reset.argtypes = [i32, vp, vp]
+    L.pp_play_delay_push.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
     # ---- include/ppenv_ppo_meter.h
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]

@@ -10,6 +10,7 @@
     python -m isaacgym_amd.play ... --against other.pth [--against third.pth] [--sweep friction_scale=0.5,1.0]                     checkpoints A/B on the same balls
 
     python -m isaacgym_amd.play ... --actuators --sweep link_mass_scale=0.7:1.3:3 [--actuators-out act.json]                       per cell, a per-joint table: torque, speed, limits, energy
+    python -m isaacgym_amd.play ... --sweep action_delay=0,1,2,3 --paired --paired-diff --baseline 0 [--obs-delay 1]                  the return lost per control step of command latency
 
 Semantics.  Restated from rl_games' published BasePlayer.run (rl_games is absent offline: parity unpinned, the same status as ppo.py):
 per row a running return `cr += r` (fp32, the unscaled reward) and a running length; the rows whose `done` is set are finished games
@@ -58,7 +59,16 @@ the mechanical energy of a game (the reward's power term sum |tau * qd|, times t
 SoA planes, the 27-dof AoS rows — in two launches per control step, under the totals' freeze; an env that has just finished is not
 sampled (its tensors already hold the next episode's reset state), so a game of L steps gives L - 1 samples.
 
-Out of scope: sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
+Control latency.  `Player(..., action_delay=K, obs_delay=K)` / `--action-delay`, `--obs-delay` and the sweep axes `action_delay`, `obs_delay`
+(whole control steps, 0 .. 15) put a delay line between the policy and the task: per control step obs_seen = obs_line.push(obs, done_prev),
+a = policy.act(obs_seen), a_applied = act_line.push(a, done_prev), task.step(a_applied).  `Delay` (include/ppenv_play_delay.h, which carries
+the rule in full — this build's own specification: the reference delays nothing and no oracle pins it) is a per-row ring on the device, one
+launch per push: from sample d of an episode on every output is exactly d control steps old, before that the episode's first sample is held
+(no artificial neutral command), and nothing is carried across a reset.  A line whose delays are all zero is not built, so the defaults are
+the player without the feature byte for byte.  The result gains `latency` = dict(control_dt, action_delay=[per cell], obs_delay=[per cell]).
+
+Out of scope: latency during training (the trainer and its collector are untouched), delays drawn per episode, action hold / policy decimation,
+per-cell observation or action noise, a VecTask-level latency setting; sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
 paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
 `--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
@@ -465,21 +475,80 @@ class ActuatorStats:
         return self._partial.cpu().numpy().tobytes()
 
 
+DELAY_MAX, DELAY_MAX_WIDTH = _lib.PLAY_DELAY_MAX, _lib.PLAY_DELAY_MAX_WIDTH
+
+
+class Delay:
+    """pp_play_delay_reset / pp_play_delay_push (include/ppenv_play_delay.h) on torch tensors: a delay line of whole control steps for a
+    [rows, width] float32 tensor, row r delayed by delays[r] (an int array [rows], 0 .. 15) — push(x, done) stores this control step's
+    sample and returns the one delays[r] steps old of the same episode, or the episode's first sample while there is none that old;
+    `done` ([rows] int64, the done the previous env step returned, or None right after reset()) marks the sample as the first of a new
+    episode of its env (agent 0's word, as everywhere in this module).  It owns the ring [max(delays) + 1, rows, width], the ages and the
+    output; x is not modified.  One launch per push, nothing here synchronises."""
+
+    def __init__(self, rows, width, delays, device, num_agents=1):
+        self.rows, self.width, self.num_agents = R, W, A = int(rows), int(width), int(num_agents)
+        if R < 1 or A not in (1, 2) or R % A or not 1 <= W <= DELAY_MAX_WIDTH:
+            raise ValueError(f"Delay: rows {rows} (>= 1, a multiple of num_agents), num_agents {num_agents} (1 or 2), width {width} (1..{DELAY_MAX_WIDTH})")
+        d = np.asarray(delays)
+        if d.shape != (R,) or d.dtype.kind not in "iu" or int(d.min()) < 0 or int(d.max()) > DELAY_MAX:
+            raise ValueError(f"Delay: delays must be an integer array [{R}] of whole control steps 0..{DELAY_MAX}, not {d.dtype} {list(d.shape)}" +
+                             (f" with values {int(d.min())}..{int(d.max())}" if d.size and d.dtype.kind in "iu" else ""))
+        self.delays = np.ascontiguousarray(d, np.int32)
+        self.depth = int(self.delays.max()) + 1                       # every delay < depth: what pp_play_delay_push leaves to its caller
+        self.device = dev = torch.device(device)
+        L = self.L = _lib.lib()
+        self._delay = torch.from_numpy(self.delays).to(dev)
+        self.age = torch.zeros(R, dtype=torch.int32, device=dev)
+        self.ring = torch.zeros((self.depth, R, W), dtype=torch.float32, device=dev)
+        assert self.ring.numel() * 4 == L.pp_play_delay_ring_bytes(R, W, self.depth)
+        self.out = torch.zeros((R, W), dtype=torch.float32, device=dev)
+        self.reset()
+
+    def reset(self):
+        _lib.check(self.L.pp_play_delay_reset(self.rows, self.age.data_ptr(), _lib.stream(self.device)), self.L)
+
+    def push(self, x, done=None):
+        """x: float32 [rows, width] on this device, unit stride along the row and a row stride >= width (a contiguous tensor, or the first
+        `width` columns of a wider one).  -> the [rows, width] output tensor (this object's: the next push overwrites it)."""
+        R, W = self.rows, self.width
+        if x.dtype != torch.float32 or x.device != self.device or tuple(x.shape) != (R, W) or (W > 1 and x.stride(1) != 1) or (R > 1 and x.stride(0) < W):
+            raise ValueError(f"Delay.push: x must be float32 [{R}, {W}] on {self.device} with unit stride along the row and a row stride >= {W}")
+        if done is not None and (done.dtype != torch.int64 or done.numel() != R or not done.is_contiguous() or done.device != self.device):
+            raise ValueError(f"Delay.push: done must be int64, contiguous [{R}] on {self.device}, or None")
+        _lib.check(self.L.pp_play_delay_push(x.data_ptr(), x.stride(0) if R > 1 else W, _lib.ptr(done), R, self.num_agents, W, self.depth, self._delay.data_ptr(),
+                                             self.age.data_ptr(), self.ring.data_ptr(), self.out.data_ptr(), W, _lib.stream(self.device)), self.L)
+        return self.out
+
+
 _AXIS = re.compile(r"^([A-Za-z_]\w*)(?:\[(\d+)\])?$")
 
 
 SERVE_AXES = serve.AXES_27DOF              # serve_speed, serve_tilt, serve_tilt_z; ball_y, ball_z (27-dof task only)
+DELAY_AXES = ("action_delay", "obs_delay")  # control latency in whole control steps: the command path, the sensing path
+
+
+def delay_steps(axis, v):
+    """A latency value -> the int 0 .. DELAY_MAX; 2.0 (the CLI's float parse) is 2.  Anything else — a fraction, a (lo, hi) range, a
+    value outside the range — raises ValueError naming the axis."""
+    try:
+        ok = not isinstance(v, (bool, tuple, list, str)) and float(v) == int(v) and 0 <= int(v) <= DELAY_MAX
+    except (TypeError, ValueError, OverflowError):
+        ok = False
+    if not ok:
+        raise ValueError(f"sweep axis {axis!r}: a delay is a number of whole control steps 0..{DELAY_MAX}, not {v!r}")
+    return int(v)
 
 
 def _axis(axis):
-    """'name' or 'name[row]' -> (table name, row or None), or (serve axis, None); a name that is neither a table of set_randomization nor a
-    serve axis raises ValueError."""
-    if isinstance(axis, str) and axis in SERVE_AXES:
+    """'name' or 'name[row]' -> (table name, row or None), or (serve axis, None), or (latency axis, None); a name that is none of these
+    raises ValueError."""
+    if isinstance(axis, str) and (axis in SERVE_AXES or axis in DELAY_AXES):
         return axis, None
     m = _AXIS.match(axis) if isinstance(axis, str) else None
     if m is None or m.group(1) not in TABLE_NAMES:
         raise ValueError(f"sweep axis {axis!r}: an axis is one of {', '.join(TABLE_NAMES)}, or one row of a table as name[row], or a serve axis: "
-                         f"{', '.join(SERVE_AXES)}")
+                         f"{', '.join(SERVE_AXES)}, or a latency axis in whole control steps: {', '.join(DELAY_AXES)}")
     return m.group(1), None if m.group(2) is None else int(m.group(2))
 
 
@@ -489,6 +558,9 @@ class Sweep:
     the plain axis of the same table in that row).  What a cell does not name stays 1.0.
     A SERVE axis (SERVE_AXES: serve_speed, serve_tilt, serve_tilt_z in degrees; ball_y, ball_z on the 27-dof task) maps to a number — the
     quantity is pinned, and may be negative — or a (lo, hi) range it is drawn from; what a cell does not name is the task's configured range.
+    A LATENCY axis (DELAY_AXES: action_delay, obs_delay) maps to a whole number of control steps 0 .. 15 — how old the command the env
+    consumes, or the observation the policy sees, is (Delay; Player) — and is seen by neither tables() nor serve_cells(); what a cell does
+    not name is the Player's keyword (default 0).
     paired: env i of every group is served the same sequence of balls (a serve plan keyed by the index within the group), with or
     without a serve axis."""
 
@@ -502,6 +574,9 @@ class Sweep:
                 if _axis(axis)[0] in SERVE_AXES:
                     lo, hi = serve.value_range(axis, v)
                     cell[axis] = lo if lo == hi else (lo, hi)
+                    continue
+                if axis in DELAY_AXES:
+                    cell[axis] = delay_steps(axis, v)
                     continue
                 cell[axis] = float(v)
                 if not math.isfinite(cell[axis]) or cell[axis] < 0.0:
@@ -554,21 +629,36 @@ class Sweep:
             return None
         return serve.resolve_cells(named, defaults, tuple(defaults))
 
-    def tables(self, rows_by_name, num_envs):
-        """The per-env tables of this sweep for an environment of num_envs envs whose tables have rows_by_name rows (its DR_TABLE_ROWS; 0: a
-        per-env scalar) -> {name: float32 array [rows, N] or [N]} for the tables some cell names; cell g fills columns [g * S, (g + 1) * S)."""
+    def _envs_per_cell(self, num_envs):
         G, N = len(self.cells), int(num_envs)
         if N < G or N % G:
             below = N // G * G
             raise ValueError(f"a sweep of {G} cells needs a multiple of {G} envs, not {N}: the nearest are " +
                              (f"{below} and {below + G}" if below > 0 else f"{G}"))
-        S = N // G
+        return N // G
+
+    def cell_delays(self, action_delay=0, obs_delay=0):
+        """-> {axis: [per cell, the cell's value or the keyword's]} for the two latency axes."""
+        default = dict(action_delay=delay_steps("action_delay", action_delay), obs_delay=delay_steps("obs_delay", obs_delay))
+        return {axis: [int(cell.get(axis, default[axis])) for cell in self.cells] for axis in DELAY_AXES}
+
+    def delays(self, num_envs, num_agents, action_delay=0, obs_delay=0):
+        """The per-row delays of this sweep for num_envs envs of num_agents rows each -> {axis: int32 [num_agents * num_envs]} for both
+        latency axes; cell g fills the rows [A * S * g, A * S * (g + 1)), with the keyword's value where it does not name the axis."""
+        S, A = self._envs_per_cell(num_envs), int(num_agents)
+        return {axis: np.repeat(np.asarray(per, np.int32), A * S) for axis, per in self.cell_delays(action_delay, obs_delay).items()}
+
+    def tables(self, rows_by_name, num_envs):
+        """The per-env tables of this sweep for an environment of num_envs envs whose tables have rows_by_name rows (its DR_TABLE_ROWS; 0: a
+        per-env scalar) -> {name: float32 array [rows, N] or [N]} for the tables some cell names; cell g fills columns [g * S, (g + 1) * S)."""
+        N = int(num_envs)
+        S = self._envs_per_cell(N)
         out = {}
         for plain in (True, False):                                  # the whole-table axes first, then the single rows over them
             for g, cell in enumerate(self.cells):
                 for axis, v in cell.items():
                     name, row = _axis(axis)
-                    if (row is None) != plain or name in SERVE_AXES:
+                    if (row is None) != plain or name in SERVE_AXES or name in DELAY_AXES:
                         continue
                     if name not in rows_by_name:
                         raise ValueError(f"sweep axis {axis!r}: this environment's tables are {', '.join(rows_by_name)}")
@@ -666,10 +756,19 @@ class Player:
     joint positions / velocities / drive torques and the policy's raw actions where they lie, and sums per joint and per cell how the
     return was earned: torque against the effort limit, speed against the velocity limit, position against the joint limits, mechanical
     energy per game.  It counts the same games under the same freeze as the totals.  The result gains `actuators` (read_actuators());
-    every other key, `groups` included, is what it is without the option, and what is played does not change."""
+    every other key, `groups` included, is what it is without the option, and what is played does not change.
+    action_delay, obs_delay: control latency in whole control steps (0 .. 15), for every env — or, with a sweep, for the cells that do not
+    name the axis of that name.  Per control step: obs_seen = obs_line.push(obs, done_prev); a = policy.act(obs_seen); a_applied =
+    act_line.push(a, done_prev); task.step(a_applied), done_prev being the done the previous task.step returned (None right after start()):
+    the env consumes the command of action_delay steps ago and the policy sees the observation of obs_delay steps ago, both held at the
+    episode's first sample until there is one that old, nothing carried across a reset (Delay; include/ppenv_play_delay.h).  A line whose
+    delays are all zero is not built — no allocation, no launch — so the defaults are today's player byte for byte.  `actions` stays the
+    policy's raw output (the actuator report's clip share reads it), `applied_actions` is what the env consumed, `policy_obs` what the
+    policy saw.  The lines sit between the policy and the task and compose with everything above, a `randomize: True` task included.  With
+    a line in use the result gains `latency` = dict(control_dt, action_delay=[per cell], obs_delay=[per cell])."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
-                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None, actuators=False):
+                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None, actuators=False, action_delay=0, obs_delay=0):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -734,6 +833,17 @@ class Player:
             G = 1 if sweep is None else len(sweep)
             self.act = ActuatorStats(task.num_envs // G, G, len(self._act_names), self.games_num, self._act_limits, thr, sim, num_agents=self.num_agents)
             self._act_inputs = task.env.joint_views()                     # the 27-dof AoS tensors, the 7-dof SoA planes: [N, D] views
+        rows = task.num_envs * self.num_agents
+        if sweep is None:
+            self._cell_delays = {axis: [delay_steps(axis, v)] for axis, v in (("action_delay", action_delay), ("obs_delay", obs_delay))}
+            per_row = {axis: np.full(rows, per[0], np.int32) for axis, per in self._cell_delays.items()}
+        else:
+            self._cell_delays = sweep.cell_delays(action_delay, obs_delay)
+            per_row = sweep.delays(task.num_envs, self.num_agents, action_delay, obs_delay)
+        # a line whose delays are all zero is not built: that path is the player without the feature
+        self._act_line = Delay(rows, task.num_actions, per_row["action_delay"], sim, self.num_agents) if per_row["action_delay"].any() else None
+        self._obs_line = Delay(rows, task.num_obs, per_row["obs_delay"], sim, self.num_agents) if per_row["obs_delay"].any() else None
+        self._done_prev = None
         self._runs = self._cell_actions = None
         if per_cell:                                                     # runs of consecutive cells that hold the same object: (policy, first row, end row)
             w, runs = self.num_agents * (task.num_envs // len(sweep)), []
@@ -751,7 +861,7 @@ class Player:
             self.outcome = task.enable_outcomes()
             self._latched = torch.zeros_like(self.outcome)
         self.steps_played = 0
-        self.actions = None
+        self.actions = self.applied_actions = self.policy_obs = None
         self._obs = None
 
     def end_sweep(self):
@@ -772,7 +882,8 @@ class Player:
         if self.sweep is not None:
             if self._episode0 is None:
                 self._episode0 = self.task.env.episode.clone()
-            if self._tables or self._serve_cells is None:             # (a sweep of serves alone keeps the plain step kernel)
+            latency = any(a in DELAY_AXES for cell in self.sweep.cells for a in cell)
+            if self._tables or (self._serve_cells is None and not latency):      # (a sweep of serves or of latency alone keeps the plain step kernel)
                 self.task.env.set_randomization(**self._tables)       # before the reset: the first counted episode is already the cell's
             if self._serve_cells is not None:                         # fill = serve 0; the reset below consumes it and leaves count 1
                 self.task.set_serve_plan(self._serve_cells, paired=self.sweep.paired)
@@ -785,30 +896,37 @@ class Player:
             self.pairs.reset()
         if self.act is not None:
             self.act.reset()
+        for line in (self._act_line, self._obs_line):
+            if line is not None:
+                line.reset()
+        self._done_prev = None
         for p in self._distinct:
             p._counter = 0
         self._obs = self.task.reset()["obs"]
         self.steps_played = 0
 
-    def _act_per_cell(self):
+    def _act_per_cell(self, obs):
         """Every run of cells under its own policy, into ONE [rows, num_actions] tensor: a policy owns its output buffer and may serve
         several runs, so each result is copied out before the next act()."""
         if self._cell_actions is None:
-            self._cell_actions = torch.empty((self._obs.shape[0], self.task.num_actions), dtype=torch.float32, device=self._obs.device)
+            self._cell_actions = torch.empty((obs.shape[0], self.task.num_actions), dtype=torch.float32, device=obs.device)
         for p, r0, r1 in self._runs:
-            a, _ = p.act(self._obs[r0:r1], deterministic=self.deterministic, seed=self.seed)
+            a, _ = p.act(obs[r0:r1], deterministic=self.deterministic, seed=self.seed)
             self._cell_actions[r0:r1].copy_(a)
         return self._cell_actions
 
     def step(self):
-        """One control step: policy -> task.step -> accumulate (-> record, with paired_diff).  No host read."""
+        """One control step: (obs line ->) policy (-> action line) -> task.step -> accumulate (-> record, with paired_diff).  No host read."""
         if self._obs is None:
             self.start()
+        self.policy_obs = self._obs if self._obs_line is None else self._obs_line.push(self._obs, self._done_prev)
         if self._runs is None:
-            self.actions, _ = self.policy.act(self._obs, deterministic=self.deterministic, seed=self.seed)
+            self.actions, _ = self.policy.act(self.policy_obs, deterministic=self.deterministic, seed=self.seed)
         else:
-            self.actions = self._act_per_cell()
-        obs, rew, done, _ = self.task.step(self.actions)
+            self.actions = self._act_per_cell(self.policy_obs)
+        self.applied_actions = self.actions if self._act_line is None else self._act_line.push(self.actions, self._done_prev)
+        obs, rew, done, _ = self.task.step(self.applied_actions)
+        self._done_prev = done
         if self.outcome is not None:
             self.stats.latch_outcome(self.outcome, self._latched)
         self.stats.accumulate(rew, done)
@@ -837,6 +955,10 @@ class Player:
         return dict(thresholds=dict(self.act.thresholds), joints=list(self._act_names), control_dt=dt,
                     total=actuator_summary(sum_act_totals(per), self._act_limits, self._act_names, dt),
                     groups=[dict(cell=dict(c), **actuator_summary(t, self._act_limits, self._act_names, dt)) for c, t in zip(cells, per)])
+
+    def latency(self):
+        """run()'s `latency`: the control dt in seconds and, per cell (one entry without a sweep), the two delays in control steps."""
+        return dict(control_dt=control_dt_of(self.task), **{axis: list(per) for axis, per in self._cell_delays.items()})
 
     def run(self, on_poll=None):
         """Play until games_num games are counted (seen at a poll) or max_steps control steps.  on_poll(totals dict): called after every
@@ -875,6 +997,8 @@ class Player:
                 out["captured_frames"] = self.recorder.captured
             if self.act is not None:
                 out["actuators"] = self.read_actuators()
+            if self._act_line is not None or self._obs_line is not None:
+                out["latency"] = self.latency()
             return out
         finally:
             self.end_sweep()
@@ -897,7 +1021,8 @@ def parse_args(argv=None):
     ap.add_argument("--sweep", action="append", default=None, metavar="AXIS=SPEC", help="play under a grid of physical-parameter scales in one pass (repeatable: "
                     "one axis each; the envs are split into one group per cell and --games is per cell): AXIS is dof_stiffness_scale, dof_damping_scale, "
                     "link_mass_scale, restitution_scale or friction_scale, or one row of a table as NAME[ROW], or a serve axis: serve_speed, serve_tilt, "
-                    "serve_tilt_z (degrees; may be negative), ball_y, ball_z (27-dof task); SPEC is lo:hi:count (inclusive) or v0,v1,...")
+                    "serve_tilt_z (degrees; may be negative), ball_y, ball_z (27-dof task), or a latency axis in whole control steps (0..15): action_delay, "
+                    "obs_delay; SPEC is lo:hi:count (inclusive) or v0,v1,...")
     ap.add_argument("--paired", action="store_true", help="with --sweep: env i of every cell is served the same sequence of balls (common random numbers), "
                     "so the serve noise cancels in the difference of two cells")
     ap.add_argument("--sweep-out", default=None, metavar="FILE.json", help="with --sweep: write the per-cell results (the result's `groups`) to FILE.json")
@@ -915,6 +1040,11 @@ def parse_args(argv=None):
     ap.add_argument("--vel-frac", type=float, default=None, help=f"with --actuators: at the velocity limit means |qd| >= this x the limit (default {ACT_THRESHOLDS['vel_frac']})")
     ap.add_argument("--limit-margin", type=float, default=None, help="with --actuators: at a position limit means within this many rad of it, or beyond "
                     f"(default {ACT_THRESHOLDS['limit_margin']})")
+    ap.add_argument("--action-delay", type=int, default=0, metavar="K", help=f"control latency of the command path: the env consumes the action of K control steps "
+                    f"ago (0..{DELAY_MAX}; the episode's first action is held until there is one that old); with --sweep, the value of the cells that do not "
+                    "name action_delay")
+    ap.add_argument("--obs-delay", type=int, default=0, metavar="K", help=f"control latency of the sensing path: the policy sees the observation of K control "
+                    f"steps ago (0..{DELAY_MAX}); with --sweep, the value of the cells that do not name obs_delay")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -949,12 +1079,22 @@ def parse_args(argv=None):
             ap.error("--baseline needs --paired-diff")
         if args.paired_out and not args.paired_diff:
             ap.error("--paired-out needs --paired-diff or --against")
+    for flag, axis in (("--action-delay", "action_delay"), ("--obs-delay", "obs_delay")):
+        if not 0 <= getattr(args, axis) <= DELAY_MAX:
+            ap.error(f"{flag} is a number of whole control steps 0..{DELAY_MAX}")
     if args.sweep:
         try:
             Sweep.parse(args.sweep)
         except ValueError as e:
             ap.error(str(e))
     return args
+
+
+def latency_line(lat):
+    """The CLI's head line for run()'s `latency`: per axis the cells' delays in control steps and in milliseconds."""
+    ms = 1000.0 * lat["control_dt"]
+    return f"latency: control dt {ms:.6g} ms; " + "; ".join(
+        f"{axis} {','.join(str(k) for k in lat[axis])} steps = {','.join(f'{k * ms:.6g}' for k in lat[axis])} ms" for axis in DELAY_AXES)
 
 
 def actuator_option(args):
@@ -1012,7 +1152,7 @@ def main(argv=None):
             print(f"checkpoint {k}: {p}", flush=True)
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
                 max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep, paired_diff=paired_diff,
-                baseline=baseline, actuators=actuator_option(args))
+                baseline=baseline, actuators=actuator_option(args), action_delay=getattr(args, "action_delay", 0), obs_delay=getattr(args, "obs_delay", 0))
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll
@@ -1027,6 +1167,8 @@ def main(argv=None):
 
     res = pl.run(on_poll=on_poll)
     print(f"av reward: {res['av_reward']} av steps: {res['av_steps']}")
+    if "latency" in res:
+        print(latency_line(res["latency"]))
     if args.outcomes:
         print("\n".join(outcome_lines(res["outcomes"])) if res["outcomes"]["windows"] > 0 else "no env has reset: no outcome window yet")
     for a, p in enumerate(res["per_agent"]):
@@ -1045,12 +1187,12 @@ def main(argv=None):
                 json.dump(res["actuators"], fh, indent=1)
             print(f"wrote {args.actuators_out}")
     if getattr(args, "sweep_out", None):
-        with open(args.sweep_out, "w") as fh:
+        with open(args.sweep_out, "w") as fh:                                  # (a cell's latency axes are in its `cell`, as ints)
             json.dump(res["groups"], fh, indent=1)
         print(f"wrote {args.sweep_out}")
     if getattr(args, "paired_out", None):
         with open(args.paired_out, "w") as fh:
-            json.dump(res["paired_diff"], fh, indent=1)
+            json.dump(dict(res["paired_diff"], latency=res["latency"]) if "latency" in res else res["paired_diff"], fh, indent=1)
         print(f"wrote {args.paired_out}")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
     if recorder is not None and args.capture_trajectory:
