@@ -35,7 +35,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_play_pair_device.h"), os.path.join(ROOT, "include", "ppenv_play_pair.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_act_device.h"), os.path.join(ROOT, "include", "ppenv_play_act.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay_device.h"), os.path.join(ROOT, "include", "ppenv_play_delay.h"),
-           os.path.join(_PKG, "csrc", "ppenv_host.h")]
+           os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
 # the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);

@@ -1,5 +1,5 @@
 // ppenv_host.h — host-side plumbing shared by the translation units of libppenv: the error text, HIP call and launch checks,
-// device selection and the handles' status word.  Internal and host-only: no part of the ABI (include/*.h), exports nothing.
+// grid sizes, device selection and the handles' status word.  Internal and host-only: no part of the ABI (include/*.h), exports nothing.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -38,6 +38,9 @@ inline int pp_launched(const char* what) {
     ppenv_set_error(what);
     return PPENV_EHIP;
 }
+
+// workgroups of `block` lanes that cover n items (n up to 2^31 - 1 table entries: the count is formed in 64 bits)
+inline uint32_t pp_blocks_of(int64_t n, int block) { return (uint32_t)((n + block - 1) / block); }
 
 // every entry point of a handle launches on the device the handle was created on, whatever the caller's current device is
 inline int pp_use_device(int id) {

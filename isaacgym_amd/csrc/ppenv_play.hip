@@ -5,8 +5,8 @@
 // ppo_loss_grad_kernel / ppo_loss_reduce_kernel:
 //   play_rows_kernel     workgroup (x, y) of a P x G grid is chunk x of group y (P = chunks of 256 envs in S, counted from the group's first
 //                        env, ragged last chunk per group guarded); a lane owns one env: the per-env step of ppenv_play_device.h, then the workgroup's
-//                        finished games summed in a fixed order (xor butterfly within a wave, the four waves in order through LDS) into
-//                        ONE ppenv_play_partial.  Reads totals[g].games for the freeze; writes no word of the totals.
+//                        finished games summed in a fixed order (ppenv_reduce_device.h: xor butterfly within a wave, strides 32 down to 1,
+//                        the four waves in order through LDS) into ONE ppenv_play_partial.  Reads totals[g].games for the freeze; writes no word of the totals.
 //   play_totals_kernel   one wave per group: lane l sums the group's partials l, l + 64, ... in order, a butterfly, lane 0 adds the result
 //                        to totals[g].
 // The totals are written by the second launch only, and wave g of it reads and writes totals[g] alone: nothing a workgroup reads is
@@ -20,34 +20,19 @@
 #include <cstdint>
 
 #include "ppenv_play_device.h"
+#include "ppenv_reduce_device.h"
 #include "../../include/ppenv_play_group.h"
 
-#include "ppenv_host.h"
+#include "ppenv_play_host.h"
 
 namespace {
 
 constexpr int kBlock = PPENV_PLAY_BLOCK;
 constexpr int kWaves = kBlock / 64;
 
-inline int32_t blocks_of(int32_t n) { return (n + kBlock - 1) / kBlock; }
-
-// Every lane ends with the same partial: at each stage both partners form a + b and b + a, which are the same bits.
-__device__ __forceinline__ void wave_merge(ppenv_play_partial& p) {
-    #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        ppenv_play_partial o;
-        o.games = __shfl_xor((long long)p.games, off, 64);
-        o.steps = __shfl_xor((long long)p.steps, off, 64);
-        #pragma unroll
-        for (int a = 0; a < PPENV_PLAY_MAX_AGENTS; ++a) {
-            o.reward[a] = __shfl_xor(p.reward[a], off, 64);
-            o.reward_sq[a] = __shfl_xor(p.reward_sq[a], off, 64);
-            o.reward_min[a] = __shfl_xor(p.reward_min[a], off, 64);
-            o.reward_max[a] = __shfl_xor(p.reward_max[a], off, 64);
-        }
-        pp::play_merge(p, o);
-    }
-}
+struct Merge {
+    __device__ void operator()(ppenv_play_partial& into, const ppenv_play_partial& from) const { pp::play_merge(into, from); }
+};
 
 // Workgroup (x, y) is chunk x of group y: a workgroup belongs to one group, so the freeze test is uniform in it.
 __global__ __launch_bounds__(kBlock) void play_rows_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t envs_per_group,
@@ -57,19 +42,11 @@ __global__ __launch_bounds__(kBlock) void play_rows_kernel(const float* __restri
     __shared__ ppenv_play_partial wave_part[kWaves];
     const int32_t g = (int32_t)blockIdx.y, chunk = (int32_t)blockIdx.x;
     if (pp::play_frozen(totals[g].games, games_num)) return;     // uniform: the whole workgroup leaves (its partial is not read either)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int32_t local = chunk * kBlock + tid;                  // the env's index within its group
+    const int32_t local = chunk * kBlock + (int32_t)threadIdx.x;     // the env's index within its group
     ppenv_play_partial acc;
     pp::play_clear(acc);
     if (local < envs_per_group) pp::play_env(g * envs_per_group + local, num_agents, rew, done, cur_reward, cur_steps, acc);
-    wave_merge(acc);
-    if (lane == 0) wave_part[wave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        ppenv_play_partial s = wave_part[0];
-        for (int w = 1; w < kWaves; ++w) pp::play_merge(s, wave_part[w]);
-        partial[g * parts + chunk] = s;
-    }
+    if (pp::block_reduce(acc, wave_part, Merge())) partial[g * parts + chunk] = acc;
 }
 
 __global__ __launch_bounds__(64) void play_totals_kernel(const ppenv_play_partial* __restrict__ partial, int32_t parts, int64_t games_num,
@@ -80,7 +57,7 @@ __global__ __launch_bounds__(64) void play_totals_kernel(const ppenv_play_partia
     ppenv_play_partial acc;
     pp::play_clear(acc);
     for (int32_t b = (int32_t)threadIdx.x; b < parts; b += 64) pp::play_merge(acc, mine[b]);
-    wave_merge(acc);
+    pp::wave_butterfly(acc, Merge());
     if (threadIdx.x == 0) {
         ppenv_play_totals t = totals[g];
         pp::play_totals_add(t, acc);
@@ -100,22 +77,16 @@ __global__ __launch_bounds__(kBlock) void play_reset_kernel(int32_t num_envs, in
     }
 }
 
-// What both pairs of entries require of the sizes; the plain ones are groups = 1 and have no group bound to break.
-bool sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents) {
-    return groups >= 1 && groups <= PP_PLAY_GROUP_MAX && envs_per_group > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS &&
-           (int64_t)envs_per_group * groups * num_agents <= INT32_MAX;
-}
-
 // The launches, after the entry's own validation.
 int launch_reset(int32_t envs_per_group, int32_t groups, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
     const int32_t num_envs = envs_per_group * groups, rows = num_envs * num_agents;
-    hipLaunchKernelGGL(play_reset_kernel, dim3(blocks_of(rows)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, groups, cur_reward, cur_steps, totals);
+    hipLaunchKernelGGL(play_reset_kernel, dim3(pp_blocks_of(rows, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, num_envs, rows, groups, cur_reward, cur_steps, totals);
     return pp_launched("launching play_reset_kernel failed");
 }
 
 int launch_accumulate(const float* rew, const int64_t* done, int32_t envs_per_group, int32_t groups, int32_t num_agents, int64_t games_num, float* cur_reward,
                       int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
-    const int32_t parts = blocks_of(envs_per_group);             // per group; groups * parts <= 2^31 / 256 workgroups
+    const int32_t parts = pp_blocks_of(envs_per_group, kBlock);  // per group; groups * parts <= 2^31 / 256 workgroups
     hipLaunchKernelGGL(play_rows_kernel, dim3((uint32_t)parts, (uint32_t)groups), dim3(kBlock), 0, (hipStream_t)stream, rew, done, envs_per_group, parts,
                        num_agents, games_num, cur_reward, cur_steps, totals, partial);
     if (int rc = pp_launched("launching play_rows_kernel failed")) return rc;
@@ -127,11 +98,11 @@ int launch_accumulate(const float* rew, const int64_t* done, int32_t envs_per_gr
 
 // ---- the plain entries (include/ppenv_play.h): one population, the G = 1 case ------------------------------------------------------------
 extern "C" size_t ppenv_play_partial_bytes(int32_t num_envs) {
-    return num_envs > 0 ? (size_t)blocks_of(num_envs) * sizeof(ppenv_play_partial) : 0;
+    return num_envs > 0 ? (size_t)pp_blocks_of(num_envs, kBlock) * sizeof(ppenv_play_partial) : 0;
 }
 
 extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, void* stream) {
-    if (!sizes_ok(num_envs, 1, num_agents) || !cur_reward || !cur_steps || !totals) {
+    if (!pp_play_sizes_ok(num_envs, 1, num_agents) || !cur_reward || !cur_steps || !totals) {
         ppenv_set_error("ppenv_play_reset: NULL pointer, num_envs <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
         return PPENV_EINVAL;
     }
@@ -140,7 +111,7 @@ extern "C" int ppenv_play_reset(int32_t num_envs, int32_t num_agents, float* cur
 
 extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int32_t num_envs, int32_t num_agents, int64_t games_num, float* cur_reward,
                                      int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
-    if (!sizes_ok(num_envs, 1, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+    if (!pp_play_sizes_ok(num_envs, 1, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
         ppenv_set_error("ppenv_play_accumulate: NULL pointer, num_envs <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, or games_num < 1");
         return PPENV_EINVAL;
     }
@@ -149,12 +120,12 @@ extern "C" int ppenv_play_accumulate(const float* rew, const int64_t* done, int3
 
 // ---- the grouped entries (include/ppenv_play_group.h): G populations of S envs, each with its own totals and its own freeze -------------
 extern "C" size_t pp_play_group_partial_bytes(int32_t envs_per_group, int32_t groups) {
-    return sizes_ok(envs_per_group, groups, 1) ? (size_t)groups * (size_t)blocks_of(envs_per_group) * sizeof(ppenv_play_partial) : 0;
+    return pp_play_sizes_ok(envs_per_group, groups, 1) ? (size_t)groups * (size_t)pp_blocks_of(envs_per_group, kBlock) * sizeof(ppenv_play_partial) : 0;
 }
 
 extern "C" int pp_play_group_reset(int32_t envs_per_group, int32_t groups, int32_t num_agents, float* cur_reward, int32_t* cur_steps,
                                    ppenv_play_totals* totals, void* stream) {
-    if (!sizes_ok(envs_per_group, groups, num_agents) || !cur_reward || !cur_steps || !totals) {
+    if (!pp_play_sizes_ok(envs_per_group, groups, num_agents) || !cur_reward || !cur_steps || !totals) {
         ppenv_set_error("pp_play_group_reset: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, or more than 2^31 - 1 rows");
         return PPENV_EINVAL;
     }
@@ -163,7 +134,7 @@ extern "C" int pp_play_group_reset(int32_t envs_per_group, int32_t groups, int32
 
 extern "C" int pp_play_group_accumulate(const float* rew, const int64_t* done, int32_t envs_per_group, int32_t groups, int32_t num_agents, int64_t games_num,
                                         float* cur_reward, int32_t* cur_steps, ppenv_play_totals* totals, ppenv_play_partial* partial, void* stream) {
-    if (!sizes_ok(envs_per_group, groups, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
+    if (!pp_play_sizes_ok(envs_per_group, groups, num_agents) || !rew || !done || !cur_reward || !cur_steps || !totals || !partial || games_num < 1) {
         ppenv_set_error("pp_play_group_accumulate: NULL pointer, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, more than 2^31 - 1 rows, "
                         "or games_num < 1");
         return PPENV_EINVAL;

@@ -5,7 +5,9 @@
 //   play_act_rows_kernel     workgroup (x, y) is chunk x of group y (chunks of 256 envs counted from the group's first env, the ragged
 //                            last one guarded); a lane owns one env: a sample (the dof loop of ppenv_play_act_device.h) or a fold.  The
 //                            folds of the workgroup are summed in a fixed order — xor butterfly within a wave (strides 1 up to 32, four of
-//                            the six stages as DPP row operations: wave_merge), the four waves in order through LDS — into ONE partial: a pp_play_act_group and D pp_play_act_joint.  A workgroup in which no env
+//                            the six stages as DPP row operations: wave_merge), the four waves in order through LDS — into ONE partial: a
+//                            pp_play_act_group and D pp_play_act_joint.  (The other accounting kernels share ppenv_reduce_device.h, whose
+//                            butterfly runs 32 down to 1 through permutes; this unit keeps its own exchange for the DPP stages.)  A workgroup in which no env
 //                            finished skips all of that and writes the empty partial (a uniform branch: __syncthreads_or).
 //   play_act_totals_kernel   one workgroup per group, one wave per three dofs: lane l sums the group's partials l, l + 64, ... of the wave's
 //                            dofs in order, a butterfly, a lane adds the result to joint[g * D + d]; wave 0 does the same for group[g]
@@ -26,7 +28,7 @@
 
 #include "ppenv_play_act_device.h"
 
-#include "ppenv_host.h"
+#include "ppenv_play_host.h"
 
 namespace {
 
@@ -35,8 +37,6 @@ constexpr int kWaves = kBlock / 64;
 constexpr int kFold = 3;                                         // dofs whose folds run side by side in play_act_rows_kernel
 constexpr int kTotalsBlock = 64 * ((PP_PLAY_ACT_MAX_DOF + kFold - 1) / kFold);      // play_act_totals_kernel: at most one wave per kFold dofs
 constexpr int kResetBlocks = 4096;                              // the reset's grid-stride cap
-
-inline int32_t blocks_of(int32_t n) { return (n + kBlock - 1) / kBlock; }
 
 // The xor butterfly runs from stride 1 up to 32.  Every lane ends with the same sums: at each stage both partners form a + b and b + a,
 // which are the same bits — so after the strides below `off` all lanes of an aligned group of `off` lanes hold the same bits, and the
@@ -248,8 +248,7 @@ __global__ __launch_bounds__(kBlock) void play_act_reset_kernel(int64_t words, i
 }
 
 bool sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents, int32_t num_dofs) {
-    return groups >= 1 && groups <= PP_PLAY_GROUP_MAX && envs_per_group > 0 && num_agents >= 1 && num_agents <= PPENV_PLAY_MAX_AGENTS &&
-           (int64_t)envs_per_group * groups * num_agents <= INT32_MAX && num_dofs >= 1 && num_dofs <= PP_PLAY_ACT_MAX_DOF && num_dofs % num_agents == 0;
+    return pp_play_sizes_ok(envs_per_group, groups, num_agents) && num_dofs >= 1 && num_dofs <= PP_PLAY_ACT_MAX_DOF && num_dofs % num_agents == 0;
 }
 
 const char kSizes[] = "num_dofs outside 1..32 or no multiple of num_agents, groups outside 1..1024, envs_per_group <= 0, num_agents not 1 or 2, or more than "
@@ -263,7 +262,7 @@ extern "C" size_t pp_play_act_state_bytes(int32_t envs_per_group, int32_t groups
 
 extern "C" size_t pp_play_act_partial_bytes(int32_t envs_per_group, int32_t groups, int32_t num_dofs) {
     return sizes_ok(envs_per_group, groups, 1, num_dofs)
-               ? (size_t)groups * (size_t)blocks_of(envs_per_group) * (sizeof(pp_play_act_group) + (size_t)num_dofs * sizeof(pp_play_act_joint))
+               ? (size_t)groups * (size_t)pp_blocks_of(envs_per_group, kBlock) * (sizeof(pp_play_act_group) + (size_t)num_dofs * sizeof(pp_play_act_joint))
                : 0;
 }
 
@@ -288,7 +287,7 @@ extern "C" int pp_play_act_accumulate(const pp_play_act_inputs* in, const int64_
         pp_set_errorf("pp_play_act_accumulate: NULL pointer, %s, or games_num < 1", kSizes);
         return PPENV_EINVAL;
     }
-    const int32_t parts = blocks_of(envs_per_group);             // per group
+    const int32_t parts = pp_blocks_of(envs_per_group, kBlock);  // per group
     pp_play_act_group* gpart = (pp_play_act_group*)partial;      // [G * parts], then the joints' [G * parts * D]: both 8-byte aligned
     pp_play_act_joint* jpart = (pp_play_act_joint*)(gpart + (size_t)groups * parts);
     hipLaunchKernelGGL(play_act_rows_kernel, dim3((uint32_t)parts, (uint32_t)groups), dim3(kBlock), 0, (hipStream_t)stream, *in, done, envs_per_group, parts,

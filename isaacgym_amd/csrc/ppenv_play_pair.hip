@@ -5,8 +5,8 @@
 //   play_pair_record_kernel   one lane per env, every step: the per-env step of ppenv_play_pair_device.h.  An env reads and writes its
 //                             own words alone.
 //   play_pair_reduce_kernel   at polls only: workgroup g is cell g; lane l sums the pairs l, l + 256, ... in order, an xor butterfly
-//                             within the wave, the four waves in order through LDS, thread 0 OVERWRITES out[g].  It reads the table
-//                             and writes out[g] alone: idempotent.
+//                             within the wave (strides 32 down to 1), the four waves in order through LDS (ppenv_reduce_device.h),
+//                             thread 0 OVERWRITES out[g].  It reads the table and writes out[g] alone: idempotent.
 //   play_pair_reset_kernel    one lane per table entry: ret to quiet NaN, everything else to zero.
 // No atomics, no hand-off between workgroups; every sum has a fixed order.
 //
@@ -17,33 +17,18 @@
 #include <cstdint>
 
 #include "ppenv_play_pair_device.h"
+#include "ppenv_reduce_device.h"
 
-#include "ppenv_host.h"
+#include "ppenv_play_host.h"
 
 namespace {
 
 constexpr int kBlock = PPENV_PLAY_BLOCK;
 constexpr int kWaves = kBlock / 64;
 
-inline uint32_t blocks_of(int64_t n) { return (uint32_t)((n + kBlock - 1) / kBlock); }
-
-// Every lane ends with the same sums: at each stage both partners form a + b and b + a, which are the same bits.
-__device__ __forceinline__ void wave_merge(pp_play_pair_totals& t) {
-    #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        pp_play_pair_totals o;
-        o.pairs = __shfl_xor((long long)t.pairs, off, 64);
-        o.steps_diff = __shfl_xor((long long)t.steps_diff, off, 64);
-        #pragma unroll
-        for (int a = 0; a < PPENV_PLAY_MAX_AGENTS; ++a) {
-            o.diff[a] = __shfl_xor(t.diff[a], off, 64);
-            o.diff_sq[a] = __shfl_xor(t.diff_sq[a], off, 64);
-            o.cell[a] = __shfl_xor(t.cell[a], off, 64);
-            o.base[a] = __shfl_xor(t.base[a], off, 64);
-        }
-        pp::play_pair_merge(t, o);
-    }
-}
+struct Merge {
+    __device__ void operator()(pp_play_pair_totals& into, const pp_play_pair_totals& from) const { pp::play_pair_merge(into, from); }
+};
 
 __global__ __launch_bounds__(kBlock) void play_pair_record_kernel(const float* __restrict__ rew, const int64_t* __restrict__ done, int32_t num_envs,
                                                                   int32_t num_agents, int32_t episodes, float* __restrict__ cur_reward,
@@ -59,19 +44,13 @@ __global__ __launch_bounds__(kBlock) void play_pair_reduce_kernel(int32_t envs_p
                                                                   pp_play_pair_totals* __restrict__ out) {
     __shared__ pp_play_pair_totals wave_part[kWaves];
     const int32_t g = (int32_t)blockIdx.x, b = baseline[g];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     pp_play_pair_totals acc;
     pp::play_pair_clear(acc);
     const bool ok = pp::play_pair_baseline_ok(b, groups);        // uniform in the workgroup
-    if (ok) pp::play_pair_lane(tid, kBlock, g, b, envs_per_group, num_agents, episodes, count, ret, len, acc);
-    wave_merge(acc);
-    if (lane == 0) wave_part[wave] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        pp_play_pair_totals s = wave_part[0];
-        for (int w = 1; w < kWaves; ++w) pp::play_pair_merge(s, wave_part[w]);
-        if (!ok) s.pairs = -1;
-        out[g] = s;
+    if (ok) pp::play_pair_lane((int)threadIdx.x, kBlock, g, b, envs_per_group, num_agents, episodes, count, ret, len, acc);
+    if (pp::block_reduce(acc, wave_part, Merge())) {
+        if (!ok) acc.pairs = -1;
+        out[g] = acc;
     }
 }
 
@@ -89,9 +68,8 @@ __global__ __launch_bounds__(kBlock) void play_pair_reset_kernel(int64_t n_ret, 
 }
 
 bool sizes_ok(int32_t envs_per_group, int32_t groups, int32_t num_agents, int32_t episodes) {
-    if (groups < 1 || groups > PP_PLAY_GROUP_MAX || envs_per_group < 1 || num_agents < 1 || num_agents > PPENV_PLAY_MAX_AGENTS || episodes < 1) return false;
-    const int64_t envs = (int64_t)envs_per_group * groups;       // < 2^41
-    return envs <= INT32_MAX && envs * num_agents <= INT32_MAX && envs * num_agents <= INT32_MAX / (int64_t)episodes;
+    return pp_play_sizes_ok(envs_per_group, groups, num_agents) && episodes >= 1 &&
+           (int64_t)envs_per_group * groups * num_agents <= INT32_MAX / (int64_t)episodes;        // the table's entries
 }
 
 const char kSizes[] = "groups outside 1..1024, envs_per_group < 1, num_agents not 1 or 2, episodes < 1, or more than 2^31 - 1 table entries";
@@ -113,7 +91,7 @@ extern "C" int pp_play_pair_reset(int32_t envs_per_group, int32_t groups, int32_
         return PPENV_EINVAL;
     }
     const int64_t num_envs = (int64_t)envs_per_group * groups, rows = num_envs * num_agents, n_len = num_envs * episodes, n_ret = n_len * num_agents;
-    hipLaunchKernelGGL(play_pair_reset_kernel, dim3(blocks_of(n_ret)), dim3(kBlock), 0, (hipStream_t)stream, n_ret, n_len, rows, num_envs, cur_reward,
+    hipLaunchKernelGGL(play_pair_reset_kernel, dim3(pp_blocks_of(n_ret, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, n_ret, n_len, rows, num_envs, cur_reward,
                        cur_steps, count, ret, len);
     return pp_launched("launching play_pair_reset_kernel failed");
 }
@@ -125,7 +103,7 @@ extern "C" int pp_play_pair_record(const float* rew, const int64_t* done, int32_
         return PPENV_EINVAL;
     }
     const int32_t num_envs = envs_per_group * groups;
-    hipLaunchKernelGGL(play_pair_record_kernel, dim3(blocks_of(num_envs)), dim3(kBlock), 0, (hipStream_t)stream, rew, done, num_envs, num_agents, episodes,
+    hipLaunchKernelGGL(play_pair_record_kernel, dim3(pp_blocks_of(num_envs, kBlock)), dim3(kBlock), 0, (hipStream_t)stream, rew, done, num_envs, num_agents, episodes,
                        cur_reward, cur_steps, count, ret, len);
     return pp_launched("launching play_pair_record_kernel failed");
 }

@@ -22,6 +22,7 @@
 
 #include "../../include/ppenv.h"
 #include "../../include/ppenv_ppo.h"
+#include "ppenv_reduce_device.h"
 
 #include "ppenv_host.h"
 
@@ -31,18 +32,6 @@ constexpr int kLossThreads = 256;                 // 4 waves, one row per lane
 constexpr int kOptThreads = 256;
 constexpr int PS = PPENV_PPO_PARTIAL_STRIDE;
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
-
-__device__ __forceinline__ float wave_sum(float v) {
-    #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 // ---- loss gradient: one lane per row, one partial row per workgroup -------------------------------------------------------------
 __global__ void __launch_bounds__(kLossThreads) ppo_loss_grad_kernel(ppenv_ppo_loss_args p) {
@@ -108,12 +97,13 @@ __global__ void __launch_bounds__(kLossThreads) ppo_loss_grad_kernel(ppenv_ppo_l
             const float z = (act[j] - mu[j]) / sg;
             t = g * (1.0f - z * z);
         }
-        t = wave_sum(t);
+        pp::wave_butterfly(t, pp::add());
         if (lane == 0) wsum[wave][j] = t;
     }
     const float terms[5] = {al, cl, bl, kl, clipped};
     for (int k = 0; k < 5; ++k) {
-        const float t = wave_sum(valid ? terms[k] : 0.0f);
+        float t = valid ? terms[k] : 0.0f;
+        pp::wave_butterfly(t, pp::add());
         if (lane == 0) wsum[wave][PPENV_PPO_MAX_ACTIONS + k] = t;
     }
     __syncthreads();
@@ -182,7 +172,7 @@ __device__ void load_table(const ppenv_ppo_tensor* t, int count, Table& s) {
 
 __device__ __forceinline__ double block_sum(double v, double* red) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    v = wave_sum(v);
+    pp::wave_butterfly(v, pp::add());
     if (lane == 0) red[wave] = v;
     __syncthreads();
     double s = 0.0;

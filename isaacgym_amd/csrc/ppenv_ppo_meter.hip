@@ -5,9 +5,9 @@
 // play_totals_kernel:
 //   meter_rows_kernel    lane e owns env e (256 envs per workgroup, ragged tail guarded) and walks t = 0 .. h-1 with its running return and
 //                        length in registers, kChunk steps at a time: the chunk's rewards and done words are loaded first (independent
-//                        loads, one wait), then per step the wave's finished games are summed by an xor butterfly (skipped, wave-uniformly,
-//                        when no lane finished) and left in LDS; after the chunk one lane per step adds the four waves in order and writes
-//                        the workgroup's ppenv_ppo_meter_partial for that step.
+//                        loads, one wait), then per step the wave's finished games are summed by an xor butterfly (ppenv_reduce_device.h,
+//                        strides 32 down to 1; skipped, wave-uniformly, when no lane finished) and left in LDS; after the chunk one lane
+//                        per step adds the four waves in order and writes the workgroup's ppenv_ppo_meter_partial for that step.
 //   meter_update_kernel  one wave, for t in order: lane l sums partials l, l + 64, ... in order, a butterfly, AverageMeter.update.
 // The meter is written by the second launch only, which has one workgroup; cur_reward / cur_len and the partials are written by the
 // lane / workgroup that owns them: nothing a workgroup reads is written by another one in the same launch, without atomics, tickets
@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "ppenv_ppo_meter_device.h"
+#include "ppenv_reduce_device.h"
 
 #include "ppenv_host.h"
 
@@ -29,26 +30,16 @@ constexpr int kBlock = PPENV_PPO_METER_BLOCK;
 constexpr int kWaves = kBlock / 64;
 constexpr int kChunk = 16;                         // steps whose rewards and done words a lane holds at once
 
-inline int32_t blocks_of(int32_t n) { return (n + kBlock - 1) / kBlock; }
-
-// Every lane ends with the same partial: at each stage both partners form a + b and b + a, which are the same bits.
-__device__ __forceinline__ void wave_merge(ppenv_ppo_meter_partial& p) {
-    #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-        ppenv_ppo_meter_partial o;
-        o.sum = __shfl_xor(p.sum, off, 64);
-        o.len = __shfl_xor((long long)p.len, off, 64);
-        o.count = __shfl_xor(p.count, off, 64);
-        pp::meter_merge(p, o);
-    }
-}
+struct Merge {
+    __device__ void operator()(ppenv_ppo_meter_partial& into, const ppenv_ppo_meter_partial& from) const { pp::meter_merge(into, from); }
+};
 
 __global__ __launch_bounds__(kBlock) void meter_rows_kernel(const float* __restrict__ rew, int64_t ld_rew, const int64_t* __restrict__ done,
                                                             int64_t ld_done, int32_t h, int32_t num_envs, int32_t num_agents,
                                                             float* __restrict__ cur_reward, int32_t* __restrict__ cur_len,
                                                             ppenv_ppo_meter_partial* __restrict__ partial, int32_t parts) {
     __shared__ ppenv_ppo_meter_partial wave_part[kChunk][kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int32_t e = (int32_t)(blockIdx.x * kBlock + tid);
     const bool live = e < num_envs;
     const size_t col = (size_t)num_agents * (size_t)(live ? e : 0);      // agent 0's row of the env
@@ -70,16 +61,13 @@ __global__ __launch_bounds__(kBlock) void meter_rows_kernel(const float* __restr
                 ppenv_ppo_meter_partial fin;
                 pp::meter_clear(fin);
                 if (live) pp::meter_env_step(r[j], d[j], cr, cl, fin);
-                if (__ballot(fin.count != 0) != 0ull) wave_merge(fin);   // wave-uniform; without it lane 0 holds zeros: no lane finished
-                if (lane == 0) wave_part[j][wave] = fin;
+                // wave-uniform; without it lane 0 holds zeros: no lane finished
+                if (__ballot(fin.count != 0) != 0ull) pp::wave_butterfly(fin, Merge());
+                pp::wave_store(wave_part[j], fin);
             }
         }
         __syncthreads();
-        if (tid < nt) {
-            ppenv_ppo_meter_partial s = wave_part[tid][0];
-            for (int w = 1; w < kWaves; ++w) pp::meter_merge(s, wave_part[tid][w]);
-            partial[(size_t)(t0 + tid) * (size_t)parts + blockIdx.x] = s;
-        }
+        if (tid < nt) partial[(size_t)(t0 + tid) * (size_t)parts + blockIdx.x] = pp::waves_in_order(wave_part[tid], Merge());
         __syncthreads();                                                 // the next chunk rewrites wave_part
     }
     if (live) {
@@ -96,7 +84,7 @@ __global__ __launch_bounds__(64) void meter_update_kernel(const ppenv_ppo_meter_
         pp::meter_clear(acc);
         for (int32_t b = (int32_t)threadIdx.x; b < parts; b += 64) pp::meter_merge(acc, partial[(size_t)t * (size_t)parts + b]);
         if (__ballot(acc.count != 0) == 0ull) continue;                  // wave-uniform: nobody finished at t
-        wave_merge(acc);
+        pp::wave_butterfly(acc, Merge());
         pp::meter_apply(m, acc, games_to_track);
     }
     if (threadIdx.x == 0) *meter = m;
@@ -105,7 +93,7 @@ __global__ __launch_bounds__(64) void meter_update_kernel(const ppenv_ppo_meter_
 }  // namespace
 
 extern "C" size_t ppo_meter_partial_bytes(int32_t h, int32_t num_envs) {
-    return h > 0 && num_envs > 0 ? (size_t)h * (size_t)blocks_of(num_envs) * sizeof(ppenv_ppo_meter_partial) : 0;
+    return h > 0 && num_envs > 0 ? (size_t)h * (size_t)pp_blocks_of(num_envs, kBlock) * sizeof(ppenv_ppo_meter_partial) : 0;
 }
 
 extern "C" int ppo_meter_update(const float* rew, int64_t ld_rew, const int64_t* done, int64_t ld_done, int32_t h, int32_t num_envs, int32_t num_agents,
@@ -118,7 +106,7 @@ extern "C" int ppo_meter_update(const float* rew, int64_t ld_rew, const int64_t*
                         "num_agents x num_envs, or games_to_track < 1");
         return PPENV_EINVAL;
     }
-    const int32_t parts = blocks_of(num_envs);
+    const int32_t parts = pp_blocks_of(num_envs, kBlock);
     hipLaunchKernelGGL(meter_rows_kernel, dim3(parts), dim3(kBlock), 0, (hipStream_t)stream, rew, ld_rew, done, ld_done, h, num_envs, num_agents,
                        cur_reward, cur_len, partial, parts);
     if (int rc = pp_launched("launching meter_rows_kernel failed")) return rc;

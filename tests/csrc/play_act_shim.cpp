@@ -2,6 +2,7 @@
 // host and summed in the kernels' order, as play_pair_shim.cpp does for the paired statistics.  TEST INFRASTRUCTURE ONLY.  Built by
 // tests/play_act_shim_binding.py with -ffp-contract=off and WITHOUT -ffinite-math-only (max_exc starts at -inf).
 #include "../../isaacgym_amd/csrc/ppenv_play_act_device.h"
+#include "butterfly_host.h"
 
 namespace {
 
@@ -15,39 +16,15 @@ struct JointOps {
     void operator()(pp_play_act_joint& into, const pp_play_act_joint& from) const { pp::act_joint_merge(into, from); }
 };
 
-// play_act_rows_kernel's sum of one chunk: every wave of 64 by the xor butterfly, strides 1 up to 32 (stage by stage, each lane adding its
-// partner's value of before the stage), then the waves in order.
-template <class T, class Merge>
-T chunk_sum(T* lane, Merge merge) {
-    T next[PPENV_PLAY_BLOCK];
-    for (int off = 1; off <= 32; off <<= 1) {
-        for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) {
-            next[l] = lane[l];
-            merge(next[l], lane[l ^ off]);
-        }
-        for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) lane[l] = next[l];
-    }
-    T s = lane[0];
-    for (int w = 1; w < PPENV_PLAY_BLOCK / 64; ++w) merge(s, lane[64 * w]);
-    return s;
-}
-
 // play_act_totals_kernel's sum of a group's partials (stride `step` apart): lane l takes l, l + 64, ... in order, then the butterfly.
 template <class T, class Ops>
 T wave_sum(const T* part, int32_t parts, size_t step, Ops merge) {
-    T lane[64], next[64];
+    T lane[64];
     for (int l = 0; l < 64; ++l) {
         merge(lane[l]);                                          // with one argument: Ops' clear
         for (int32_t b = l; b < parts; b += 64) merge(lane[l], part[(size_t)b * step]);
     }
-    for (int off = 1; off <= 32; off <<= 1) {
-        for (int l = 0; l < 64; ++l) {
-            next[l] = lane[l];
-            merge(next[l], lane[l ^ off]);
-        }
-        for (int l = 0; l < 64; ++l) lane[l] = next[l];
-    }
-    return lane[0];
+    return butterfly::block_sum(lane, 64, butterfly::ascending, merge);
 }
 
 }  // namespace
@@ -99,7 +76,7 @@ void play_act_shim_accumulate(const pp_play_act_inputs* in, const int64_t* done,
                 pp::act_group_clear(ga[l]);
                 n[l] = fin[l] ? pp::act_fold_env(env[l], num_envs, num_dofs, state, ga[l]) : 0;
             }
-            gpart[slot] = chunk_sum(ga, GroupOps());
+            gpart[slot] = butterfly::block_sum(ga, PPENV_PLAY_BLOCK, butterfly::ascending, GroupOps());     // the waves by the butterfly, strides 1 up to 32, then in order
             for (int32_t d = 0; d < num_dofs; ++d) {
                 pp_play_act_joint ja[PPENV_PLAY_BLOCK];
                 for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) {
@@ -111,7 +88,7 @@ void play_act_shim_accumulate(const pp_play_act_inputs* in, const int64_t* done,
                         pp::act_fold_zero(env[l], num_envs, num_dofs, d, state);
                     }
                 }
-                jpart[slot * num_dofs + d] = chunk_sum(ja, JointOps());
+                jpart[slot * num_dofs + d] = butterfly::block_sum(ja, PPENV_PLAY_BLOCK, butterfly::ascending, JointOps());
             }
         }
     }

@@ -2,6 +2,7 @@
 // the host, as play_shim.cpp does for the episode accounting.  TEST INFRASTRUCTURE ONLY.  Built by tests/play_pair_shim_binding.py with
 // -ffp-contract=off and WITHOUT -ffinite-math-only (the table starts as NaN).
 #include "../../isaacgym_amd/csrc/ppenv_play_pair_device.h"
+#include "butterfly_host.h"
 
 extern "C" {
 
@@ -24,26 +25,19 @@ void play_pair_shim_record(const float* rew, const int64_t* done, int32_t envs_p
 }
 
 // pp_play_pair_reduce on host memory, in play_pair_reduce_kernel's order: the PPENV_PLAY_BLOCK lanes' own sums, the xor butterfly of
-// every wave of 64 (stage by stage, each lane adding its partner's value of before the stage), the waves in order.
+// every wave of 64, strides 32 down to 1, the waves in order (butterfly_host.h).
 void play_pair_shim_reduce(int32_t envs_per_group, int32_t groups, int32_t num_agents, int32_t episodes, const int32_t* baseline,
                            const int32_t* count, const float* ret, const int32_t* len, pp_play_pair_totals* out) {
     for (int32_t g = 0; g < groups; ++g) {
         const int32_t b = baseline[g];
         const bool ok = pp::play_pair_baseline_ok(b, groups);
-        pp_play_pair_totals lane[PPENV_PLAY_BLOCK], next[PPENV_PLAY_BLOCK];
+        pp_play_pair_totals lane[PPENV_PLAY_BLOCK];
         for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) {
             pp::play_pair_clear(lane[l]);
             if (ok) pp::play_pair_lane(l, PPENV_PLAY_BLOCK, g, b, envs_per_group, num_agents, episodes, count, ret, len, lane[l]);
         }
-        for (int off = 32; off >= 1; off >>= 1) {
-            for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) {
-                next[l] = lane[l];
-                pp::play_pair_merge(next[l], lane[l ^ off]);
-            }
-            for (int l = 0; l < PPENV_PLAY_BLOCK; ++l) lane[l] = next[l];
-        }
-        pp_play_pair_totals s = lane[0];
-        for (int w = 1; w < PPENV_PLAY_BLOCK / 64; ++w) pp::play_pair_merge(s, lane[64 * w]);
+        pp_play_pair_totals s = butterfly::block_sum(lane, PPENV_PLAY_BLOCK, butterfly::descending,
+                                                     [](pp_play_pair_totals& into, const pp_play_pair_totals& from) { pp::play_pair_merge(into, from); });
         if (!ok) s.pairs = -1;
         out[g] = s;
     }

@@ -2,21 +2,16 @@
 // own summation order, as play_shim.cpp does for the play accounting.  TEST INFRASTRUCTURE ONLY.  Built by
 // tests/ppo_meter_shim_binding.py with -ffp-contract=off.
 #include "../../isaacgym_amd/csrc/ppenv_ppo_meter_device.h"
+#include "butterfly_host.h"
 
 namespace {
 
 constexpr int kBlock = PPENV_PPO_METER_BLOCK;
 
-// wave_merge of ppenv_ppo_meter.hip on 64 lanes' values: the xor butterfly, stage by stage; every lane ends with lane 0's bits.
-void butterfly(ppenv_ppo_meter_partial* v) {
-    for (int off = 32; off >= 1; off >>= 1) {
-        ppenv_ppo_meter_partial next[64];
-        for (int i = 0; i < 64; ++i) {
-            next[i] = v[i];
-            pp::meter_merge(next[i], v[i ^ off]);
-        }
-        for (int i = 0; i < 64; ++i) v[i] = next[i];
-    }
+// ppenv_ppo_meter.hip's order on an array of lanes: the xor butterfly of every wave, strides 32 down to 1, then the waves in order
+ppenv_ppo_meter_partial lanes_sum(ppenv_ppo_meter_partial* lane, int n) {
+    return butterfly::block_sum(lane, n, butterfly::descending,
+                                [](ppenv_ppo_meter_partial& into, const ppenv_ppo_meter_partial& from) { pp::meter_merge(into, from); });
 }
 
 }  // namespace
@@ -35,28 +30,22 @@ void ppo_meter_shim_update(const float* rew, int64_t ld_rew, const int64_t* done
         ppenv_ppo_meter_partial lanes[64];                     // meter_update_kernel's lanes: partials l, l + 64, ... in order
         for (int l = 0; l < 64; ++l) pp::meter_clear(lanes[l]);
         for (int32_t b = 0; b < parts; ++b) {                  // meter_rows_kernel's workgroup b at step t
-            ppenv_ppo_meter_partial part;
-            for (int w = 0; w < kBlock / 64; ++w) {
-                ppenv_ppo_meter_partial fin[64];
-                for (int l = 0; l < 64; ++l) {
-                    const int64_t e = (int64_t)b * kBlock + w * 64 + l;
-                    pp::meter_clear(fin[l]);
-                    if (e < num_envs) {
-                        const size_t col = (size_t)num_agents * (size_t)e;
-                        pp::meter_env_step(rew[(size_t)t * ld_rew + col], done[(size_t)t * ld_done + col], cur_reward[e], cur_len[e], fin[l]);
-                    }
+            ppenv_ppo_meter_partial fin[kBlock];
+            for (int l = 0; l < kBlock; ++l) {
+                const int64_t e = (int64_t)b * kBlock + l;
+                pp::meter_clear(fin[l]);
+                if (e < num_envs) {
+                    const size_t col = (size_t)num_agents * (size_t)e;
+                    pp::meter_env_step(rew[(size_t)t * ld_rew + col], done[(size_t)t * ld_done + col], cur_reward[e], cur_len[e], fin[l]);
                 }
-                butterfly(fin);
-                if (w == 0) part = fin[0];
-                else pp::meter_merge(part, fin[0]);
             }
-            pp::meter_merge(lanes[b % 64], part);
+            pp::meter_merge(lanes[b % 64], lanes_sum(fin, kBlock));
         }
-        butterfly(lanes);
-        if (step_sum) step_sum[t] = lanes[0].sum;
-        if (step_len) step_len[t] = lanes[0].len;
-        if (step_count) step_count[t] = lanes[0].count;
-        if (lanes[0].count != 0) pp::meter_apply(*meter, lanes[0], games_to_track);
+        const ppenv_ppo_meter_partial step = lanes_sum(lanes, 64);
+        if (step_sum) step_sum[t] = step.sum;
+        if (step_len) step_len[t] = step.len;
+        if (step_count) step_count[t] = step.count;
+        if (step.count != 0) pp::meter_apply(*meter, step, games_to_track);
     }
 }
 

@@ -13,7 +13,7 @@ from isaacgym_amd._lib import PLAY_ACT_FIELDS, PlayActGroup, PlayActInput, PlayA
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "play_act_shim.cpp")
-_HDRS = [os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_play_act_device.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h"),
+_HDRS = [os.path.join(_HERE, "csrc", "butterfly_host.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_play_act_device.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h"),
          os.path.join(_HERE, "..", "include", "ppenv_play_act.h"), os.path.join(_HERE, "..", "include", "ppenv_play_group.h"),
          os.path.join(_HERE, "..", "include", "ppenv_play.h")]
 _LIB = os.path.join(_HERE, "csrc", "libppenv_playactshim.so")

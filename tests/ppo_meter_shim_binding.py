@@ -11,7 +11,7 @@ from isaacgym_amd._lib import PPOMeter
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SRC = os.path.join(_HERE, "csrc", "ppo_meter_shim.cpp")
-_HDRS = [os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_ppo_meter_device.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h"),
+_HDRS = [os.path.join(_HERE, "csrc", "butterfly_host.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_ppo_meter_device.h"), os.path.join(_HERE, "..", "isaacgym_amd", "csrc", "ppenv_device.h"),
          os.path.join(_HERE, "..", "include", "ppenv_ppo_meter.h")]
 _LIB = os.path.join(_HERE, "csrc", "libppenv_ppometershim.so")
 _lib = None
