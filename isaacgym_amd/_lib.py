@@ -23,7 +23,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_play_delay.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -35,6 +35,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_play_pair_device.h"), os.path.join(ROOT, "include", "ppenv_play_pair.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_act_device.h"), os.path.join(ROOT, "include", "ppenv_play_act.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay_device.h"), os.path.join(ROOT, "include", "ppenv_play_delay.h"),
+           os.path.join(_PKG, "csrc", "ppenv_train_delay_device.h"), os.path.join(ROOT, "include", "ppenv_train_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -125,6 +126,11 @@ class PlayPairTotals(C.Structure):
 
 PLAY_ACT_MAX_DOF, PLAY_ACT_FIELDS = 32, 10                                               # PP_PLAY_ACT_MAX_DOF, PP_PLAY_ACT_FIELDS
 PLAY_DELAY_MAX, PLAY_DELAY_MAX_WIDTH = 15, 512                                           # PP_PLAY_DELAY_MAX, PP_PLAY_DELAY_MAX_WIDTH
+
+
+class TrainDelayConsts(C.Structure):
+    """ctypes mirror of pp_train_delay_consts (include/ppenv_train_delay.h)."""
+    _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("seed", C.c_uint64), ("env_id_offset", C.c_int32), ("channel", C.c_int32)]
 
 
 class PlayActLimit(C.Structure):
@@ -443,6 +449,12 @@ def load(path):
     L.pp_play_delay_ring_bytes.argtypes = [i32, i32, i32]
     L.pp_play_delay_reset.argtypes = [i32, vp, vp]
     L.pp_play_delay_push.argtypes = [vp, i64, vp, i32, i32, i32, i32, vp, vp, vp, vp, i64, vp]
+    # ---- include/ppenv_train_delay.h
+    L.pp_train_delay_ring_bytes.restype = L.pp_train_delay_table_bytes.restype = sz
+    L.pp_train_delay_ring_bytes.argtypes = [i32, i32, i32]
+    L.pp_train_delay_table_bytes.argtypes = [i32]
+    L.pp_train_delay_reset.argtypes = [i32, vp, vp, vp]
+    L.pp_train_delay_push.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(TrainDelayConsts), vp, vp, vp, vp, vp, i64, vp]
     # ---- include/ppenv_ppo_meter.h
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]

@@ -19,6 +19,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from .latency import COMMAND, SENSING, DelayLine, delay_range
 
 
 def gae(rewards, values, dones, gamma=0.99, tau=0.95, reward_scale=1.0, advantages=None, returns=None):
@@ -37,9 +38,22 @@ class RolloutCollector:
     """`collect()` plays `horizon` steps of env + policy and leaves the horizon in `obs [H+1, N, num_obs]`, `actions [H, N, A]`,
     `neglogp [H, N]`, `mu [H+1, N, A]`, `values [H+1, N]`, `rewards [H, N]`, `dones [H, N]`, `advantages`, `returns [H, N]`.
     `seed` goes to the sampling launch as given (policy.sample_actions): with the env's own seed the exploration draw of step t would be
-    the env's action noise of step t + 1 for the same row and action.  Pass policy.sampler_stream_seed(user seed), as PPOTrainer does."""
+    the env's action noise of step t + 1 for the same row and action.  Pass policy.sampler_stream_seed(user seed), as PPOTrainer does.
 
-    def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0):
+    action_delay, obs_delay: control latency in whole control steps, an int K or a (lo, hi) pair drawn anew per env at every episode start
+    (latency.DelayLine; include/ppenv_train_delay.h, keyed by `latency_seed` — a STREAM seed, scene.stream_seed(seed, STREAM_LATENCY) —
+    and `env_id_offset`).  The order is the Player's: obs_seen = obs_line.push(obs, done_prev), a = policy(obs_seen), a_applied =
+    act_line.push(a, done_prev), env.step(a_applied).  With a sensing line (`obs_line`) the env step writes `raw_obs` [N, num_obs] and the
+    line pushes it, with this step's dones, straight into obs[t + 1]; obs[0] of the first horizon is the initial observation pushed with no
+    done, and the bootstrap forward reads the delayed obs[H].  With a command line (`act_line`) actions[t] — the policy's own clamped
+    action, which the learner's ratio is evaluated on — is pushed into `applied` [N, A] with the done the previous env step returned
+    (dones[t - 1]; at t = 0 the previous horizon's dones[H - 1], still in the buffer; before any step none), and the env consumes
+    `applied`.  A path whose hi is 0 is not built — no allocation, no launch, the attribute is None — so the default collector is the
+    collector without the feature."""
+
+    def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0, action_delay=0, obs_delay=0,
+                 latency_seed=0, env_id_offset=0):
+        self.action_delay, self.obs_delay = delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay)
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
         n, dev, a = env.num_rows, env.device, net.num_actions        # actor rows: A * N for the 4-actor variant
@@ -53,7 +67,17 @@ class RolloutCollector:
         self.sigma = (torch.ones(a, device=dev) if sigma is None else sigma.to(dev, torch.float32)).contiguous()
         self.counter = 0
         self.on_step = None                   # called with no arguments right after every env.step of collect() (render.TrainingCapture.on_step)
-        self.obs[0].copy_(env.obs_buf)
+        self.act_line = self.obs_line = self.applied = self.raw_obs = None
+        self._done_prev = None                # the dones of the last env step (a row of `dones`); None before any step
+        line = lambda width, rng, channel: DelayLine(n, width, rng[0], rng[1], dev, env.num_agents, latency_seed, env_id_offset, channel)
+        if self.action_delay[1] > 0:
+            self.act_line, self.applied = line(a, self.action_delay, COMMAND), z(n, a)
+        if self.obs_delay[1] > 0:
+            self.obs_line, self.raw_obs = line(env.obs_buf.shape[1], self.obs_delay, SENSING), z(n, env.obs_buf.shape[1])
+            self.raw_obs.copy_(env.obs_buf)
+            self.obs_line.push(self.raw_obs, None, self.obs[0])
+        else:
+            self.obs[0].copy_(env.obs_buf)
 
     @torch.no_grad()
     def collect(self):
@@ -62,7 +86,13 @@ class RolloutCollector:
             self.counter += 1
             self.net.forward(self.obs[t], head_out=self.head[t],
                              sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
-            self.env.step(self.actions[t], obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
+            act = self.actions[t] if self.act_line is None else self.act_line.push(self.actions[t], self._done_prev, self.applied)
+            if self.obs_line is None:
+                self.env.step(act, obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
+            else:
+                self.env.step(act, obs=self.raw_obs, rew=self.rewards[t], reset=self.dones[t])
+                self.obs_line.push(self.raw_obs, self.dones[t], self.obs[t + 1])
+            self._done_prev = self.dones[t]
             if self.on_step is not None:
                 self.on_step()
         self.net.forward(self.obs[self.h], head_out=self.head[self.h])            # bootstrap value of the last observation

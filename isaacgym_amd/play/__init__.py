@@ -71,7 +71,10 @@ launch per push: from sample d of an episode on every output is exactly d contro
 (no artificial neutral command), and nothing is carried across a reset.  A line whose delays are all zero is not built, so the defaults are
 the player without the feature byte for byte.  The result gains `latency` = dict(control_dt, action_delay=[per cell], obs_delay=[per cell]).
 
-Out of scope: latency during training (the trainer and its collector are untouched), delays drawn per episode, action hold / policy decimation,
+Training under latency is the trainer's: PPOTrainer(action_delay=, obs_delay=) with isaacgym_amd.latency.DelayLine (include/ppenv_train_delay.h),
+fixed or drawn per episode, in this player's order — a fixed delay trains under exactly what the sweep axes above measure.
+
+Out of scope: delays drawn per episode in the player (fixed-delay sweeps evaluate a policy trained under them), action hold / policy decimation,
 per-cell observation or action noise, a VecTask-level latency setting; sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
 paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
@@ -82,6 +85,7 @@ from .._lib import MAX_AGENTS, PlayTotals     # PPENV_PLAY_MAX_AGENTS and the ct
 from .._lib import PlayPairTotals             # ... and of pp_play_pair_totals
 from .._lib import TA_OUTCOME_NAMES, TAOutcome
 from ..dr import TABLE_NAMES
+from ..latency import DelayLine               # the trainer's line (delays drawn per episode), beside the player's Delay
 from .accounting import ACT_THRESHOLDS, DELAY_MAX, DELAY_MAX_WIDTH, MAX_GROUPS, ActuatorStats, Delay, EpisodeStats, GroupStats, PairStats
 from .cli import actuator_option, main, make_recorder, make_renderer, parse_args
 from .player import Player, actuator_limits, control_dt_of

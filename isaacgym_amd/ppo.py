@@ -29,7 +29,13 @@ Deviations from rl_games:
   - The minibatches are the contiguous row ranges of the horizon-major buffers, in order.
 
 Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
-They also carry "meter" (the score meter's struct) and "last_mean_rewards" (the best score so far); load() accepts files without them.
+They also carry "meter" (the score meter's struct), "last_mean_rewards" (the best score so far) and "latency" (the two delay ranges the
+run trained under, {"action_delay": [lo, hi], "obs_delay": [lo, hi]}: a record — load() accepts files without any of them, and the
+trainer that loads keeps the delays it was built with).
+
+Control latency (PPOTrainer(action_delay=, obs_delay=), --action-delay / --obs-delay K | LO:HI): the rollout runs with a delay line on the
+command path and / or the sensing path, fixed or drawn per env at every episode start (RolloutCollector; include/ppenv_train_delay.h;
+DESIGN §5d "Training under latency").  Off by default, and then nothing is built.
 
 The score (GameMeter; C ABI: include/ppenv_ppo_meter.h) is rl_games' game_rewards / game_lengths: AverageMeter(games_to_track) over the
 finished games' unscaled returns (agent 0's row of each env) and lengths, updated once per epoch over the collector's horizon by two
@@ -63,10 +69,11 @@ import time
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, scene
 from . import distributed as D
 from ._lib import PPOAdam, PPOLossArgs, PPOMeter, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h and ppenv_ppo_meter.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
+from .latency import delay_range, latency_text
 from .policy import UNITS, NativeActorCritic, RunningMeanStd, sampler_stream_seed
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -403,9 +410,17 @@ class PPOTrainer:
     outcomes: the 27-dof task's five head-counts (task.enable_outcomes(); the other tasks raise ValueError) — train_epoch() then also returns
     outcome_windows, outcome_envs and the five outcome_<name> rates of the most recent window.  The step kernel's clear sums them into a struct
     of their own: parameters, moments, scaler, statistics and meter stay bitwise those of a run without.  Not checkpointed: the envs restart on
-    resume."""
+    resume.
+    action_delay, obs_delay: train under control latency — whole control steps, an int K (every env, always) or a (lo, hi) pair drawn anew
+    per env at every episode start (RolloutCollector; include/ppenv_train_delay.h — this build's own rule, the reference delays nothing).
+    The env consumes the command of that many steps ago and the policy sees — and the learner trains on — the observation of that many
+    steps ago; the stored actions are the policy's own.  The draws are keyed scene.stream_seed(seed, scene.STREAM_LATENCY) and the task's
+    env_id_offset, so ranks under seed + r share none.  Rewards, dones, GAE, the score meter, outcomes and capture are untouched; with both
+    delays 0 (the default) no line is built and the run is bitwise the run without the arguments.  A fixed delay K trains under exactly
+    what `python -m isaacgym_amd.play --sweep action_delay=...` measures.  Checkpoints carry the two ranges under "latency"; the lines'
+    state is not checkpointed (the envs restart on resume)."""
 
-    def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False):
+    def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
@@ -440,7 +455,9 @@ class PPOTrainer:
         self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
         H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
-                                    sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed))   # ranks under seed + r share no exploration noise, and none is the env's noise
+                                    sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
+                                    action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
+                                    env_id_offset=task._env_id_offset)
         self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
@@ -457,6 +474,7 @@ class PPOTrainer:
         self.meter = GameMeter(env.num_envs, n // env.num_envs, cfg.games_to_track, dev)     # rl_games' score: per rank, as in rl_games
         self.last_mean_rewards = NO_SCORE                                  # the score of the best checkpoint so far (fit)
         self.epoch, self.frame = 0, 0
+        self.loaded_latency = None                                         # load(): the "latency" of the checkpoint resumed from
         self.outcome = task.enable_outcomes() if outcomes else None         # pp_ta_outcome, int64 [16] (include/ppenv_ta_outcome.h)
         if self.multi:
             self._broadcast_start()
@@ -495,6 +513,10 @@ class PPOTrainer:
             return
         capture.start_step = self.epoch * self.cfg.horizon_length
         self.col.on_step = capture.on_step
+
+    def latency(self):
+        """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
+        return dict(control_dt=self.env.control_dt, action_delay=list(self.col.action_delay), obs_delay=list(self.col.obs_delay))
 
     # -- the steps of an epoch --
     def collect(self):
@@ -645,7 +667,8 @@ class PPOTrainer:
         stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms))
                  if rms is not None for k in ("mean", "inv_std")}
         return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
-                "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards)}
+                "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards),
+                "latency": {k: v for k, v in self.latency().items() if k != "control_dt"}}
 
     def save(self, path):
         """Data-parallel: rank 0 writes, the other ranks return (their parameters and optimizer state are rank 0's)."""
@@ -684,6 +707,7 @@ class PPOTrainer:
         if "meter" in ck:                                                    # checkpoints from before the score meter have neither
             self.meter.load_state_dict(ck["meter"])
         self.last_mean_rewards = float(ck.get("last_mean_rewards", NO_SCORE))
+        self.loaded_latency = ck.get("latency")                              # what the file's run trained under; None: a file from before the key
 
 
 # ---- the run loop -----------------------------------------------------------------------------------------------------------------
@@ -796,6 +820,9 @@ def main(argv=None):
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="nccl (RCCL) one GPU per rank; gloo: ranks may share a GPU")
     ap.add_argument("--force-dist", action="store_true", help="with --multi-gpu: accept a one-rank world and run the collectives anyway")
     ap.add_argument("--outcomes", action="store_true", help="27-dof task: report the reference's five outcome counts (TA:1164-1168) as rates of the envs per epoch")
+    ap.add_argument("--action-delay", default="0", metavar="K|LO:HI", help="train under control latency of the command path: the env consumes the action of K "
+                    "control steps ago (0..15), or of LO..HI steps ago, drawn per env at every episode start")
+    ap.add_argument("--obs-delay", default="0", metavar="K|LO:HI", help="... of the sensing path: the policy sees the observation of K (or LO..HI) control steps ago")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -812,6 +839,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.force_dist and not args.multi_gpu:
         ap.error("--force-dist belongs to --multi-gpu")
+    action_delay, obs_delay = delay_range("--action-delay", args.action_delay), delay_range("--obs-delay", args.obs_delay)
     rank, seed, dev = 0, args.seed, None
     if args.multi_gpu:
         rank, dev = init_rank(args.dist_backend, force=args.force_dist)
@@ -837,7 +865,9 @@ def main(argv=None):
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, multi_gpu=True, device=dev, cfg=task_cfg)
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
-    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes)
+    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay)
+    if rank == 0 and (action_delay[1] or obs_delay[1]):
+        print(latency_text(tr.latency()), flush=True)
     if args.checkpoint:
         tr.load(args.checkpoint)                                   # every rank: the same file
         if rank == 0:

@@ -1005,6 +1005,31 @@ def stream_seed(seed, family_salt):
     return _mix64((int(seed) ^ family_salt) & 0xFFFFFFFFFFFFFFFF)
 
 
+STREAM_LATENCY = 0x452821E638D01377                                                                      # the per-episode control-latency draws (include/ppenv_train_delay.h)
+
+
+def latency_draws(stream_seed, gids, episodes, channel, lo, hi):
+    """Host restatement of the training delay line's draw (include/ppenv_train_delay.h; pp::train_delay_draw) in numpy integer arithmetic:
+    the delay in lo .. hi of global env id `gids` in its episode number `episodes` (arrays, broadcast against each other) on `channel`
+    (0: the command path, 1: the sensing path) under the STREAM seed `stream_seed` (stream_seed(seed, STREAM_LATENCY)) -> int32 array.
+    Both rows of a 4-actor env share their env's draw.  lo == hi gives lo for every key."""
+    lo, hi, channel = int(lo), int(hi), int(channel)
+    if not 0 <= lo <= hi <= 15 or channel not in (0, 1):
+        raise ValueError(f"latency_draws: a range of whole control steps 0 <= lo <= hi <= 15 and channel 0 or 1, not lo {lo}, hi {hi}, channel {channel}")
+    u32, u64 = np.uint32, np.uint64
+    seed = int(stream_seed) & 0xFFFFFFFFFFFFFFFF
+
+    def hash32(x):                                              # (uint32 arrays wrap silently)
+        x = (x ^ (x >> u32(16))) * u32(0x7FEB352D)
+        x = (x ^ (x >> u32(15))) * u32(0x846CA68B)
+        return x ^ (x >> u32(16))
+    gid, n = np.broadcast_arrays(np.atleast_1d(np.asarray(gids, np.int64)).astype(u32), np.atleast_1d(np.asarray(episodes, np.int64)).astype(u32))
+    h = hash32(gid ^ u32(seed & 0xFFFFFFFF))
+    h = hash32(h + n * u32(0x9E3779B9) + u32(seed >> 32))
+    h = hash32(h + u32(((channel + 1) * 0x85EBCA6B) & 0xFFFFFFFF))
+    return (lo + (((h >> u32(8)).astype(u64) * u64(hi - lo + 1)) >> u64(24)).astype(np.int64)).astype(np.int32)
+
+
 def ta_reset_draws(params, env_ids, episodes):
     """Host restatement of the 27-DoF task's reset draws (ta_post_physics_kernel, TA:976-979 + 346-377): for each (env,
     episode) the five values ball y, ball z, vx, vy, vz.  Used to lay out the state at creation (episode 0); resets during
