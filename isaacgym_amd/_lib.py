@@ -23,7 +23,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ppo.hip"), os.path.join(_PKG, "csrc", "ppenv_dr.hip"), os.path.join(_PKG, "csrc", "ppenv_play.hip"),
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -36,16 +37,19 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_play_act_device.h"), os.path.join(ROOT, "include", "ppenv_play_act.h"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay_device.h"), os.path.join(ROOT, "include", "ppenv_play_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_train_delay_device.h"), os.path.join(ROOT, "include", "ppenv_train_delay.h"),
+           os.path.join(_PKG, "csrc", "ppenv_serve_curric_device.h"), os.path.join(ROOT, "include", "ppenv_serve_curric.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
 # the score meter's fp64 update rounds every operation on its own, as its host build does (no contraction, signed zeros, a nan mean stays one);
 # the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign;
 # the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN;
-# the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf
+# the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf;
+# the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_serve_curric.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
@@ -195,6 +199,23 @@ class ServePlan(C.Structure):
     """ctypes mirror of pp_serve_plan."""
     _fields_ = [("num_envs", C.c_int32), ("env_id_offset", C.c_int32), ("seed", C.c_uint64), ("form", C.c_int32), ("layout", C.c_int32),
                 ("reset_rows", C.c_int32), ("groups", C.c_int32), ("envs_per_group", C.c_int32), ("paired", C.c_int32), ("cells", C.c_void_p)]
+
+
+CURRIC_MAX_BINS, CURRIC_MAX_POWER, CURRIC_FOLD_CHUNK = 256, 4, 16384                     # PP_CURRIC_MAX_BINS, PP_CURRIC_MAX_POWER, PP_CURRIC_FOLD_CHUNK
+CURRIC_DROPPED = -2 ** 63                                                               # PP_CURRIC_DROPPED
+
+
+class ServeCurric(C.Structure):
+    """ctypes mirror of pp_serve_curric (include/ppenv_serve_curric.h)."""
+    _fields_ = [("num_envs", C.c_int32), ("env_id_offset", C.c_int32), ("seed", C.c_uint64), ("form", C.c_int32), ("layout", C.c_int32),
+                ("reset_rows", C.c_int32), ("num_agents", C.c_int32), ("bins", C.c_int32), ("power", C.c_int32), ("mix", C.c_float),
+                ("alpha", C.c_float), ("cells", C.c_void_p)]
+
+
+class ServeCurricState(C.Structure):
+    """ctypes mirror of pp_serve_curric_state: device pointers."""
+    _fields_ = [("count", C.c_void_p), ("next_bin", C.c_void_p), ("cur_bin", C.c_void_p), ("ret", C.c_void_p), ("games", C.c_void_p),
+                ("mean", C.c_void_p), ("dropped", C.c_void_p), ("cdf", C.c_void_p)]
 
 
 RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
@@ -476,6 +497,15 @@ def load(path):
     L.pp_serve_fill.argtypes = [vp, i32, vp, vp, vp]
     L.pp_serve_apply.argtypes = [vp, i32, vp, vp, vp, vp]
     L.pp_serve_apply_ids.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    # ---- include/ppenv_serve_curric.h
+    statep = C.POINTER(ServeCurricState)
+    L.pp_serve_curric_upload.argtypes = [C.POINTER(ServeCurric), C.POINTER(ServeCell), vp, vp, vp]
+    L.pp_serve_curric_fill.argtypes = [vp, i32, i32, statep, vp, vp]
+    L.pp_serve_curric_step.argtypes = [vp, i32, vp, vp, statep, vp, vp, vp, vp]
+    L.pp_serve_curric_fold_bytes.restype = sz
+    L.pp_serve_curric_fold_bytes.argtypes = [i64]
+    L.pp_serve_curric_fold.argtypes = [vp, vp, i64, i32, vp, vp, vp]
+    L.pp_serve_curric_update.argtypes = [vp, i32, vp, statep, vp]
     return L
 
 

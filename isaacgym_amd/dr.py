@@ -138,7 +138,34 @@ class NativeEnv:
     joint_limits()                  (float32 [num_dofs, 4]: lower, upper, effort, vel_limit; the joint names) of the model the step runs
     joint_views()                   (q, qd, tau) as [num_envs, num_dofs] float32 views of the env's own tensors, any strides
     step(actions), reset_all(), reset_idx(env_ids)
-    set_serve_plan, apply_serve_plan, clear_serve_plan, serve_defaults, serve_plan   (include/ppenv_serve.h)"""
+    set_serve_plan, apply_serve_plan, clear_serve_plan, serve_defaults, serve_plan   (include/ppenv_serve.h)
+    set_serve_curriculum, clear_serve_curriculum, serve_curriculum, serve_target()   (include/ppenv_serve_curric.h; a plan and a curriculum
+                                    write the same override buffer and cannot coexist)"""
+    serve_curriculum = None
+
+    def set_serve_curriculum(self, bins, power=1, mix=0.25, alpha=0.3, seed=None, horizon=32):
+        """An adaptive serve curriculum (include/ppenv_serve_curric.h; curriculum.ServeCurriculum has the arguments): from now on every reset
+        inside a step serves the ball the curriculum last drew for that env, and the caller launches curriculum.step(t, rew, reset) once after
+        every step, fold() and update() once per horizon.  Switches the override exactly as set_serve_plan does — for the 7-dof handles BY
+        VALUE in the step kernel's arguments: a graph captured before this call must be captured again.  With a serve plan set: ValueError.
+        -> the ServeCurriculum."""
+        if self.serve_plan is not None:
+            raise ValueError("a serve plan is set: a plan and a curriculum write the same override buffer; call clear_serve_plan() first")
+        from .curriculum import ServeCurriculum
+        cur = ServeCurriculum(self, bins, power=power, mix=mix, alpha=alpha, seed=seed, horizon=horizon)
+        self._serve_override_switch(True)
+        self.serve_curriculum = cur
+        return cur
+
+    def clear_serve_curriculum(self):
+        """The built-in serves again, as after clear_serve_plan."""
+        if self.serve_curriculum is not None:
+            self._serve_override_switch(False)
+            self.serve_curriculum = None
+
+    def _refuse_plan_beside_curriculum(self):
+        if self.serve_curriculum is not None:
+            raise ValueError("a serve curriculum is set: a plan and a curriculum write the same override buffer; call clear_serve_curriculum() first")
 
     def apply_serve_plan(self, env_ids=None):
         """The per-step launch (pp_serve_apply on reset_buf), once after every step while a plan is set; env_ids: the id variant, after

@@ -220,6 +220,15 @@ class PPEnv(NativeEnv, Randomizable):
         return {"serve_speed": (cfg.serve_speed_lo, cfg.serve_speed_hi), "serve_tilt": (cfg.serve_tilt_lo_deg, cfg.serve_tilt_hi_deg),
                 "serve_tilt_z": (cfg.serve_tilt_z_lo_deg, cfg.serve_tilt_z_hi_deg)}
 
+    def serve_target(self):
+        """What a serve plan or curriculum of this handle writes and how it keys its draws: serve_override [3][N], the variant's form."""
+        cfg = self._config_of()
+        return dict(axes=serve.AXES_7DOF, out=self.serve_override, form=cfg.variant, layout=_lib.SERVE_LAYOUT_SOA3, reset_rows=self.num_agents,
+                    seed=scene.stream_seed(cfg.seed, scene.STREAM_SERVES), env_id_offset=cfg.env_id_offset)
+
+    def _serve_override_switch(self, on):
+        _lib.check(self.L.ppenv_set_serve_override(self.h, None, int(bool(on)), _lib.stream(self.device)), self.L)
+
     def set_serve_plan(self, cells, paired=False, seed=None):
         """A serve plan (include/ppenv_serve.h; serve.ServePlan): the envs are split into len(cells) equal groups, and from now on every reset
         of an env of group g — in a step, reset_all or reset_idx — serves the ball its cell describes instead of the built-in draw.  A cell is
@@ -229,6 +238,7 @@ class PPEnv(NativeEnv, Randomizable):
         The plan fills ppenv_buffers.serve_override with every env's serve 0 and switches the override on; the caller then launches
         apply_serve_plan() once after every step.  The switch travels BY VALUE in the step kernel's arguments: a graph captured before this
         call does not see it and must be captured again (one captured after it may hold step + apply_serve_plan).  -> the ServePlan (out, count, cells)."""
+        self._refuse_plan_beside_curriculum()
         cfg = self._config_of()
         seed = scene.stream_seed(cfg.seed, scene.STREAM_SERVES) if seed is None else seed
         plan = serve.ServePlan(self.L, self.device, self.num_envs, cells, self.serve_defaults(), serve.AXES_7DOF, self.serve_override, form=cfg.variant,

@@ -62,6 +62,7 @@ Only rank 0 writes checkpoints; load() on every rank reads the same file, so the
 import argparse
 import ctypes as C
 import dataclasses
+import json
 import math
 import os
 import time
@@ -418,15 +419,32 @@ class PPOTrainer:
     env_id_offset, so ranks under seed + r share none.  Rewards, dones, GAE, the score meter, outcomes and capture are untouched; with both
     delays 0 (the default) no line is built and the run is bitwise the run without the arguments.  A fixed delay K trains under exactly
     what `python -m isaacgym_amd.play --sweep action_delay=...` measures.  Checkpoints carry the two ranges under "latency"; the lines'
-    state is not checkpointed (the envs restart on resume)."""
+    state is not checkpointed (the envs restart on resume).
+    serve_plan, serve_paired: train on a serve plan (include/ppenv_serve.h) — cells of serve ranges over equal env groups, as
+    env.set_serve_plan takes them — keyed scene.stream_seed(seed, scene.STREAM_SERVES) and the task's env_id_offset, so ranks under seed + r
+    share no serves.  The collector runs the plan's launch after every env step.  A task that arrives with a plan set (task.set_serve_plan)
+    is refused, as before: that plan is keyed by the task's seed, not the trainer's; clear it and pass its cells here.  One cell of pinned values trains on exactly what `python -m isaacgym_amd.play --sweep serve_speed=...` measures.
+    curriculum: dict(bins=..., power=1, mix=0.25, alpha=0.3) — an adaptive serve curriculum kept on the device (include/
+    ppenv_serve_curric.h — this build's own rule, the reference has none): `bins` are cell dicts (curriculum.grid(...)); every finished
+    game's return (agent 0's, unscaled) is credited to the bin its ball was drawn from, and every env's next serve is drawn from a table
+    that favours the bins with the lowest mean return.  One launch per control step, a fold and an update per epoch, no host read;
+    data-parallel, the horizon's per-bin totals are summed over the ranks (one int64 all-reduce of 3 B words), so every rank holds the same
+    table.  train_epoch() then also returns curriculum_games, curriculum_mean and curriculum_prob, [B] device tensors.  power=0 or mix=1
+    keeps the statistics over uniform bins: the control run.  Checkpoints carry the plan's cells under "serve" and the curriculum's bins,
+    parameters and table under "curriculum"; load() restores the table and raises ValueError on other bins.  Per-env state is not
+    checkpointed.  A plan together with a curriculum is a ValueError; with neither, nothing is allocated or launched and the run is
+    bitwise the run without the arguments.  clear_serve() gives the built-in serves back."""
 
-    def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0):
+    def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
+                 curriculum=None):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
         if task._serve_plan is not None:
             raise ValueError("a task with a serve plan set is not supported by PPOTrainer: the collector drives the env below VecTask.step, so the plan's "
-                             "per-step launch would not run; call task.clear_serve_plan() first")
+                             "per-step launch would not run; call task.clear_serve_plan() first and pass the cells as serve_plan=")
+        if curriculum is not None and serve_plan is not None:
+            raise ValueError("serve_plan together with curriculum: a plan and a curriculum write the same serve override buffer")
         self.task, self.env = task, task.env
         env = self.env
         self.device = dev = torch.device(env.device)
@@ -454,10 +472,16 @@ class PPOTrainer:
         self.value_rms = RunningMeanStd(1, dev) if cfg.normalize_value else None
         self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
         H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
+        self.curriculum = None
+        serve_seed = scene.stream_seed(self.seed, scene.STREAM_SERVES)
+        if serve_plan is not None:
+            task._serve_plan = env.set_serve_plan(serve_plan, paired=serve_paired, seed=serve_seed)
+        elif curriculum is not None:
+            self.curriculum = env.set_serve_curriculum(**dict(curriculum), seed=serve_seed, horizon=H)
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
                                     sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
                                     action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
-                                    env_id_offset=task._env_id_offset)
+                                    env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan)
         self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
@@ -513,6 +537,29 @@ class PPOTrainer:
             return
         capture.start_step = self.epoch * self.cfg.horizon_length
         self.col.on_step = capture.on_step
+
+    def serve(self):
+        """The serve plan's resolved cells and pairing, or None without a plan."""
+        plan = self.task._serve_plan
+        return None if plan is None else dict(cells=[{k: [float(v[0]), float(v[1])] for k, v in c.items()} for c in plan.cells], paired=plan.paired)
+
+    def clear_serve(self):
+        """The built-in serves again: the plan or the curriculum is dropped and the collector launches nothing for it any more."""
+        self.col.serve = None
+        self.task.clear_serve_plan()
+        self.env.clear_serve_curriculum()
+        self.curriculum = None
+
+    @torch.no_grad()
+    def _curriculum_epoch(self):
+        """The collected horizon into the curriculum: fold, the ranks' totals summed, update.  -> the epoch's three [B] tensors."""
+        cur = self.curriculum
+        tot = cur.fold()
+        if self.multi:
+            torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
+        cur.update(tot)
+        t = cur.table()
+        return dict(curriculum_games=t["games"].clone(), curriculum_mean=t["mean"].clone(), curriculum_prob=t["prob"])
 
     def latency(self):
         """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
@@ -628,6 +675,7 @@ class PPOTrainer:
         skipped0 = self.opt.fields()["skipped"].clone()
         self.net.train()
         self.collect()
+        curric = self._curriculum_epoch() if self.curriculum is not None else None
         self.meter.update(self.col.rewards, self.col.dones)
         score = self.meter.snapshot()
         ep = self._episodes()
@@ -654,6 +702,8 @@ class PPOTrainer:
         out.update(meter_return=score["mean_reward"], meter_length=score["mean_length"], meter_games=score["current_size"])
         if self.outcome is not None:
             out.update(self._outcomes())
+        if curric is not None:
+            out.update(curric)
         return out
 
     # -- checkpoints --
@@ -666,9 +716,14 @@ class PPOTrainer:
         # statistics in torch and can differ in the last bit): a resumed run normalises exactly as the uninterrupted one
         stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms))
                  if rms is not None for k in ("mean", "inv_std")}
-        return {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
-                "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards),
-                "latency": {k: v for k, v in self.latency().items() if k != "control_dt"}}
+        sd = {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
+              "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards),
+              "latency": {k: v for k, v in self.latency().items() if k != "control_dt"}}
+        if self.task._serve_plan is not None:
+            sd["serve"] = self.serve()
+        if self.curriculum is not None:
+            sd["curriculum"] = self.curriculum.state_dict()
+        return sd
 
     def save(self, path):
         """Data-parallel: rank 0 writes, the other ranks return (their parameters and optimizer state are rank 0's)."""
@@ -681,6 +736,8 @@ class PPOTrainer:
         """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame.
         Data-parallel: every rank loads the same file (rank 0's), so all resume identical, each with rank 0's input and value statistics."""
         ck = torch.load(path, map_location=self.device, weights_only=True)
+        if self.curriculum is not None and "curriculum" in ck:               # first: other bins raise before anything is overwritten.  A file without one: the table starts fresh
+            self.curriculum.load_state_dict(ck["curriculum"])
         sd, lr = ck["model"], self.learner
         from .policy import layers_from_rlgames_state_dict
         actor, critic = layers_from_rlgames_state_dict(sd)
@@ -710,8 +767,9 @@ class PPOTrainer:
         self.loaded_latency = ck.get("latency")                              # what the file's run trained under; None: a file from before the key
 
 
+
 # ---- the run loop -----------------------------------------------------------------------------------------------------------------
-def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
+def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, curriculum_every=0, curriculum_out=None):
     """rl_games' train loop around train_epoch(), restated from its published a2c_common.train (rl_games is absent offline: parity
     unpinned).  Runs until trainer.epoch reaches max_epochs (default cfg.max_epochs: the TOTAL, so a resumed trainer continues its
     numbering) or the score wins.  After every epoch, with ONE host read (here, not in train_epoch):
@@ -725,7 +783,9 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
     -> dict(epochs: run by this call, epoch: the trainer's, stopped, reason: "max_epochs" | "score_to_win", best_score: last_mean_rewards
     (NO_SCORE while there is no best), paths: dict(latest, best, won: None where not written by this call), written: every path in order).
     capture: a render.TrainingCapture (trainer.set_capture is called with it): polled after every epoch's host read, closed before
-    returning; the result then has `videos`, the files it wrote."""
+    returning; the result then has `videos`, the files it wrote.
+    curriculum_every: with a serve curriculum, rank 0 prints its table every so many epochs and at the end (0: never) — a second host read in
+    those epochs — and rewrites curriculum_out (a json path) with it."""
     cfg = trainer.cfg
     if capture is not None:
         trainer.set_capture(capture)
@@ -744,7 +804,7 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
         res = trainer.train_epoch()
         ran += 1
         epoch = trainer.epoch
-        keys = list(res)
+        keys = [k for k in res if res[k].dim() == 0]                        # the curriculum's [B] tensors are read when its table is printed
         vals = dict(zip(keys, torch.stack([res[k].detach().double() for k in keys]).tolist()))     # the epoch's only host read
         if capture is not None:
             capture.poll()
@@ -767,6 +827,14 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None):
                    f" ({vals['outcome_windows']:.0f} windows)" if "outcome_windows" in vals else ""), flush=True)
             if stopped:
                 print(f"score {score} above score_to_win {cfg.score_to_win}: stopping", flush=True)
+        if curriculum_every and trainer.curriculum is not None and (epoch % curriculum_every == 0 or last) and trainer.rank == 0:
+            from .curriculum import table_json, table_lines
+            rows = table_json(trainer.curriculum, epoch)
+            print("\n".join(table_lines(rows)), flush=True)
+            if curriculum_out:
+                os.makedirs(os.path.dirname(os.path.abspath(curriculum_out)), exist_ok=True)
+                with open(curriculum_out, "w") as fh:
+                    json.dump(rows, fh, indent=1)
     out = dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
                best_score=trainer.last_mean_rewards, paths=paths, written=written)
     if capture is not None:
@@ -802,6 +870,21 @@ def init_rank(backend="nccl", force=False):
     return rank, dev
 
 
+def serve_cell_parse(flags):
+    """--serve AXIS=V / AXIS=LO:HI flags -> [one cell dict] for PPOTrainer(serve_plan=), or None without flags.  The values stay text:
+    serve.value_range and serve.resolve_cells judge them, with their own error texts, when the plan is set."""
+    if not flags:
+        return None
+    cell = {}
+    for flag in flags:
+        axis, sep, v = str(flag).partition("=")
+        if not sep:
+            raise ValueError(f"--serve {flag!r}: expected AXIS=V or AXIS=LO:HI")
+        parts = v.split(":")
+        cell[axis.strip()] = parts[0] if len(parts) == 1 else tuple(parts)
+    return [cell]
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m isaacgym_amd.ppo", description="PPO (rl_games a2c_continuous) on the native env and network")
     ap.add_argument("--task", default="HumanoidPingpongTiltNESSparse27DOFG1")
@@ -823,6 +906,15 @@ def main(argv=None):
     ap.add_argument("--action-delay", default="0", metavar="K|LO:HI", help="train under control latency of the command path: the env consumes the action of K "
                     "control steps ago (0..15), or of LO..HI steps ago, drawn per env at every episode start")
     ap.add_argument("--obs-delay", default="0", metavar="K|LO:HI", help="... of the sensing path: the policy sees the observation of K (or LO..HI) control steps ago")
+    ap.add_argument("--serve", action="append", default=[], metavar="AXIS=V|AXIS=LO:HI", help="train on a serve plan: pin a serve axis (serve_speed, serve_tilt, "
+                    "serve_tilt_z; the 27-dof task also ball_y, ball_z) or give its range; repeatable, all flags together are one cell over all envs")
+    ap.add_argument("--curriculum", action="append", default=[], metavar="AXIS=LO:HI:BINS", help="an adaptive serve curriculum: cut the axis into BINS equal "
+                    "bins; repeatable, the product of the axes are the bins (at most 256)")
+    ap.add_argument("--curriculum-power", type=int, default=1, help="a bin's weight is (1 / its rank by mean return) to this power, 0 .. 4 (0: uniform bins)")
+    ap.add_argument("--curriculum-mix", type=float, default=0.25, help="the share of the draws spread evenly over the bins, 0 .. 1")
+    ap.add_argument("--curriculum-alpha", type=float, default=0.3, help="the weight of an epoch's mean return in a bin's running mean, (0, 1]")
+    ap.add_argument("--curriculum-every", type=int, default=0, help="print the curriculum's table every so many epochs (0: never)")
+    ap.add_argument("--curriculum-out", default=None, help="a json file rewritten with the table at each print")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -840,6 +932,17 @@ def main(argv=None):
     if args.force_dist and not args.multi_gpu:
         ap.error("--force-dist belongs to --multi-gpu")
     action_delay, obs_delay = delay_range("--action-delay", args.action_delay), delay_range("--obs-delay", args.obs_delay)
+    try:
+        serve_plan, curriculum = serve_cell_parse(args.serve), None
+        if args.curriculum:
+            if serve_plan is not None:
+                raise ValueError("--serve together with --curriculum: a plan and a curriculum write the same serve override buffer")
+            from . import curriculum as curriculum_mod
+            curriculum_mod.check_parameters(args.curriculum_power, args.curriculum_mix, args.curriculum_alpha)
+            curriculum = dict(bins=curriculum_mod.grid(curriculum_mod.grid_parse(args.curriculum)), power=args.curriculum_power, mix=args.curriculum_mix,
+                              alpha=args.curriculum_alpha)
+    except ValueError as e:
+        ap.error(str(e))
     rank, seed, dev = 0, args.seed, None
     if args.multi_gpu:
         rank, dev = init_rank(args.dist_backend, force=args.force_dist)
@@ -865,7 +968,12 @@ def main(argv=None):
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, multi_gpu=True, device=dev, cfg=task_cfg)
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
-    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay)
+    tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay,
+                    serve_plan=serve_plan, curriculum=curriculum)
+    if rank == 0 and serve_plan is not None:
+        print("serve plan: " + ", ".join(f"{k} {v[0]:g}..{v[1]:g}" for k, v in tr.serve()["cells"][0].items()), flush=True)
+    if rank == 0 and curriculum is not None:
+        print(f"serve curriculum: {tr.curriculum.bins} bins, power {tr.curriculum.power}, mix {tr.curriculum.mix:g}, alpha {tr.curriculum.alpha:g}", flush=True)
     if rank == 0 and (action_delay[1] or obs_delay[1]):
         print(latency_text(tr.latency()), flush=True)
     if args.checkpoint:
@@ -879,7 +987,7 @@ def main(argv=None):
         renderer = play.make_renderer(task, args)
         capture = render.TrainingCapture(renderer, os.path.join(out, "videos"), freq=args.capture_video_freq or 1464, length=args.capture_video_len or 100,
                                          every=args.capture_every, fps=args.capture_fps, deferred=args.capture_deferred, trajectories=args.capture_trajectories)
-    done = fit(tr, out, args.task, print_every=args.print_every, capture=capture)
+    done = fit(tr, out, args.task, print_every=args.print_every, capture=capture, curriculum_every=args.curriculum_every, curriculum_out=args.curriculum_out)
     if rank == 0:
         for path in done.get("videos", []):
             print(f"saved {path} (video)", flush=True)

@@ -89,6 +89,10 @@ class ServePlan:
         _lib.check(self.L.pp_serve_apply(self.plan_dev.data_ptr(), self.num_envs, reset_buf.data_ptr(), self.out.data_ptr(), self.count.data_ptr(),
                                          _lib.stream(self.device)), self.L)
 
+    def step(self, t, rew_t, reset_t):
+        """What RolloutCollector calls after the env step of row t of a horizon (its `serve` object): apply(reset_t)."""
+        self.apply(reset_t)
+
     def apply_ids(self, env_ids):
         """The same for the envs reset_idx(env_ids) lists (pp_serve_apply_ids); duplicates are dropped here (the kernel wants distinct ids)."""
         ids = torch.unique(torch.as_tensor(env_ids, dtype=torch.int64).reshape(-1).to(self.device))

@@ -270,7 +270,8 @@ class TAEnv(NativeEnv):
         obs_buf / rew_buf / reset_buf — a rollout collector passes its horizon-major slices, so nothing is copied afterwards."""
         if actions.dtype != torch.float32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
-        ov = self.serve_plan.out if self.serve_plan is not None else None      # [N,5]: what an env that resets in this step is served
+        src = self.serve_plan if self.serve_plan is not None else self.serve_curriculum
+        ov = src.out if src is not None else None                              # [N,5]: what an env that resets in this step is served
         if self.fused:
             self.sim.step(self.state, actions, self.initial_rb_states, self.root_states, self.dof_states,
                           self._rb_states if self.materialize_rb else None, self.dof_force_tensor, self.pre_ball_vx,
@@ -368,12 +369,23 @@ class TAEnv(NativeEnv):
         return {"serve_speed": (p.serve_speed_lo, p.serve_speed_hi), "serve_tilt": (p.serve_tilt_lo_deg, p.serve_tilt_hi_deg),
                 "serve_tilt_z": (p.serve_tilt_z_lo_deg, p.serve_tilt_z_hi_deg), "ball_y": (p.ball_y_lo, p.ball_y_hi), "ball_z": (p.ball_z_lo, p.ball_z_hi)}
 
+    def serve_target(self):
+        """What a serve plan or curriculum of this task writes and how it keys its draws: a [N,5] buffer of its own (out None: the caller
+        allocates it), which `step` hands to the kernel as reset_override; the TN form."""
+        p = self.params
+        return dict(axes=serve.AXES_27DOF, out=None, form=scene.VARIANT_TN, layout=_lib.SERVE_LAYOUT_AOS5, reset_rows=1,
+                    seed=scene.stream_seed(p.seed, scene.STREAM_SERVES), env_id_offset=p.env_id_offset)
+
+    def _serve_override_switch(self, on):
+        """Nothing to switch: the override is a pointer argument of every launch, which `step` picks."""
+
     def set_serve_plan(self, cells, paired=False, seed=None):
         """A serve plan (include/ppenv_serve.h; PPEnv.set_serve_plan has the contract): a cell is a dict of any of serve_speed, serve_tilt,
         serve_tilt_z, ball_y, ball_z, each a number (pinned) or (lo, hi); what it does not name is the task's range (`params`).  While it
         is set, `step` hands the plan's [N,5] buffer (ball y, z, v_x, v_y, v_z) to the kernel as its reset_override — a pointer argument of
         every launch — and reset_idx takes the listed envs' rows from it; apply_serve_plan() follows every step.  seed: a STREAM seed,
         default scene.stream_seed(the task's seed, scene.STREAM_SERVES).  -> the ServePlan (out, count, cells)."""
+        self._refuse_plan_beside_curriculum()
         p, defaults = self.params, self.serve_defaults()
         seed = scene.stream_seed(p.seed, scene.STREAM_SERVES) if seed is None else seed
         out = torch.zeros((self.num_envs, 5), dtype=torch.float32, device=self.device)
@@ -388,6 +400,8 @@ class TAEnv(NativeEnv):
     def reset_idx(self, env_ids=None):
         """_reset_idx (TA:965-1028) outside a step, for the listed env ids (None: all).  A rare host-driven path: plain torch
         indexing on the task's own tensors with the draws of each env's next episode (the same keyed draws the kernel uses)."""
+        if self.serve_curriculum is not None:
+            raise _lib.PPEnvError("reset_idx while a serve curriculum is set: the curriculum supports resets inside collector steps only")
         n = self.num_envs
         ids = torch.arange(n) if env_ids is None else torch.as_tensor(env_ids, dtype=torch.int64).reshape(-1).cpu()
         if ids.numel() == 0:

@@ -138,6 +138,7 @@ class VecTask:
         """One control step: K1..K8 in a single kernel launch (TT:1002-1052).  controlFrequencyInv = k (upstream: pre_physics_step
         once, k simulate calls, post_physics_step once) is folded into the native config at create time — k * substeps physics
         substeps of the same length ahead of one reward / reset / observation pass — so it is still one launch."""
+        self._refuse_under_curriculum("step")
         if self.randomize:                   # upstream applies them from _reset_idx (TT:849-850); here once per step, gated by `frequency`
             self.apply_randomizations(self.randomization_params)
         self.env.step(actions)              # action clamp (clipActions) happens inside the kernel
@@ -250,11 +251,19 @@ class VecTask:
         serve, progress 0 and the initial flags; every other env keeps its trajectory.  `env_ids` as the reference passes them:
         an int64 tensor of env indices (`reset_buf.nonzero()`, TT:1034).  None resets every env (VecTask.reset_idx() of a fresh
         task).  For the two-agent task an id is an ENV index (both agent rows of that env reset together, T4:853-912)."""
+        self._refuse_under_curriculum("reset_idx")
         if env_ids is None:
             self.env.reset_all()
         else:
             self.env.reset_idx(env_ids)
         self._reset_idx_randomization(env_ids)
+
+    def _refuse_under_curriculum(self, what):
+        """A serve curriculum credits every finished game to its ball's bin from the rewards and dones of a collector step: a reset or a
+        step from this surface would consume a serve it never hears of."""
+        if self.env.serve_curriculum is not None:
+            raise RuntimeError(f"{type(self).__name__}.{what}() while a serve curriculum is set: the curriculum supports resets inside collector steps only "
+                               "(RolloutCollector(serve=...)); call env.clear_serve_curriculum() first")
 
     def set_serve_plan(self, cells, paired=False):
         """A serve plan on the task's environment (PPEnv.set_serve_plan / TAEnv.set_serve_plan: one cell of serve ranges per equal group of
