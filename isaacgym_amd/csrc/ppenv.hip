@@ -320,7 +320,10 @@ struct MovingGeom {
 // the ball wave is the critical path (35k cycles against the arm waves' 21k), so each arm wave's start-of-substep sweep is the
 // world-space one and hands its geometry to the ball wave through two alternating LDS slots; the ball wave is left with the
 // contacts.  (Tried and dropped, DESIGN.md §5 / §6: <1, 1>, <2, 0>, and separate geometry waves — five waves on four SIMDs slow
-// each other more than the hand-off saves.)
+// each other more than the hand-off saves.  <1, 1> again on top of the packed pairs, and a hybrid in which the ball wave sweeps boundary 0
+// and the arm wave the later ones through one LDS slot: the world-space sweep and its LDS writes cost the arm wave 1.9k cycles per
+// boundary and save the ball wave 1.0k, and the arm wave, whose final sweep, serve draw and paddle hand-off take 3k cycles after its
+// last substep, has no such slack — the task tail starts 2k cycles later and the step takes 11.58 against 11.27 us)
 // BW = ball waves per 64 envs: always 1.  (Narrower ball waves, 2 or 4 per 64 envs, were measured in round 3 and removed: DESIGN.md §9.
 // The parameter stays so that the kernel's name, which profiles and bench.py key on, does not change; the ball wave's env offsets below
 // are written for BW waves because folding them away changes the generated code.)
@@ -549,6 +552,7 @@ __global__ __launch_bounds__((A + BW) * kBlock) void step_kernel_split(const Ste
     }
 #pragma unroll
     for (int a = 0; a < A; a++) PP_AWAIT(&s_flag[a], substeps + 1);   // final dof state, drive torques and paddle position
+    PP_STAMP_AT(11);
     if (bactive) {
         BodyState bodies[A * NB];   // the task part reads the pelvis (row 0) and the paddle (row 9) only
         LdsRowStore stores[A];

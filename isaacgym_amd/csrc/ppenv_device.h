@@ -413,8 +413,8 @@ PP_HD void fk_sweep(const ArmSite& S, const float* q, const float* qd, JointSave
         V3 r = ld3(J.origin_xyz);
         V3 pw = pp + mul(Rp, r);
         M3 Rw = mul(Rp, E);
-        V3 w = tmul(E, wp);
-        V3 v = tmul(E, vp + cross(wp, r));
+        V3p wv = tmul(E, pk(wp, vp + cross(wp, r)));   // the angular and the linear half take the same rotation
+        V3 w = lo(wv), v = hi(wv);
         if (T::axis(i) == 0) w.x += qd[i]; else if (T::axis(i) == 1) w.y += qd[i]; else w.z += qd[i];
         js[i].c = c; js[i].s = s; js[i].w = w; js[i].v = v;
         vis(i, Rw, pw, w, v);
@@ -428,22 +428,30 @@ struct GeomVisitor {
     ArmGeom<T::kShapes>& g;
     PP_HD explicit GeomVisitor(ArmGeom<T::kShapes>& gg) : g(gg) {}
     PP_HD void operator()(int i, const M3& Rw, V3 pw, V3 w, V3 v) {
-        const V3 ww = mul(Rw, w), vw = mul(Rw, v);   // link angular / origin velocity in world axes
+        bool used = i == ND - 1;
+#pragma unroll
+        for (int s = 0; s < T::kShapes; s++) used = used || T::shape_link(s) == i;
+        if (!used) return;
+        const V3p wv = mul(Rw, pk(w, v));            // link angular / origin velocity in world axes
+        const V3 ww = lo(wv), vw = hi(wv);
         if (i == ND - 1) {   // paddle_link is validated to be the last link at create time
             const ModelPaddle P = T::paddle();
-            V3 off = mul(Rw, ld3(P.center));
+            const V3p on = mul(Rw, pk(ld3(P.center), ld3(P.normal)));   // (offset of the centre, normal)
+            const V3 off = lo(on);
+            const V3p x = cross(ww, on);                                // (omega x offset, omega x normal)
             g.pc = pw + off;
-            g.vpc = vw + cross(ww, off);
-            g.pn = mul(Rw, ld3(P.normal));
-            g.pnd = cross(ww, g.pn);
+            g.vpc = vw + lo(x);
+            g.pn = hi(on);
+            g.pnd = hi(x);
         }
 #pragma unroll
         for (int s = 0; s < T::kShapes; s++)
             if (T::shape_link(s) == i) {
                 const ModelShape sh = T::shape(s);
-                V3 oa = mul(Rw, ld3(sh.a)), ob = mul(Rw, ld3(sh.b));
-                g.a[s] = pw + oa; g.va[s] = vw + cross(ww, oa);
-                g.b[s] = pw + ob; g.vb[s] = vw + cross(ww, ob);
+                const V3p o = mul(Rw, pk(ld3(sh.a), ld3(sh.b)));        // both ends of the capsule
+                const V3p x = cross(ww, o);
+                g.a[s] = pw + lo(o); g.va[s] = vw + lo(x);
+                g.b[s] = pw + hi(o); g.vb[s] = vw + hi(x);
             }
     }
 };
@@ -466,17 +474,20 @@ struct BodyVisitor {
     PP_HD void operator()(int i, const M3& Rw, V3 pw, V3 w, V3 v) {
         GeomVisitor<T> gv(g);
         gv(i, Rw, pw, w, v);
-        V3 ww = mul(Rw, w), vw = mul(Rw, v);
+        const V3p wv = mul(Rw, pk(w, v));
+        const V3 ww = lo(wv), vw = hi(wv);
         bodies[1 + i].pos = pw; bodies[1 + i].lin = vw;
         if (FULL) { bodies[1 + i].rot = Rw; bodies[1 + i].ang = ww; }
         if (i == ND - 1) {
-#pragma unroll
-            for (int j = 8; j < NB; j++) {
-                const JointKin f = T::tip_frame(j);
-                V3 off = mul(Rw, ld3(f.origin_xyz));
-                bodies[j].pos = pw + off;
-                bodies[j].lin = vw + cross(ww, off);
-                if (FULL) { bodies[j].rot = mul(Rw, ldm(f.origin_rot)); bodies[j].ang = ww; }
+            static_assert(NB == 10, "the two bodies that ride on the last link are handled as a pair");
+            const JointKin f8 = T::tip_frame(8), f9 = T::tip_frame(9);
+            const V3p off = mul(Rw, pk(ld3(f8.origin_xyz), ld3(f9.origin_xyz)));
+            const V3p x = cross(ww, off);
+            bodies[8].pos = pw + lo(off); bodies[8].lin = vw + lo(x);
+            bodies[9].pos = pw + hi(off); bodies[9].lin = vw + hi(x);
+            if (FULL) {
+                bodies[8].rot = mul(Rw, ldm(f8.origin_rot)); bodies[8].ang = ww;
+                bodies[9].rot = mul(Rw, ldm(f9.origin_rot)); bodies[9].ang = ww;
             }
         }
     }
@@ -487,12 +498,34 @@ PP_HD void static_body(const ArmSite& S, BodyState& b) {   // obs_body[0]: the p
     if (FULL) { b.rot = ldm(S.root_rot); b.ang = mk(0, 0, 0); }
 }
 
+// Rigid-body inertia of a link about its origin, [[Io, m c x],[m c x^T, m 1]]: mass m, first moment mc = m c, rotational block A = Io.
+// msc: rigid_body_properties.mass scaling (DR), mass and inertia together.  Without the tables every operand is a literal and the compiler
+// folds the whole block, rounding operation by operation; with them (DR) the same expressions run on the device, and contracted into FMAs
+// they would round differently — unit tables would not reproduce the table-free kernel's inertias.  So nothing here is contracted.
+template <bool DR>
+PP_HD void link_inertia(const JointInertial& J, float msc, float& m, V3& mc, S3& A) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    m = DR ? J.mass * msc : J.mass;
+    V3 cm = ld3(J.com);
+    mc = cm * m;
+    float cc = dot(cm, cm);
+    float Jin[6];
+#pragma unroll
+    for (int t = 0; t < 6; t++) Jin[t] = DR ? J.inertia[t] * msc : J.inertia[t];
+    S3 a = {Jin[0] + m * (cc - cm.x * cm.x), Jin[1] + m * (cc - cm.y * cm.y), Jin[2] + m * (cc - cm.z * cm.z),
+            Jin[3] - m * cm.x * cm.y, Jin[4] - m * cm.x * cm.z, Jin[5] - m * cm.y * cm.z};
+    A = a;
+}
+
 // --------------------------------------------------- ABA passes 2 and 3 (RBDA 7.1)
 // tau / arm_eff: drive torque and joint-space inertia added on the diagonal
 // (armature + the implicit PD terms).  Returns qdd.
 template <class T, bool DR = false>
 PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const float* tau, const float* arm_eff, float* qdd, const EnvDR* dr = nullptr) {
-    // articulated inertia / bias force handed down by the child, in this link's coordinates
+    // articulated inertia / bias force handed down by the child, in this link's coordinates.  Pairs that take the same
+    // operator travel packed (V3p / S3p above): (A, D), (p_n, p_f), (w, v), (U_a, U_b).
     S3 cA = {0, 0, 0, 0, 0, 0}, cD = {0, 0, 0, 0, 0, 0};
     M3 cB = {{0, 0, 0, 0, 0, 0, 0, 0, 0}};
     V3 cn = mk(0, 0, 0), cf = mk(0, 0, 0);
@@ -502,21 +535,15 @@ PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const flo
         const JointInertial J = T::inertial(i);
         const int ax = T::axis(i);
         V3 w = js[i].w, v = js[i].v;
-        // rigid-body inertia about the link origin: [[Io, m c x],[m c x^T, m 1]]
-        const float msc = DR ? dr->ms[i] : 1.f;              // rigid_body_properties.mass scaling: mass and inertia together
-        float m = DR ? J.mass * msc : J.mass;
-        V3 cm = ld3(J.com);
-        V3 mc = cm * m;
-        float cc = dot(cm, cm);
-        float Jin[6];
-#pragma unroll
-        for (int t = 0; t < 6; t++) Jin[t] = DR ? J.inertia[t] * msc : J.inertia[t];
-        S3 A = {Jin[0] + m * (cc - cm.x * cm.x), Jin[1] + m * (cc - cm.y * cm.y), Jin[2] + m * (cc - cm.z * cm.z),
-                Jin[3] - m * cm.x * cm.y, Jin[4] - m * cm.x * cm.z, Jin[5] - m * cm.y * cm.z};
+        float m;
+        V3 mc;
+        S3 A;
+        link_inertia<DR>(J, DR ? dr->ms[i] : 1.f, m, mc, A);
         V3 h_ang = mul(A, w) + cross(mc, v);
         V3 h_lin = v * m - cross(mc, w);
-        V3 pn = cross(w, h_ang) + cross(v, h_lin) + cn;
-        V3 pf = cross(w, h_lin) + cf;
+        V3p wxh = cross(w, pk(h_ang, h_lin));                       // (w x h_ang, w x h_lin)
+        V3 pn = lo(wxh) + cross(v, h_lin) + cn;
+        V3 pf = hi(wxh) + cf;
         add_sym(A, cA);
         M3 B = {{cB.m[0], cB.m[1] - mc.z, cB.m[2] + mc.y, cB.m[3] + mc.z, cB.m[4], cB.m[5] - mc.x, cB.m[6] - mc.y, cB.m[7] + mc.x, cB.m[8]}};
         S3 D = {cD.xx + m, cD.yy + m, cD.zz + m, cD.xy, cD.xz, cD.yz};
@@ -526,8 +553,9 @@ PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const flo
         float u = tau[i] - comp(pn, ax);
         js[i].ua = ua; js[i].ub = ub; js[i].dinv = dinv; js[i].u = u;
         if (i > 0) {
-            sym_rank1_sub(A, ua, dinv);
-            sym_rank1_sub(D, ub, dinv);
+            S3p AD = pk(A, D);
+            const V3p uab = pk(ua, ub);
+            sym_rank1_sub(AD, uab, dinv);
             V3 uad = ua * dinv;
 #pragma unroll
             for (int r = 0; r < 3; r++) {
@@ -535,16 +563,19 @@ PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const flo
                 B.m[3 * r] -= k * ub.x; B.m[3 * r + 1] -= k * ub.y; B.m[3 * r + 2] -= k * ub.z;
             }
             V3 e = unit(ax);
-            V3 cw = cross(w, e) * qd[i], cv = cross(v, e) * qd[i];   // c = v x S qd
+            V3p c = cross(pk(w, v), e) * qd[i];                     // c = v x S qd, both halves
+            V3 cw = lo(c), cv = hi(c);
             float ud = u * dinv;
-            V3 pan = pn + mul(A, cw) + mul(B, cv) + ua * ud;
-            V3 paf = pf + tmul(B, cw) + mul(D, cv) + ub * ud;
+            // p^a = p + I^a c + U u / D:  (A cw, D cv) packed, the B terms are a matrix and its transpose
+            V3p pa = pk(pn, pf) + mul(AD, c) + pk(mul(B, cv), tmul(B, cw)) + uab * ud;
             // to the parent's coordinates: rotate by E, shift the origin by r
             M3 E = ax == 0 ? joint_rot<0>(JK.origin_rot, js[i].c, js[i].s) : (ax == 1 ? joint_rot<1>(JK.origin_rot, js[i].c, js[i].s) : joint_rot<2>(JK.origin_rot, js[i].c, js[i].s));
             V3 r = ld3(JK.origin_xyz);
-            S3 Ar = rot_sym(E, A), Dr = rot_sym(E, D);
+            const S3p ADr = rot_sym(E, AD);
+            const S3 Ar = lo(ADr), Dr = hi(ADr);
             M3 Br = mul_t(mul(E, B), E);
-            V3 nr = mul(E, pan), fr = mul(E, paf);
+            const V3p nfr = mul(E, pa);
+            V3 nr = lo(nfr), fr = hi(nfr);
             // Bp = Br + r x Dr  (column-wise cross)
             M3 Dm = from_sym(Dr);
             M3 Bp;
@@ -554,10 +585,9 @@ PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const flo
                 Bp.m[j] = Br.m[j] + x.x; Bp.m[3 + j] = Br.m[3 + j] + x.y; Bp.m[6 + j] = Br.m[6 + j] + x.z;
             }
             // Ap[i][j] = Ar[i][j] + (r x row_j(Bp))[i] + (r x row_i(Br))[j]
-            V3 wp0 = cross(r, row(Bp, 0)), wp1 = cross(r, row(Bp, 1)), wp2 = cross(r, row(Bp, 2));
-            V3 wb0 = cross(r, row(Br, 0)), wb1 = cross(r, row(Br, 1)), wb2 = cross(r, row(Br, 2));
-            cA.xx = Ar.xx + wp0.x + wb0.x; cA.yy = Ar.yy + wp1.y + wb1.y; cA.zz = Ar.zz + wp2.z + wb2.z;
-            cA.xy = Ar.xy + wp1.x + wb0.y; cA.xz = Ar.xz + wp2.x + wb0.z; cA.yz = Ar.yz + wp2.y + wb1.z;
+            V3p w0 = cross(r, pk(row(Bp, 0), row(Br, 0))), w1 = cross(r, pk(row(Bp, 1), row(Br, 1))), w2 = cross(r, pk(row(Bp, 2), row(Br, 2)));
+            cA.xx = Ar.xx + w0.x[0] + w0.x[1]; cA.yy = Ar.yy + w1.y[0] + w1.y[1]; cA.zz = Ar.zz + w2.z[0] + w2.z[1];
+            cA.xy = Ar.xy + w1.x[0] + w0.y[1]; cA.xz = Ar.xz + w2.x[0] + w0.z[1]; cA.yz = Ar.yz + w2.y[0] + w1.z[1];
             cB = Bp; cD = Dr;
             cn = nr + cross(r, fr); cf = fr;
         }
@@ -572,6 +602,8 @@ PP_HD void aba_solve(const ArmSite& S, JointSave* js, const float* qd, const flo
         M3 E = ax == 0 ? joint_rot<0>(J.origin_rot, js[i].c, js[i].s) : (ax == 1 ? joint_rot<1>(J.origin_rot, js[i].c, js[i].s) : joint_rot<2>(J.origin_rot, js[i].c, js[i].s));
         V3 r = ld3(J.origin_xyz);
         V3 e = unit(ax);
+        // (scalar: with this recursion packed, the table-reading instantiation fed unit tables strays from the table-free one by more than
+        //  tests/test_gpu_parity.py::test_unit_randomization_tables_reproduce_the_plain_kernel allows, 1.10 x its tolerance against 0.95)
         V3 aw2 = tmul(E, aw) + cross(js[i].w, e) * qd[i];
         V3 av2 = tmul(E, av + cross(aw, r)) + cross(js[i].v, e) * qd[i];
         float a = (js[i].u - dot(js[i].ua, aw2) - dot(js[i].ub, av2)) * js[i].dinv;
@@ -840,6 +872,13 @@ PP_HD V3 heading_rotate(const float hinv[4], V3 v) {
     float k = sz * qw * 2.0f;
     return mk(v.x * s - v.y * k, v.y * s + v.x * k, v.z);
 }
+PP_HD V3p heading_rotate(const float hinv[4], V3p v) {   // both halves by the same heading
+    float qw = hinv[3], sz = hinv[2];
+    float s = 2.0f * (qw * qw) - 1.0f;
+    float k = sz * qw * 2.0f;
+    V3p r = {v.x * s - v.y * k, v.y * s + v.x * k, v.z};
+    return r;
+}
 
 struct RewardIn {
     float humanoid_x;   // humanoid1_root_states[..., 0]
@@ -1037,8 +1076,8 @@ PP_HD void write_obs_bodies(const V3* body_pos, const V3* body_vel, const float 
     V3 root = body_pos[0];
 #pragma unroll
     for (int j = J0; j < J1; j++) {
-        V3 lp = heading_rotate(hinv, body_pos[j] - root);   // TT:1696
-        V3 lv = heading_rotate(hinv, body_vel[j]);          // TT:1697
+        const V3p l = heading_rotate(hinv, pk(body_pos[j] - root, body_vel[j]));   // TT:1696 and TT:1697 take the same rotation
+        const V3 lp = lo(l), lv = hi(l);
         store(3 * j, lp.x); store(3 * j + 1, lp.y); store(3 * j + 2, lp.z);
         store(3 * NB + 3 * j, lv.x); store(3 * NB + 3 * j + 1, lv.y); store(3 * NB + 3 * j + 2, lv.z);
     }

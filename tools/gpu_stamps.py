@@ -11,10 +11,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 lib = os.path.join(ROOT, os.environ.get("OUT", "out"), "libppenv_stamp.so")
 SRC = os.environ.get("PPENV_STAMP_SRC", os.path.join(ROOT, "isaacgym_amd", "csrc"))   # another source tree to stamp (A/B of two builds)
+prebuilt = os.environ.get("PPENV_STAMP_LIB")      # a stamped library built elsewhere (isaacgym_amd._lib.build(out=..., extra_flags=["-DPP_STAMP=1"])): nothing is compiled here
+if prebuilt:
+    lib = os.path.abspath(prebuilt)
 os.makedirs(os.path.dirname(lib), exist_ok=True)
-subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only",
-                "-fPIC", "-shared", "-DPP_STAMP=1", *os.environ.get("PPENV_STAMP_DEFS", "").split(), "-I", os.path.join(ROOT, "include"), "-o", lib, os.path.join(SRC, "ppenv.hip"), os.path.join(SRC, "ppenv_ta.hip"),
-                os.path.join(SRC, "ppenv_ta_sim.hip"), os.path.join(SRC, "ppenv_ta_chain.hip"), os.path.join(SRC, "ppenv_policy.hip")], check=True)
+if not prebuilt:
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only",
+                    "-fPIC", "-shared", "-DPP_STAMP=1", *os.environ.get("PPENV_STAMP_DEFS", "").split(), "-I", os.path.join(ROOT, "include"), "-o", lib, os.path.join(SRC, "ppenv.hip"), os.path.join(SRC, "ppenv_ta.hip"),
+                    os.path.join(SRC, "ppenv_ta_sim.hip"), os.path.join(SRC, "ppenv_ta_chain.hip"), os.path.join(SRC, "ppenv_policy.hip")], check=True)
 os.environ["PPENV_LIB"] = lib
 import torch  # noqa: E402
 from isaacgym_amd import _lib, scene  # noqa: E402
@@ -44,6 +48,9 @@ if os.environ.get("PPENV_STEP_KERNEL", "split") == "fused":
         print(f"  {names[k]:24s} {d:9.0f} cycles  {100 * d / tot:5.1f} %")
 else:
     t0 = np.minimum(t[:, 0], t[:, 16])
+    if t[:, 11].any():    # (builds from before the stamp existed leave the slot zero)
+        d = t[:, 11] - t0
+        print("  task tail starts (final hand-off received) percentiles 0/50/90/100: " + " ".join(f"{np.percentile(d, q):.0f}" for q in (0, 50, 90, 100)))
     arm = {1: "arm: loads + targets", 2: "arm: substep 1 (vel sweep + ABA) + publish", 4: "arm: substep 2 + publish",
            5: "arm: FK of final state + publish paddle", 6: "arm: body obs", 7: "arm: final barrier wait"}
     ball = {17: "ball: loads + next serve", 18: "ball: (no wait)", 19: "ball: FK + substep 1", 20: "ball: wait for boundary 1",
