@@ -24,7 +24,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip"), os.path.join(_PKG, "csrc", "ppenv_dr_adr.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -38,6 +38,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_play_delay_device.h"), os.path.join(ROOT, "include", "ppenv_play_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_train_delay_device.h"), os.path.join(ROOT, "include", "ppenv_train_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_serve_curric_device.h"), os.path.join(ROOT, "include", "ppenv_serve_curric.h"),
+           os.path.join(_PKG, "csrc", "ppenv_dr_adr_device.h"), os.path.join(ROOT, "include", "ppenv_dr_adr.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -45,11 +46,13 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize
 # the ray caster's depth of a sky pixel is +inf; the serve plan's draw rounds every operation on its own, as its host build does, and a pinned zero keeps its sign;
 # the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN;
 # the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf;
-# the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does
+# the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does;
+# ADR draws with the reset-time plan's arithmetic, stages returns as the serve curriculum does and rounds every operation of its update on its own
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve_curric.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_dr_adr.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
@@ -216,6 +219,28 @@ class ServeCurricState(C.Structure):
     """ctypes mirror of pp_serve_curric_state: device pointers."""
     _fields_ = [("count", C.c_void_p), ("next_bin", C.c_void_p), ("cur_bin", C.c_void_p), ("ret", C.c_void_p), ("games", C.c_void_p),
                 ("mean", C.c_void_p), ("dropped", C.c_void_p), ("cdf", C.c_void_p)]
+
+
+ADR_COIN_INDEX, ADR_PICK_INDEX, ADR_MAX_SLOTS = 512, 513, 2 * scene.DR_MAX_TABLES + 1     # PP_ADR_COIN_INDEX, PP_ADR_PICK_INDEX, PP_ADR_MAX_SLOTS
+
+
+class AdrDim(C.Structure):
+    """ctypes mirror of pp_dr_adr_dim (include/ppenv_dr_adr.h)."""
+    _fields_ = [("table", C.c_void_p), ("rows", C.c_int32), ("start_lo", C.c_float), ("start_hi", C.c_float), ("limit_lo", C.c_float),
+                ("limit_hi", C.c_float), ("step", C.c_float)]
+
+
+class Adr(C.Structure):
+    """ctypes mirror of pp_dr_adr."""
+    _fields_ = [("num_envs", C.c_int32), ("env_id_offset", C.c_int32), ("seed", C.c_uint64), ("reset_rows", C.c_int32), ("num_agents", C.c_int32),
+                ("dims", C.c_int32), ("thr", C.c_uint32), ("min_games", C.c_int32), ("t_low", C.c_float), ("t_high", C.c_float), ("reserved", C.c_int32),
+                ("dim", AdrDim * scene.DR_MAX_TABLES)]
+
+
+class AdrState(C.Structure):
+    """ctypes mirror of pp_dr_adr_state: device pointers."""
+    _fields_ = [("range", C.c_void_p), ("draws", C.c_void_p), ("slot", C.c_void_p), ("ret", C.c_void_p), ("acc_n", C.c_void_p), ("acc_q", C.c_void_p),
+                ("games", C.c_void_p), ("dropped", C.c_void_p), ("mean", C.c_void_p), ("widened", C.c_void_p), ("narrowed", C.c_void_p)]
 
 
 RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
@@ -506,6 +531,12 @@ def load(path):
     L.pp_serve_curric_fold_bytes.argtypes = [i64]
     L.pp_serve_curric_fold.argtypes = [vp, vp, i64, i32, vp, vp, vp]
     L.pp_serve_curric_update.argtypes = [vp, i32, vp, statep, vp]
+    # ---- include/ppenv_dr_adr.h
+    adrsp = C.POINTER(AdrState)
+    L.pp_dr_adr_upload.argtypes = [C.POINTER(Adr), C.c_double, vp, vp]
+    L.pp_dr_adr_fill.argtypes = [vp, i32, i32, adrsp, vp]
+    L.pp_dr_adr_step.argtypes = [vp, i32, vp, vp, adrsp, vp, vp, vp]
+    L.pp_dr_adr_update.argtypes = [vp, i32, vp, adrsp, vp]
     return L
 
 

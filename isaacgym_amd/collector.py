@@ -54,10 +54,14 @@ class RolloutCollector:
     serve: what keeps the env's serve override buffer — a serve.ServePlan or a curriculum.ServeCurriculum set on `env` — an object with
     step(t, rew_t, reset_t), called right after the env step of row t with rewards[t] (unscaled) and dones[t]: one launch, no copy.  A
     plan runs its apply(dones[t]); a curriculum also credits the games that ended and stages row t for the trainer's fold().  None (the
-    default): no call."""
+    default): no call.
+
+    randomizer: what keeps the env's randomisation tables — a dr.ResetRandomizer (a reset-time plan) or an adr.AutoRandomizer — likewise an
+    object with step(t, rew_t, reset_t), called right after serve.step with the same rows.  It is independent of `serve`: a serve
+    curriculum and ADR can run together.  None (the default): no call."""
 
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0, action_delay=0, obs_delay=0,
-                 latency_seed=0, env_id_offset=0, serve=None):
+                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None):
         self.action_delay, self.obs_delay = delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay)
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
@@ -72,6 +76,7 @@ class RolloutCollector:
         self.sigma = (torch.ones(a, device=dev) if sigma is None else sigma.to(dev, torch.float32)).contiguous()
         self.counter = 0
         self.serve = serve
+        self.randomizer = randomizer
         self.on_step = None                   # called with no arguments right after every env.step of collect() (render.TrainingCapture.on_step)
         self.act_line = self.obs_line = self.applied = self.raw_obs = None
         self._done_prev = None                # the dones of the last env step (a row of `dones`); None before any step
@@ -100,6 +105,8 @@ class RolloutCollector:
                 self.obs_line.push(self.raw_obs, self.dones[t], self.obs[t + 1])
             if self.serve is not None:
                 self.serve.step(t, self.rewards[t], self.dones[t])
+            if self.randomizer is not None:
+                self.randomizer.step(t, self.rewards[t], self.dones[t])
             self._done_prev = self.dones[t]
             if self.on_step is not None:
                 self.on_step()

@@ -47,6 +47,10 @@ class ResetRandomizer:
         _lib.check(self.L.ppenv_dr_apply(self.plan_dev.data_ptr(), self.num_envs, reset_buf.data_ptr(), self.randomize_buf.data_ptr(),
                                          self.state.data_ptr(), _lib.stream(self.device)), self.L)
 
+    def step(self, t, rew_t, reset_t):
+        """The collector's per-step hook (RolloutCollector(randomizer=)): apply(reset_t) on the row of dones the env step just wrote."""
+        self.apply(reset_t)
+
     def apply_ids(self, env_ids):
         """The rule for the envs reset_idx(env_ids) lists (ppenv_dr_apply_ids); duplicates are dropped here (the kernel wants distinct ids)."""
         ids = torch.unique(torch.as_tensor(env_ids, dtype=torch.int64).reshape(-1).to(self.device))

@@ -37,6 +37,10 @@ Control latency (PPOTrainer(action_delay=, obs_delay=), --action-delay / --obs-d
 command path and / or the sensing path, fixed or drawn per env at every episode start (RolloutCollector; include/ppenv_train_delay.h;
 DESIGN §5d "Training under latency").  Off by default, and then nothing is built.
 
+Domain randomisation (PPOTrainer(randomization=, adr=), --randomize / --adr TABLE=...): a reset-time plan (include/ppenv_dr.h) or automatic
+domain randomisation, a device-resident curriculum over the tables' ranges (adr.AutoRandomizer; include/ppenv_dr_adr.h), run from the
+collector's per-step hook (DESIGN §5d "Randomisation and ADR in training").  Off by default, and then nothing is built.
+
 The score (GameMeter; C ABI: include/ppenv_ppo_meter.h) is rl_games' game_rewards / game_lengths: AverageMeter(games_to_track) over the
 finished games' unscaled returns (agent 0's row of each env) and lengths, updated once per epoch over the collector's horizon by two
 launches.  `fit` is rl_games' loop around train_epoch(): the periodic save to nn/<name>.pth, the best checkpoint from save_best_after on,
@@ -433,13 +437,29 @@ class PPOTrainer:
     keeps the statistics over uniform bins: the control run.  Checkpoints carry the plan's cells under "serve" and the curriculum's bins,
     parameters and table under "curriculum"; load() restores the table and raises ValueError on other bins.  Per-env state is not
     checkpointed.  A plan together with a curriculum is a ValueError; with neither, nothing is allocated or launched and the run is
-    bitwise the run without the arguments.  clear_serve() gives the built-in serves back."""
+    bitwise the run without the arguments.  clear_serve() gives the built-in serves back.
+    randomization: train under reset-time domain randomisation (include/ppenv_dr.h, all of its vocabulary) — a plan dict as
+    scene.reset_randomization_plan returns, or True for the actor parameters of the task cfg's own randomization_params — set on the env with
+    env.set_reset_randomization, keyed scene.stream_seed(seed, scene.STREAM_TABLES) and the task's env_id_offset.  The tables are drawn once
+    when the trainer is built; from then on the collector runs the plan's launch after every env step on the row of dones that step wrote,
+    so an env's columns change exactly when it resets.  Noise amplitudes and gravity stay what the env has.
+    adr: dict(dims=..., boundary_frac=0.25, min_games=256, t_low=..., t_high=...) — automatic domain randomisation (adr.AutoRandomizer;
+    include/ppenv_dr_adr.h — this build's own rule): a current range per table, a share of the envs pinned to a boundary for a whole game,
+    every boundary moved outward or back in once per epoch by the mean return of its games.  One launch per control step, a fold and an
+    update per epoch, no host read; data-parallel, the per-slot totals are summed over the ranks (one int64 all-reduce of 3 S words), so
+    every rank holds the same ranges.  train_epoch() then also returns adr_lo, adr_hi [D] and adr_games, adr_mean [S].  boundary_frac=0
+    is fixed-range randomisation by the same kernel: the control run.  Checkpoints carry the plan under "randomization" and the
+    randomizer's dims, parameters, ranges and per-slot state under "adr"; load() restores the latter and raises ValueError on other dims.
+    Both arguments together are a ValueError; a task that arrives with randomize: True is refused as before; with neither, nothing is
+    allocated or launched.  clear_randomization() drops both."""
 
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
-                 curriculum=None):
+                 curriculum=None, randomization=None, adr=None):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
+        if randomization is not None and randomization is not False and adr is not None:
+            raise ValueError("randomization together with adr: a reset-time plan and ADR write the same randomisation tables")
         if task._serve_plan is not None:
             raise ValueError("a task with a serve plan set is not supported by PPOTrainer: the collector drives the env below VecTask.step, so the plan's "
                              "per-step launch would not run; call task.clear_serve_plan() first and pass the cells as serve_plan=")
@@ -478,10 +498,25 @@ class PPOTrainer:
             task._serve_plan = env.set_serve_plan(serve_plan, paired=serve_paired, seed=serve_seed)
         elif curriculum is not None:
             self.curriculum = env.set_serve_curriculum(**dict(curriculum), seed=serve_seed, horizon=H)
+        self.adr = self.randomization = None
+        tables_seed = scene.stream_seed(self.seed, scene.STREAM_TABLES)
+        if randomization is not None and randomization is not False:
+            if randomization is True:
+                randomization = scene.reset_randomization_plan(task.randomization_params, dof_rows=task.DR_DOF_ROWS, mass_rows=task.DR_MASS_ROWS)
+                if not randomization["tables"]:
+                    raise ValueError("randomization=True: the task cfg's randomization_params name no actor parameter of the humanoid")
+            self.randomization = randomization
+            rr = env.set_reset_randomization(randomization, seed=tables_seed)
+            rr.apply(torch.zeros(rr.reset_rows * env.num_envs, dtype=torch.int64, device=dev))   # the first application draws every env's columns: training starts randomised
+        elif adr is not None:
+            from .adr import AutoRandomizer
+            self.adr = AutoRandomizer(env, **dict(adr), seed=tables_seed, horizon=H)
+        randomizer = self.adr if self.adr is not None else (env.reset_randomization if self.randomization is not None else None)
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
                                     sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
                                     action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
-                                    env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan)
+                                    env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan,
+                                    randomizer=randomizer)
         self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
@@ -560,6 +595,25 @@ class PPOTrainer:
         cur.update(tot)
         t = cur.table()
         return dict(curriculum_games=t["games"].clone(), curriculum_mean=t["mean"].clone(), curriculum_prob=t["prob"])
+
+    def clear_randomization(self):
+        """No randomisation again: the plan or the ADR state is dropped, the env's tables are cleared and the collector launches nothing for
+        them any more."""
+        self.col.randomizer = None
+        if self.adr is not None or self.randomization is not None:
+            self.env.clear_randomization()
+        self.adr = self.randomization = None
+
+    @torch.no_grad()
+    def _adr_epoch(self):
+        """The collected horizon into ADR: fold, the ranks' totals summed, update.  -> the epoch's adr_lo, adr_hi [D], adr_games, adr_mean [S]."""
+        a = self.adr
+        tot = a.fold()
+        if self.multi:
+            torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
+        a.update(tot)
+        t = a.table()
+        return dict(adr_lo=t["lo"].clone(), adr_hi=t["hi"].clone(), adr_games=t["games"].clone(), adr_mean=t["mean"].clone())
 
     def latency(self):
         """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
@@ -676,6 +730,7 @@ class PPOTrainer:
         self.net.train()
         self.collect()
         curric = self._curriculum_epoch() if self.curriculum is not None else None
+        adr = self._adr_epoch() if self.adr is not None else None
         self.meter.update(self.col.rewards, self.col.dones)
         score = self.meter.snapshot()
         ep = self._episodes()
@@ -704,6 +759,8 @@ class PPOTrainer:
             out.update(self._outcomes())
         if curric is not None:
             out.update(curric)
+        if adr is not None:
+            out.update(adr)
         return out
 
     # -- checkpoints --
@@ -723,6 +780,11 @@ class PPOTrainer:
             sd["serve"] = self.serve()
         if self.curriculum is not None:
             sd["curriculum"] = self.curriculum.state_dict()
+        if self.randomization is not None:
+            sd["randomization"] = {"frequency": int(self.randomization["frequency"]),
+                                   "tables": {k: {f: (list(v) if isinstance(v, (tuple, list)) else v) for f, v in t.items()} for k, t in self.randomization["tables"].items()}}
+        if self.adr is not None:
+            sd["adr"] = self.adr.state_dict()
         return sd
 
     def save(self, path):
@@ -738,6 +800,8 @@ class PPOTrainer:
         ck = torch.load(path, map_location=self.device, weights_only=True)
         if self.curriculum is not None and "curriculum" in ck:               # first: other bins raise before anything is overwritten.  A file without one: the table starts fresh
             self.curriculum.load_state_dict(ck["curriculum"])
+        if self.adr is not None and "adr" in ck:                             # likewise: other dims raise before anything is overwritten
+            self.adr.load_state_dict(ck["adr"])
         sd, lr = ck["model"], self.learner
         from .policy import layers_from_rlgames_state_dict
         actor, critic = layers_from_rlgames_state_dict(sd)
@@ -769,7 +833,7 @@ class PPOTrainer:
 
 
 # ---- the run loop -----------------------------------------------------------------------------------------------------------------
-def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, curriculum_every=0, curriculum_out=None):
+def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, curriculum_every=0, curriculum_out=None, adr_every=0, adr_out=None):
     """rl_games' train loop around train_epoch(), restated from its published a2c_common.train (rl_games is absent offline: parity
     unpinned).  Runs until trainer.epoch reaches max_epochs (default cfg.max_epochs: the TOTAL, so a resumed trainer continues its
     numbering) or the score wins.  After every epoch, with ONE host read (here, not in train_epoch):
@@ -785,7 +849,8 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, c
     capture: a render.TrainingCapture (trainer.set_capture is called with it): polled after every epoch's host read, closed before
     returning; the result then has `videos`, the files it wrote.
     curriculum_every: with a serve curriculum, rank 0 prints its table every so many epochs and at the end (0: never) — a second host read in
-    those epochs — and rewrites curriculum_out (a json path) with it."""
+    those epochs — and rewrites curriculum_out (a json path) with it.
+    adr_every, adr_out: the same for ADR's range table (adr.table_json / table_lines)."""
     cfg = trainer.cfg
     if capture is not None:
         trainer.set_capture(capture)
@@ -834,6 +899,14 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, c
             if curriculum_out:
                 os.makedirs(os.path.dirname(os.path.abspath(curriculum_out)), exist_ok=True)
                 with open(curriculum_out, "w") as fh:
+                    json.dump(rows, fh, indent=1)
+        if adr_every and trainer.adr is not None and (epoch % adr_every == 0 or last) and trainer.rank == 0:
+            from . import adr as adr_mod
+            rows = adr_mod.table_json(trainer.adr, epoch)
+            print("\n".join(adr_mod.table_lines(rows)), flush=True)
+            if adr_out:
+                os.makedirs(os.path.dirname(os.path.abspath(adr_out)), exist_ok=True)
+                with open(adr_out, "w") as fh:
                     json.dump(rows, fh, indent=1)
     out = dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
                best_score=trainer.last_mean_rewards, paths=paths, written=written)
@@ -915,6 +988,18 @@ def main(argv=None):
     ap.add_argument("--curriculum-alpha", type=float, default=0.3, help="the weight of an epoch's mean return in a bin's running mean, (0, 1]")
     ap.add_argument("--curriculum-every", type=int, default=0, help="print the curriculum's table every so many epochs (0: never)")
     ap.add_argument("--curriculum-out", default=None, help="a json file rewritten with the table at each print")
+    ap.add_argument("--randomize", action="store_true", help="train under reset-time domain randomisation: the actor parameters of the task cfg's "
+                    "randomization_params (needs --cfg-dir, or a task whose cfg carries them), redrawn for an env when it resets")
+    ap.add_argument("--adr", action="append", default=[], metavar="TABLE=START_LO:START_HI:LIMIT_LO:LIMIT_HI:STEP", help="automatic domain randomisation of "
+                    "one table (dof_stiffness_scale, dof_damping_scale, link_mass_scale, restitution_scale, friction_scale): its range starts at "
+                    "START and widens towards LIMIT by STEP per move; repeatable")
+    ap.add_argument("--adr-boundary-frac", type=float, default=0.25, help="the share of the envs that play a game pinned to a boundary, 0 .. 1 (0: fixed ranges)")
+    ap.add_argument("--adr-min-games", type=int, default=256, help="games a boundary gathers before it is judged")
+    ap.add_argument("--adr-low", type=float, default=None, help="a boundary whose games' mean return is at or below this moves back in "
+                    "(write a negative value in exponent form as --adr-low=-1e3)")
+    ap.add_argument("--adr-high", type=float, default=None, help="a boundary whose games' mean return is at or above this moves outward")
+    ap.add_argument("--adr-every", type=int, default=0, help="print ADR's range table every so many epochs (0: never)")
+    ap.add_argument("--adr-out", default=None, help="a json file rewritten with the table at each print")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -941,6 +1026,15 @@ def main(argv=None):
             curriculum_mod.check_parameters(args.curriculum_power, args.curriculum_mix, args.curriculum_alpha)
             curriculum = dict(bins=curriculum_mod.grid(curriculum_mod.grid_parse(args.curriculum)), power=args.curriculum_power, mix=args.curriculum_mix,
                               alpha=args.curriculum_alpha)
+        adr = None
+        if args.adr:
+            if args.randomize:
+                raise ValueError("--randomize together with --adr: a reset-time plan and ADR write the same randomisation tables")
+            if args.adr_low is None or args.adr_high is None:
+                raise ValueError("--adr needs --adr-low and --adr-high: the mean returns at which a boundary moves back in / outward")
+            from . import adr as adr_mod
+            frac, games, low, high = adr_mod.check_parameters(args.adr_boundary_frac, args.adr_min_games, args.adr_low, args.adr_high)
+            adr = dict(dims=adr_mod.check_dims(adr_mod.parse(args.adr)), boundary_frac=frac, min_games=games, t_low=low, t_high=high)
     except ValueError as e:
         ap.error(str(e))
     rank, seed, dev = 0, args.seed, None
@@ -969,7 +1063,13 @@ def main(argv=None):
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay,
-                    serve_plan=serve_plan, curriculum=curriculum)
+                    serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr)
+    if rank == 0 and tr.randomization is not None:
+        print("reset-time randomisation: " + ", ".join(f"{k} {t['distribution']} {t['operation']} {t['range'][0]:g}..{t['range'][1]:g}"
+                                                       for k, t in tr.randomization["tables"].items()), flush=True)
+    if rank == 0 and adr is not None:
+        from .adr import table_json, table_lines
+        print("\n".join(table_lines(table_json(tr.adr))), flush=True)
     if rank == 0 and serve_plan is not None:
         print("serve plan: " + ", ".join(f"{k} {v[0]:g}..{v[1]:g}" for k, v in tr.serve()["cells"][0].items()), flush=True)
     if rank == 0 and curriculum is not None:
@@ -987,7 +1087,8 @@ def main(argv=None):
         renderer = play.make_renderer(task, args)
         capture = render.TrainingCapture(renderer, os.path.join(out, "videos"), freq=args.capture_video_freq or 1464, length=args.capture_video_len or 100,
                                          every=args.capture_every, fps=args.capture_fps, deferred=args.capture_deferred, trajectories=args.capture_trajectories)
-    done = fit(tr, out, args.task, print_every=args.print_every, capture=capture, curriculum_every=args.curriculum_every, curriculum_out=args.curriculum_out)
+    done = fit(tr, out, args.task, print_every=args.print_every, capture=capture, curriculum_every=args.curriculum_every, curriculum_out=args.curriculum_out,
+               adr_every=args.adr_every, adr_out=args.adr_out)
     if rank == 0:
         for path in done.get("videos", []):
             print(f"saved {path} (video)", flush=True)

@@ -1030,6 +1030,41 @@ def latency_draws(stream_seed, gids, episodes, channel, lo, hi):
     return (lo + (((h >> u32(8)).astype(u64) * u64(hi - lo + 1)) >> u64(24)).astype(np.int64)).astype(np.int32)
 
 
+def adr_draws(stream_seed, gids, draws, dims, ranges, thr):
+    """Host restatement of ADR's DRAW (include/ppenv_dr_adr.h; pp::adr_draw) in numpy: what redraw number `draws` of the global env ids
+    `gids` (arrays, broadcast against each other) writes under the STREAM seed `stream_seed` (stream_seed(seed, STREAM_TABLES)).  dims: the
+    rows of each dim's table, in the dims' order; ranges: [D][2] current (lo, hi); thr: floor(boundary_frac * 2^24).
+    -> (slots int32 [M]: 2 d + side for a boundary worker, 2 D for an interior env; [D] float32 arrays [rows_d, M]: the columns)."""
+    u32, u64, f32 = np.uint32, np.uint64, np.float32
+    rows = [int(r) for r in dims]
+    D = len(rows)
+    rng = np.asarray(ranges, f32).reshape(D, 2)
+    if not 1 <= D <= DR_MAX_TABLES or any(not 1 <= r <= DR_MAX_ROWS for r in rows) or not 0 <= int(thr) <= 1 << 24:
+        raise ValueError(f"adr_draws: 1 .. {DR_MAX_TABLES} dims of 1 .. {DR_MAX_ROWS} rows and thr in 0 .. 2^24, not rows {rows}, thr {thr}")
+    sd = (int(stream_seed) ^ DR_SEED_SALT) & 0xFFFFFFFFFFFFFFFF
+
+    def hash32(x):                                              # (uint32 arrays wrap silently)
+        x = (x ^ (x >> u32(16))) * u32(0x7FEB352D)
+        x = (x ^ (x >> u32(15))) * u32(0x846CA68B)
+        return x ^ (x >> u32(16))
+    gid, j = np.broadcast_arrays(np.atleast_1d(np.asarray(gids, np.int64)).astype(u32), np.atleast_1d(np.asarray(draws, np.int64)).astype(u32))
+    h = hash32(gid ^ u32(sd & 0xFFFFFFFF))
+    h = hash32(h + j * u32(0x9E3779B9) + u32(sd >> 32))
+    u24 = lambda k: hash32(h + u32(((k + 1) * 0x85EBCA6B) & 0xFFFFFFFF)) >> u32(8)
+    pick = ((u24(513).astype(u64) * u64(2 * D)) >> u64(24)).astype(np.int32)
+    slots = np.where(u24(512).astype(np.int64) < int(thr), pick, np.int32(2 * D)).astype(np.int32)
+    cols = []
+    for d, nrows in enumerate(rows):
+        lo, hi = rng[d]
+        c = np.empty((nrows, gid.size), f32)
+        for r in range(nrows):
+            v = (u24(d * DR_MAX_ROWS + r).astype(f32) * f32(1.0 / 16777216.0) * f32(hi - lo)).astype(f32) + lo
+            c[r] = np.where(v == 0, f32(0), v)
+        c[:, slots == 2 * d], c[:, slots == 2 * d + 1] = lo, hi
+        cols.append(c)
+    return slots, cols
+
+
 def ta_reset_draws(params, env_ids, episodes):
     """Host restatement of the 27-DoF task's reset draws (ta_post_physics_kernel, TA:976-979 + 346-377): for each (env,
     episode) the five values ball y, ball z, vx, vy, vz.  Used to lay out the state at creation (episode 0); resets during
