@@ -24,7 +24,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_ppo_meter.hip"), os.path.join(_PKG, "csrc", "ppenv_render.hip"), os.path.join(_PKG, "csrc", "ppenv_serve.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip"), os.path.join(_PKG, "csrc", "ppenv_dr_adr.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip"), os.path.join(_PKG, "csrc", "ppenv_dr_adr.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_critic_input.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -39,6 +40,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_train_delay_device.h"), os.path.join(ROOT, "include", "ppenv_train_delay.h"),
            os.path.join(_PKG, "csrc", "ppenv_serve_curric_device.h"), os.path.join(ROOT, "include", "ppenv_serve_curric.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_adr_device.h"), os.path.join(ROOT, "include", "ppenv_dr_adr.h"),
+           os.path.join(_PKG, "csrc", "ppenv_critic_input_device.h"), os.path.join(ROOT, "include", "ppenv_critic_input.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -47,12 +49,14 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize
 # the paired statistics round d * d before adding it, as their host build does, and their table starts as NaN;
 # the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf;
 # the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does;
-# ADR draws with the reset-time plan's arithmetic, stages returns as the serve curriculum does and rounds every operation of its update on its own
+# ADR draws with the reset-time plan's arithmetic, stages returns as the serve curriculum does and rounds every operation of its update on its own;
+# the privileged critic inputs copy a float bit for bit (a negative zero keeps its sign) and round the normaliser's two operations on their own
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve_curric.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_dr_adr.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_critic_input.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
@@ -241,6 +245,20 @@ class AdrState(C.Structure):
     """ctypes mirror of pp_dr_adr_state: device pointers."""
     _fields_ = [("range", C.c_void_p), ("draws", C.c_void_p), ("slot", C.c_void_p), ("ret", C.c_void_p), ("acc_n", C.c_void_p), ("acc_q", C.c_void_p),
                 ("games", C.c_void_p), ("dropped", C.c_void_p), ("mean", C.c_void_p), ("widened", C.c_void_p), ("narrowed", C.c_void_p)]
+
+
+CRITIC_MAX_SOURCES, CRITIC_MAX_COLS = 16, 1024                                           # PP_CRITIC_MAX_SOURCES, PP_CRITIC_MAX_COLS
+CRITIC_F32, CRITIC_I32, CRITIC_ROW_MAJOR, CRITIC_TABLE_MAJOR = 0, 1, 0, 1                # PP_CRITIC_F32 / _I32, PP_CRITIC_ROW_MAJOR / _TABLE_MAJOR
+
+
+class CriticSource(C.Structure):
+    """ctypes mirror of pp_critic_source (include/ppenv_critic_input.h)."""
+    _fields_ = [("p", C.c_void_p), ("kind", C.c_int32), ("cols", C.c_int32), ("layout", C.c_int32), ("reserved", C.c_int32), ("stride", C.c_int64)]
+
+
+class CriticTable(C.Structure):
+    """ctypes mirror of pp_critic_table."""
+    _fields_ = [("rows", C.c_int32), ("num_agents", C.c_int32), ("sources", C.c_int32), ("total_cols", C.c_int32), ("source", CriticSource * CRITIC_MAX_SOURCES)]
 
 
 RENDER_MAX_PRIMS, RENDER_MAX_ENVS, RENDER_MAX_SOURCES = 160, 16, 4           # PP_RENDER_MAX_*
@@ -537,6 +555,10 @@ def load(path):
     L.pp_dr_adr_fill.argtypes = [vp, i32, i32, adrsp, vp]
     L.pp_dr_adr_step.argtypes = [vp, i32, vp, vp, adrsp, vp, vp, vp]
     L.pp_dr_adr_update.argtypes = [vp, i32, vp, adrsp, vp]
+    # ---- include/ppenv_critic_input.h
+    L.pp_critic_input_upload.argtypes = [C.POINTER(CriticTable), vp, vp]
+    L.pp_critic_input_gather.argtypes = [vp, i32, i32, vp, i64, vp]
+    L.pp_critic_input_prepare.argtypes = [vp, i64, i32, i32, vp, vp, f32, vp, i32, i32, vp]
     return L
 
 

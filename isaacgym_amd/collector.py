@@ -58,10 +58,17 @@ class RolloutCollector:
 
     randomizer: what keeps the env's randomisation tables — a dr.ResetRandomizer (a reset-time plan) or an adr.AutoRandomizer — likewise an
     object with step(t, rew_t, reset_t), called right after serve.step with the same rows.  It is independent of `serve`: a serve
-    curriculum and ADR can run together.  None (the default): no call."""
+    curriculum and ADR can run together.  None (the default): no call.
+
+    critic_input: source names (critic_input.NAMES: "tables", "latency", "raw_obs"; a tuple or the CLI's comma-separated text) of the
+    privileged critic inputs of a num_priv > 0 network (include/ppenv_critic_input.h).  The collector then keeps `priv` [H+1, N, P] fp32 and
+    every forward reads priv[t] beside obs[t].  Row t + 1 is gathered — one launch, straight into the slice — after the env step, the
+    delay-line pushes and the serve / randomizer hooks of step t, so it shows the tables and delays the env will play step t + 1 with; row
+    0 is gathered once at construction; next_horizon() carries row H to row 0.  None or empty (the default): nothing is allocated or
+    launched, and `priv` and `critic_input` are None."""
 
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0, action_delay=0, obs_delay=0,
-                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None):
+                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None, critic_input=None):
         self.action_delay, self.obs_delay = delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay)
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
@@ -89,14 +96,26 @@ class RolloutCollector:
             self.obs_line.push(self.raw_obs, None, self.obs[0])
         else:
             self.obs[0].copy_(env.obs_buf)
+        self.critic_input = self.priv = None
+        if critic_input:
+            from .critic_input import CriticInput
+            self.critic_input = CriticInput(env, self, critic_input)
+            if self.critic_input.P != getattr(net, "num_priv", 0):
+                raise ValueError(f"critic_input: {self.critic_input.P} privileged columns, but the network was built with num_priv={getattr(net, 'num_priv', 0)}")
+            self.priv = z(self.h + 1, n, self.critic_input.P)
+            self.critic_input.gather(self.priv[0])
+
+    def _forward(self, t, **kw):
+        if self.priv is None:
+            return self.net.forward(self.obs[t], head_out=self.head[t], **kw)
+        return self.net.forward(self.obs[t], head_out=self.head[t], priv=self.priv[t], **kw)
 
     @torch.no_grad()
     def collect(self):
         """One horizon.  Row 0 of `obs` is the observation the previous horizon ended on."""
         for t in range(self.h):
             self.counter += 1
-            self.net.forward(self.obs[t], head_out=self.head[t],
-                             sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
+            self._forward(t, sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
             act = self.actions[t] if self.act_line is None else self.act_line.push(self.actions[t], self._done_prev, self.applied)
             if self.obs_line is None:
                 self.env.step(act, obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
@@ -107,13 +126,17 @@ class RolloutCollector:
                 self.serve.step(t, self.rewards[t], self.dones[t])
             if self.randomizer is not None:
                 self.randomizer.step(t, self.rewards[t], self.dones[t])
+            if self.critic_input is not None:
+                self.critic_input.gather(self.priv[t + 1])
             self._done_prev = self.dones[t]
             if self.on_step is not None:
                 self.on_step()
-        self.net.forward(self.obs[self.h], head_out=self.head[self.h])            # bootstrap value of the last observation
+        self._forward(self.h)                                                      # bootstrap value of the last observation
         gae(self.rewards, self.values, self.dones, self.gamma, self.tau, self.reward_scale, self.advantages, self.returns)
         return self
 
     def next_horizon(self):
         """Carry the last observation over as row 0 of the next horizon (one [N, num_obs] copy per horizon)."""
         self.obs[0].copy_(self.obs[self.h])
+        if self.priv is not None:
+            self.priv[0].copy_(self.priv[self.h])

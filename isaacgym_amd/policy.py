@@ -49,6 +49,15 @@ def prepare_input(out, obs, mean=None, inv_std=None, clip=5.0):
                                          out.data_ptr(), out.stride(0), _lib.stream(obs)))
 
 
+def prepare_critic_input(out, priv, col0, mean=None, inv_std=None, clip=5.0):
+    """pp_critic_input_prepare on torch tensors (include/ppenv_critic_input.h): priv fp32 [M, P] -> out[:, col0:col0 + P] fp16 normalised and
+    clamped as prepare_input does, out[:, col0 + P:] = 0; the columns below col0 stay.  The second half of a wide first-layer input:
+    prepare_input(out, obs, ...) runs first (it zeroes everything above its own columns)."""
+    L = _lib.lib()
+    _lib.check(L.pp_critic_input_prepare(priv.data_ptr(), priv.stride(0), priv.shape[0], priv.shape[1], _lib.ptr(mean), _lib.ptr(inv_std), clip,
+                                         out.data_ptr(), out.stride(0), int(col0), _lib.stream(priv)), L)
+
+
 def _descriptor(out, x, w, bias, elu, batch=1, in_stride=0, w_stride=0, bias_stride=0, out_stride=0, mean=None, inv_std=None, clip=5.0,
                 m=None, n=None, k=None):
     d = MLPLayer()
@@ -221,9 +230,16 @@ class RunningMeanStd(torch.nn.Module):
 
 class NativeMLP:
     """Actor + critic forward on the MFMA kernel.  `actor` / `critic`: lists of (weight [out, in], bias [out]) fp32 tensors, hidden
-    layers first, the head last (what `[m for m in net if isinstance(m, nn.Linear)]` yields for the reference's architecture)."""
+    layers first, the head last (what `[m for m in net if isinstance(m, nn.Linear)]` yields for the reference's architecture).
 
-    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, max_rows=None, fuse_input=False, cus=0):
+    num_priv = P > 0: an ASYMMETRIC critic (privileged critic inputs; include/ppenv_critic_input.h).  The critic's first layer
+    is [u0, num_obs + P], the actor's stays [u0, num_obs]; the first-layer operand rows are [obs | priv], num_obs + P columns padded to 64,
+    and in the stacked image w[0] the actor's columns num_obs .. are exactly zero, so mu is bitwise the mu of the narrow network (a product
+    with an exact zero adds exactly) and the two towers still run as one stacked GEMM.  `forward(obs, priv=...)` prepares the operand in
+    two launches (prepare_input, then prepare_critic_input); priv=None leaves the privileged columns zero (play: only mu is used).
+    num_priv = 0: every buffer shape and launch is the narrow network's."""
+
+    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, max_rows=None, fuse_input=False, cus=0, num_priv=0):
         """cus: the share of the chip's 256 CUs each layer launch is sized for (0 = all): 128 when two env groups' forwards run side by
         side on two streams (tools/gpu_rollout_pipeline.py); results do not depend on it.
         fuse_input: layer 1 reads the fp32 observations in place and normalises while staging (one launch fewer, but the
@@ -236,7 +252,14 @@ class NativeMLP:
         self.chain = tuple(int(x) for x in env_chain.split(",")) if env_chain else None
         self._chain_ws = None
         assert len(actor) == len(critic) and all(a[0].shape[0] == c[0].shape[0] for a, c in zip(actor[:-1], critic[:-1]))
-        self.num_obs, self.clip = int(num_obs), float(clip)
+        self.num_obs, self.clip, self.num_priv = int(num_obs), float(clip), int(num_priv)
+        if self.num_priv:
+            if not 0 < self.num_priv <= _lib.CRITIC_MAX_COLS or self.fuse_input:
+                raise ValueError(f"num_priv: {num_priv} privileged columns (0 .. {_lib.CRITIC_MAX_COLS}; not with fuse_input, whose layer 1 reads obs in place)")
+            if actor[0][0].shape[1] != self.num_obs or critic[0][0].shape[1] != self.num_obs + self.num_priv:
+                raise ValueError(f"num_priv {num_priv}: the actor's first layer must be [u0, {self.num_obs}] and the critic's [u0, {self.num_obs + self.num_priv}], "
+                                 f"not {tuple(actor[0][0].shape)} and {tuple(critic[0][0].shape)}")
+        self.priv_mean = self.priv_inv_std = None          # the privileged columns' statistics (set_priv_normalization_tensors); None: converted only
         self.units = [a[0].shape[0] for a in actor[:-1]]
         self.num_actions = actor[-1][0].shape[0]
         self.load(actor, critic)
@@ -259,10 +282,10 @@ class NativeMLP:
         """fp32 master weights -> the fp16 operand images (actor | critic stacked per layer)."""
         h = lambda t: t.detach().to(self.device, torch.float16).contiguous()
 
-        def hw(t):   # weight rows zero-padded to a multiple of 64 fp16 (one K tile): every row starts 16-byte aligned and layer 1
+        def hw(t, wide=0):   # weight rows zero-padded to a multiple of 64 fp16 (one K tile): every row starts 16-byte aligned and layer 1
             t = h(t)   # qualifies for the LDS-DMA kernels (num_obs = 313 gives 626-byte rows; unpadded, it fell back to element loads)
             k = t.shape[1]
-            kp = (k + 63) // 64 * 64
+            kp = (max(k, wide) + 63) // 64 * 64        # wide: the critic's layer-1 width, which the actor's image is zero-padded to (num_priv)
             if kp == k:
                 return t
             out = torch.zeros((t.shape[0], kp), dtype=torch.float16, device=self.device)
@@ -270,7 +293,7 @@ class NativeMLP:
             return out
         self.w, self.b = [], []
         for (wa, ba), (wc, bc) in zip(actor[:-1], critic[:-1]):
-            self.w.append(torch.stack([hw(wa), hw(wc)]).contiguous())     # [2, n, k (padded)]
+            self.w.append(torch.stack([hw(wa, wc.shape[1]), hw(wc)]).contiguous())     # [2, n, k (padded)]
             self.b.append(torch.stack([h(ba), h(bc)]).contiguous())       # [2, n]
         # the two heads as ONE block-diagonal layer over the stacked features [actor | critic]: rows 0 .. A-1 read the actor half, row A the critic half
         ul, na = self.units[-1], actor[-1][0].shape[0]
@@ -293,6 +316,22 @@ class NativeMLP:
         assert mean.dtype == inv_std.dtype == torch.float32 and mean.device == self.device and mean.numel() == inv_std.numel() == self.num_obs
         self.mean, self.inv_std = mean, inv_std
 
+    def set_priv_normalization_tensors(self, mean, inv_std):
+        """The caller's fp32 [num_priv] statistics of the privileged columns, read in place like set_normalization_tensors' (a second
+        RunningMeanStd); both None: the columns are only converted to fp16."""
+        if mean is not None:
+            assert mean.dtype == inv_std.dtype == torch.float32 and mean.device == self.device and mean.numel() == inv_std.numel() == self.num_priv
+        self.priv_mean, self.priv_inv_std = mean, inv_std
+
+    def _prepare(self, obs, priv):
+        """The first-layer operand rows from obs (and priv): the one launch of the narrow network, or the two of a wide one."""
+        prepare_input(self.x16, obs, self.mean, self.inv_std, self.clip)                   # zeroes every column above num_obs
+        if priv is not None:
+            if not self.num_priv:
+                raise ValueError("forward(priv=...): this network has no privileged columns (num_priv=0)")
+            assert priv.dtype == torch.float32 and priv.device == self.device and priv.stride(1) == 1 and tuple(priv.shape) == (obs.shape[0], self.num_priv)
+            prepare_critic_input(self.x16, priv, self.num_obs, self.priv_mean, self.priv_inv_std, self.clip)
+
     def _alloc(self, m):
         z = lambda n, dt: torch.empty((m, n), dtype=dt, device=self.device)
         self.h = [z(2 * u, torch.float16) for u in self.units]            # actor columns first, critic after
@@ -305,14 +344,15 @@ class NativeMLP:
         """Let the env's step kernel write this network's first-layer input (normalised, clamped, padded fp16 rows) next to obs_buf:
         `forward(obs, prepared=True)` then skips the normalise-and-pad launch.  Needs an env with `set_policy_input` (TAEnv on the
         chain-wave kernel) and statistics (`set_normalization`); the statistics tensors are read by every later step."""
-        assert not self.fuse_input and self.mean is not None
+        assert not self.fuse_input and self.mean is not None and not self.num_priv      # (the step kernel writes num_obs columns and pads the rest)
         if env.num_envs != self._rows:
             self._alloc(env.num_envs)
         env.set_policy_input(self.x16, self.mean, self.inv_std, self.clip)
         prepare_input(self.x16, env.obs_buf, self.mean, self.inv_std, self.clip)    # the rows of the CURRENT obs_buf: the first forward runs before any step has written them
 
-    def forward(self, obs, prepared=False, sample=None, head_out=None):
+    def forward(self, obs, prepared=False, sample=None, head_out=None, priv=None):
         """obs: fp32 [M, num_obs] on this device (the env's obs_buf, read in place) -> (mu [M, A], value [M, 1]) fp32 (buffers reused).
+        priv: fp32 [M, num_priv] (any row stride), the privileged rows of a num_priv > 0 network; None there: the columns are zero.
         prepared: the first-layer input is already in self.x16 (attach_env: written by the env's step kernel).
         sample: dict(actions=[M, A] fp32, sigma=[A], seed=, counter=, lo=-1, hi=1, neglogp=[M] or None) — the heads launch also draws the
         actions (ppenv_mlp_heads_sample): one launch fewer than forward + sample_actions, the same numbers.
@@ -330,7 +370,7 @@ class NativeMLP:
             layer_forward(self.h[0], obs, w0, self.b[0].view(-1), elu=True, cus=self.cus, mean=self.mean, inv_std=self.inv_std, clip=self.clip, k=self.num_obs)
         else:
             if not prepared:
-                prepare_input(self.x16, obs, self.mean, self.inv_std, self.clip)
+                self._prepare(obs, priv)
             layer_forward(self.h[0], self.x16, w0, self.b[0].view(-1), elu=True, cus=self.cus)
         hidden = lambda i: dict(out=self.h[i], x=self.h[i - 1], w=self.w[i], bias=self.b[i], elu=True, batch=2, in_stride=u[i - 1], w_stride=u[i] * self.w[i].shape[-1],
                                 bias_stride=u[i], out_stride=u[i], m=m, n=u[i], k=u[i - 1])
@@ -400,13 +440,22 @@ class NativeMLPLearner:
     ([M, A + 1] fp32, already multiplied by the loss scale if one is used) and fills `grads` — fp32 tensors of the parameters' shapes.
     An optimizer (rl_games: Adam) steps on `parameters()` / `grads` and calls `sync_weights()`; that part stays PyTorch."""
 
-    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, head_grad_extra=0):
+    def __init__(self, actor, critic, num_obs, device, mean=None, var=None, eps=1e-5, clip=5.0, head_grad_extra=0, num_priv=0):
         """head_grad_extra: fp32 slots right after the heads' bias gradient, `grad_extra` (a caller's gradient, e.g. the log-std's, that then
-        travels in the heads' all-reduce: each layer's gradients — and the heads' with these slots — are ONE contiguous buffer, one collective)."""
-        self.net = NativeMLP(actor, critic, num_obs, device, mean=mean, var=var, eps=eps, clip=clip)
+        travels in the heads' all-reduce: each layer's gradients — and the heads' with these slots — are ONE contiguous buffer, one collective).
+        num_priv = P > 0 (NativeMLP): w32[0] is [2, u0, num_obs + P] with the actor's columns num_obs .. exactly zero.  parameters() / gradients()
+        then expose layer 1 as TWO tensors, the actor's column view [:, :num_obs] and the critic's [:, :num_obs + P], so no optimizer, gradient
+        norm or moment ever sees the actor's privileged columns and they stay zero; the weight-gradient launch writes what it computes there
+        and nothing reads it."""
+        self.net = NativeMLP(actor, critic, num_obs, device, mean=mean, var=var, eps=eps, clip=clip, num_priv=num_priv)
         self.device = self.net.device
+        self.num_priv = self.net.num_priv
         f = lambda t: t.detach().to(self.device, torch.float32).contiguous()
-        self.w32 = [torch.stack([f(wa), f(wc)]).contiguous() for (wa, _), (wc, _) in zip(actor[:-1], critic[:-1])]
+
+        def fw(t, wide):                                                   # the actor's layer-1 master zero-padded to the critic's width
+            t = f(t)
+            return t if t.shape[1] == wide else torch.cat([t, torch.zeros((t.shape[0], wide - t.shape[1]), dtype=torch.float32, device=self.device)], 1)
+        self.w32 = [torch.stack([fw(wa, wc.shape[1]), f(wc)]).contiguous() for (wa, _), (wc, _) in zip(actor[:-1], critic[:-1])]
         self.b32 = [torch.stack([f(ba), f(bc)]).contiguous() for (_, ba), (_, bc) in zip(actor[:-1], critic[:-1])]
         self.mu_w, self.mu_b, self.value_w, self.value_b = f(actor[-1][0]), f(actor[-1][1]), f(critic[-1][0]), f(critic[-1][1])
         u, na, net = self.net.units, self.net.num_actions, self.net
@@ -429,19 +478,36 @@ class NativeMLPLearner:
         head_w, head_b, self.grad_extra = flat((self.nh, 2 * u[-1]), (na + 1,), (int(head_grad_extra),))
         self.grads = dict(w=[w for w, _ in layers], b=[b for _, b in layers], head_w=head_w, head_b=head_b)
         self._rows = 0
-        self.rms = None
+        self.rms = self.priv_rms = None
         self._cast_items = None
         self.generation = 0                 # forward passes so far: backward() differentiates the LAST one (the activation buffers are shared)
         self.sync_weights()
 
+    def layer_weights(self, i):
+        """(actor, critic) fp32 master weights of hidden layer i as every caller sees them: layer 1 of a num_priv > 0 network is the actor's
+        column view [u0, num_obs] and the critic's [u0, num_obs + P]."""
+        w = self.w32[i]
+        return (w[0][:, :self.net.num_obs], w[1]) if i == 0 and self.num_priv else (w[0], w[1])
+
+    def weight_parameters(self):
+        """The hidden layers' weights as the optimizer sees them: the stacked masters, layer 1 of a num_priv > 0 network as its two views."""
+        return (list(self.layer_weights(0)) + self.w32[1:]) if self.num_priv else list(self.w32)
+
     def parameters(self):
+        return self.weight_parameters() + self.b32 + [self.mu_w, self.mu_b, self.value_w, self.value_b]
+
+    def masters(self):
+        """The contiguous fp32 master tensors themselves (what a collective can work on in place): parameters(), except that layer 1 of a
+        num_priv > 0 network is the one stacked tensor, the actor's zero columns included."""
         return self.w32 + self.b32 + [self.mu_w, self.mu_b, self.value_w, self.value_b]
 
     def gradients(self):
         """Gradients in the order and shapes of parameters() (views of `grads`; layer 1's weight gradient without its K padding)."""
         g, u, na = self.grads, self.net.units, self.net.num_actions
-        return ([g["w"][i][..., :self.w32[i].shape[-1]] for i in range(len(u))] + g["b"] +
-                [g["head_w"][:na, :u[-1]], g["head_b"][:na], g["head_w"][na:na + 1, u[-1]:], g["head_b"][na:]])
+        w = [g["w"][i][..., :self.w32[i].shape[-1]] for i in range(len(u))]
+        if self.num_priv:
+            w = [g["w"][0][0][:, :self.net.num_obs], g["w"][0][1][:, :self.w32[0].shape[-1]]] + w[1:]
+        return (w + g["b"] + [g["head_w"][:na, :u[-1]], g["head_b"][:na], g["head_w"][na:na + 1, u[-1]:], g["head_b"][na:]])
 
     def sync_weights(self):
         """fp32 masters -> the fp16 operand images of the forward (w, zero-padded rows) and of dX (wt, transposed), and the fp16 biases: ONE launch for the
@@ -479,11 +545,21 @@ class NativeMLPLearner:
         self.rms = rms
         self.net.set_normalization_tensors(rms.mean, rms.inv_std)
 
-    def forward(self, obs, update_stats=False):
+    def attach_priv_running_mean_std(self, rms):
+        """The same for the privileged columns of a num_priv > 0 network: a second RunningMeanStd of width num_priv, updated by the same
+        kernel under the same rule."""
+        assert self.num_priv and rms.num_obs == self.num_priv
+        self.priv_rms = rms
+        self.net.set_priv_normalization_tensors(rms.mean, rms.inv_std)
+
+    def forward(self, obs, priv=None, update_stats=False):
+        """priv: the privileged rows [M, num_priv] of a num_priv > 0 network (None: zero columns)."""
         if update_stats:
             self.rms.update(obs)
+            if priv is not None and self.priv_rms is not None:
+                self.priv_rms.update(priv)
         self.generation += 1
-        return self.net.forward(obs)
+        return self.net.forward(obs, priv=priv)
 
     def backward(self, d_head, accumulate=False, on_grads=None, generation=None):
         """d_head [M, A + 1] fp32 = d loss / d [mu | value] of the rows of the last forward (M a multiple of 64).
@@ -532,8 +608,8 @@ class _ActorCriticFn(torch.autograd.Function):
     """autograd edge of NativeActorCritic: forward = NativeMLPLearner.forward, backward = NativeMLPLearner.backward."""
 
     @staticmethod
-    def forward(ctx, module, obs, *params):          # params: only so that autograd routes their gradients here
-        mu, value = module.learner.forward(obs, update_stats=module.training and module.learner.rms is not None)
+    def forward(ctx, module, obs, priv, *params):    # params: only so that autograd routes their gradients here
+        mu, value = module.learner.forward(obs, priv, update_stats=module.training and module.learner.rms is not None)
         ctx.module = module
         ctx.generation = module.learner.generation   # the activation buffers are the learner's own: backward checks nobody forwarded since
         return mu.clone(), value.clone()             # the network's own buffers are reused by the next forward
@@ -551,7 +627,7 @@ class _ActorCriticFn(torch.autograd.Function):
         grads = lr.backward(d_head, on_grads=sync, generation=ctx.generation)
         if sync is not None:
             sync.wait()                              # the clones below are ordered after the collectives
-        return (None, None) + tuple(g.clone() for g in grads)
+        return (None, None, None) + tuple(g.clone() for g in grads)
 
 
 class NativeActorCritic(torch.nn.Module):
@@ -561,20 +637,26 @@ class NativeActorCritic(torch.nn.Module):
     NativeMLPLearner.backward: a GradScaler's scaled loss gives scaled gradients, `unscale_` works as on any fp32 gradient), any torch
     optimizer steps them, and the next forward recasts the fp16 operand images when a parameter has changed.  Parameters are the stacked
     masters of NativeMLPLearner (`hidden_w.i` [2, n, k] = actor | critic, `hidden_b.i`, `mu_w`, `mu_b`, `value_w`, `value_b`); `from_rlgames`
-    builds one from an rl_games state dict.  The minibatch must be a multiple of 64 rows (the weight-gradient kernel's contraction tile)."""
+    builds one from an rl_games state dict.  The minibatch must be a multiple of 64 rows (the weight-gradient kernel's contraction tile).
+    num_priv = P > 0: an asymmetric critic (NativeMLP / NativeMLPLearner): `mu, value = net(obs, priv)`; `hidden_w` then begins with layer
+    1's TWO parameters, the actor's [u0, num_obs] and the critic's [u0, num_obs + P] (views of one stacked master), followed by the stacked
+    layers 2 ..; with normalize_input the privileged columns get statistics of their own, the submodule `critic_mean_std`."""
 
-    def __init__(self, actor, critic, num_obs, device, normalize_input=True, eps=1e-5, clip=5.0, head_grad_extra=0):
+    def __init__(self, actor, critic, num_obs, device, normalize_input=True, eps=1e-5, clip=5.0, head_grad_extra=0, num_priv=0):
         super().__init__()
-        self.learner = NativeMLPLearner(actor, critic, num_obs, device, eps=eps, clip=clip, head_grad_extra=head_grad_extra)
+        self.learner = NativeMLPLearner(actor, critic, num_obs, device, eps=eps, clip=clip, head_grad_extra=head_grad_extra, num_priv=num_priv)
         self.learner.rms = None
         if normalize_input:
             # a SUBMODULE under rl_games' own name: state_dict() / load_state_dict() carry `running_mean_std.running_mean | running_var | count`
             # (the statistics are part of a trained policy: without them a restored network would normalise with mean 0 / var 1)
             self.running_mean_std = RunningMeanStd(num_obs, device, eps=eps)
             self.learner.attach_running_mean_std(self.running_mean_std)
+            if self.learner.num_priv:
+                self.critic_mean_std = RunningMeanStd(self.learner.num_priv, device, eps=eps)
+                self.learner.attach_priv_running_mean_std(self.critic_mean_std)
         lr = self.learner
         P = torch.nn.Parameter
-        self.hidden_w = torch.nn.ParameterList([P(w) for w in lr.w32])       # the same storage as the learner's masters
+        self.hidden_w = torch.nn.ParameterList([P(w) for w in lr.weight_parameters()])       # the same storage as the learner's masters
         self.hidden_b = torch.nn.ParameterList([P(b) for b in lr.b32])
         self.mu_w, self.mu_b, self.value_w, self.value_b = P(lr.mu_w), P(lr.mu_b), P(lr.value_w), P(lr.value_b)
         self.sigma = P(torch.zeros(lr.net.num_actions, device=lr.device), requires_grad=False)   # fixed_sigma: log-std, const 0 (yaml:21-27)
@@ -584,14 +666,15 @@ class NativeActorCritic(torch.nn.Module):
     @classmethod
     def from_rlgames(cls, state_dict, device, **kw):
         actor, critic = layers_from_rlgames_state_dict(state_dict)
-        net = cls(actor, critic, actor[0][0].shape[1], device, normalize_input="running_mean_std.running_mean" in state_dict, **kw)
-        if net.learner.rms is not None:
-            rms = net.learner.rms
-            with torch.no_grad():
-                rms.running_mean.copy_(state_dict["running_mean_std.running_mean"])
-                rms.running_var.copy_(state_dict["running_mean_std.running_var"])
-                rms.count.copy_(state_dict["running_mean_std.count"])
-            rms.refresh()
+        net = cls(actor, critic, actor[0][0].shape[1], device, normalize_input="running_mean_std.running_mean" in state_dict,
+                  num_priv=critic[0][0].shape[1] - actor[0][0].shape[1], **kw)
+        for rms, prefix in ((net.learner.rms, "running_mean_std"), (net.learner.priv_rms, "critic_mean_std")):
+            if rms is not None and f"{prefix}.running_mean" in state_dict:
+                with torch.no_grad():
+                    rms.running_mean.copy_(state_dict[f"{prefix}.running_mean"])
+                    rms.running_var.copy_(state_dict[f"{prefix}.running_var"])
+                    rms.count.copy_(state_dict[f"{prefix}.count"])
+                rms.refresh()
         if "a2c_network.sigma" in state_dict:
             net.sigma.data.copy_(state_dict["a2c_network.sigma"])
         return net
@@ -602,10 +685,10 @@ class NativeActorCritic(torch.nn.Module):
         `running_mean_std.{running_mean,running_var,count}`), so that a policy trained here plays under rl_games' player or
         RLGamesPolicy.  Detached clones on the module's device.  (`value_mean_std.*` — normalize_value — belongs to the agent, not to
         this network; rl_games is absent offline: the layout is its published one, not pinned to a file.)"""
-        lr = self.learner
-        actor = [(self.hidden_w[i][0], self.hidden_b[i][0]) for i in range(len(lr.net.units))] + [(self.mu_w, self.mu_b)]
-        critic = [(self.hidden_w[i][1], self.hidden_b[i][1]) for i in range(len(lr.net.units))] + [(self.value_w, self.value_b)]
-        return rlgames_state_dict_from_layers(actor, critic, sigma=self.sigma, rms=lr.rms)
+        lr = self.learner                               # (the parameters are the learner's masters: the same storage)
+        actor = [(lr.layer_weights(i)[0], self.hidden_b[i][0]) for i in range(len(lr.net.units))] + [(self.mu_w, self.mu_b)]
+        critic = [(lr.layer_weights(i)[1], self.hidden_b[i][1]) for i in range(len(lr.net.units))] + [(self.value_w, self.value_b)]
+        return rlgames_state_dict_from_layers(actor, critic, sigma=self.sigma, rms=lr.rms, priv_rms=lr.priv_rms)
 
     def _ordered(self):
         return list(self.hidden_w) + list(self.hidden_b) + [self.mu_w, self.mu_b, self.value_w, self.value_b]
@@ -613,14 +696,14 @@ class NativeActorCritic(torch.nn.Module):
     def _versions(self):
         return tuple(p._version for p in self._ordered())
 
-    def forward(self, obs):
+    def forward(self, obs, priv=None):
         if obs.shape[0] % 64:
             raise ValueError(f"NativeActorCritic: {obs.shape[0]} rows; the minibatch must be a multiple of 64")
         v = self._versions()
         if v != self._seen:                          # an optimizer stepped (or a state dict was loaded): recast the operand images
             self.learner.sync_weights()
             self._seen = v
-        return _ActorCriticFn.apply(self, obs, *self._ordered())
+        return _ActorCriticFn.apply(self, obs, priv, *self._ordered())
 
 
 # ---- a trained rl_games checkpoint on the native forward (the reference's `train.py test=True checkpoint=...` play mode) ---------------
@@ -631,7 +714,8 @@ def layers_from_rlgames_state_dict(sd):
     """rl_games' a2c_continuous(_logstd) model state_dict (what `torch.load(ckpt)["model"]` holds for the reference's network:
     `separate: True`, cfg/train/HumanoidPingpongTiltG1PPO.yaml:10-31) -> (actor, critic) lists of (weight, bias), head last.
     Keys: a2c_network.{actor,critic}_mlp.<even index>.{weight,bias} (nn.Sequential of Linear / activation), a2c_network.mu.*,
-    a2c_network.value.*."""
+    a2c_network.value.*.  The critic's first layer may be WIDER than the actor's (a checkpoint trained with privileged critic inputs,
+    PPOTrainer(critic_inputs=)): the difference is the network's num_priv.  A wider actor is a ValueError."""
     import re
 
     def mlp(which):
@@ -641,12 +725,16 @@ def layers_from_rlgames_state_dict(sd):
         return [(sd[f"a2c_network.{which}_mlp.{i}.weight"], sd[f"a2c_network.{which}_mlp.{i}.bias"]) for i in idx]
     actor = mlp("actor") + [(sd["a2c_network.mu.weight"], sd["a2c_network.mu.bias"])]
     critic = mlp("critic") + [(sd["a2c_network.value.weight"], sd["a2c_network.value.bias"])]
+    if actor[0][0].shape[1] > critic[0][0].shape[1]:
+        raise ValueError(f"a2c_network.actor_mlp.0.weight has {actor[0][0].shape[1]} input columns, a2c_network.critic_mlp.0.weight {critic[0][0].shape[1]}: "
+                         "only the critic's first layer may be the wider one (privileged critic inputs)")
     return actor, critic
 
 
-def rlgames_state_dict_from_layers(actor, critic, sigma=None, rms=None):
+def rlgames_state_dict_from_layers(actor, critic, sigma=None, rms=None, priv_rms=None):
     """The inverse of layers_from_rlgames_state_dict: (weight, bias) lists, head last -> rl_games' keys (hidden layer i sits at index 2 i of
-    its nn.Sequential: Linear, activation, Linear, ...), plus `a2c_network.sigma` and `running_mean_std.*` when given.  Detached clones."""
+    its nn.Sequential: Linear, activation, Linear, ...), plus `a2c_network.sigma` and `running_mean_std.*` when given, and `critic_mean_std.*`
+    (the privileged columns' statistics; this project's key, rl_games has none).  Detached clones."""
     c = lambda t: t.detach().clone()
     sd = {}
     for which, layers, head in (("actor", actor, "mu"), ("critic", critic, "value")):
@@ -655,9 +743,10 @@ def rlgames_state_dict_from_layers(actor, critic, sigma=None, rms=None):
         sd[f"a2c_network.{head}.weight"], sd[f"a2c_network.{head}.bias"] = c(layers[-1][0]), c(layers[-1][1])
     if sigma is not None:
         sd["a2c_network.sigma"] = c(sigma)
-    if rms is not None:
-        for k in ("running_mean", "running_var", "count"):
-            sd[f"running_mean_std.{k}"] = c(getattr(rms, k))
+    for prefix, r in (("running_mean_std", rms), ("critic_mean_std", priv_rms)):
+        if r is not None:
+            for k in ("running_mean", "running_var", "count"):
+                sd[f"{prefix}.{k}"] = c(getattr(r, k))
     return sd
 
 
@@ -674,7 +763,10 @@ class RLGamesPolicy:
         mean, var = sd.get("running_mean_std.running_mean"), sd.get("running_mean_std.running_var")
         if mean is None:                                       # normalize_input: False
             mean, var = torch.zeros(num_obs), torch.ones(num_obs) - eps
-        self.net = NativeMLP(actor, critic, num_obs, device, mean=mean.float(), var=var.float(), eps=eps, max_rows=max_rows)
+        # a checkpoint trained with privileged critic inputs: the critic's first layer is wider.  Nothing privileged exists at play time, so
+        # those columns are held at zero: mu is the trained actor's, bit for bit; the VALUES are then meaningless (the critic never saw zeros there)
+        self.num_priv = critic[0][0].shape[1] - num_obs
+        self.net = NativeMLP(actor, critic, num_obs, device, mean=mean.float(), var=var.float(), eps=eps, max_rows=max_rows, num_priv=self.num_priv)
         self.device = self.net.device
         self.sigma = torch.exp(sd["a2c_network.sigma"].detach().float()).to(self.device).contiguous()
         vm, vv = sd.get("value_mean_std.running_mean"), sd.get("value_mean_std.running_var")
@@ -691,7 +783,9 @@ class RLGamesPolicy:
 
     def act(self, obs, deterministic=True, seed=0):
         """obs [M, num_obs] fp32 on the device -> (actions [M, A] in [-1, 1], value [M, 1] de-normalised).  seed: the user's; the draws are
-        keyed by its sampler stream (sampler_stream_seed), never by the seed itself — the task played with the same seed shares no draw with it."""
+        keyed by its sampler stream (sampler_stream_seed), never by the seed itself — the task played with the same seed shares no draw with it.
+        With num_priv > 0 (a checkpoint with a wider critic) the actions are the trained actor's and the values are MEANINGLESS: the
+        privileged columns are held at zero."""
         m = obs.shape[0]
         if self._actions is None or self._actions.shape[0] != m:
             self._actions = torch.empty(m, self.net.num_actions, device=self.device)

@@ -27,6 +27,9 @@ Deviations from rl_games:
   - `value_bootstrap` is a no-op here: `time_outs` is identically false for these tasks (vec_task.py, step), so there is nothing to add
     to the rewards.
   - The minibatches are the contiguous row ranges of the horizon-major buffers, in order.
+  - Privileged critic inputs (critic_inputs=, below) are this project's own specification.  rl_games' central value
+    (`central_value_config`) is a SEPARATE network with its own optimizer, statistics and minibatches, fed VecTask's `states`; here the
+    critic tower of the one network reads extra first-layer columns, and loss, optimizer, schedule and minibatches are the ones above.
 
 Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
 They also carry "meter" (the score meter's struct), "last_mean_rewards" (the best score so far) and "latency" (the two delay ranges the
@@ -40,6 +43,14 @@ DESIGN §5d "Training under latency").  Off by default, and then nothing is buil
 Domain randomisation (PPOTrainer(randomization=, adr=), --randomize / --adr TABLE=...): a reset-time plan (include/ppenv_dr.h) or automatic
 domain randomisation, a device-resident curriculum over the tables' ranges (adr.AutoRandomizer; include/ppenv_dr_adr.h), run from the
 collector's per-step hook (DESIGN §5d "Randomisation and ADR in training").  Off by default, and then nothing is built.
+
+Privileged critic inputs (PPOTrainer(critic_inputs=("tables", "latency", "raw_obs")), --critic-inputs tables,latency,raw_obs): an asymmetric
+actor-critic.  The named quantities — the env's randomisation tables, its delays, its undelayed observation — are gathered per control step
+into `col.priv` (critic_input.CriticInput; include/ppenv_critic_input.h) and feed first-layer columns that only the critic's weights read;
+the actor's weights over them are exactly zero and never reach the optimizer (policy.NativeMLP(num_priv=); DESIGN §5d "Privileged critic
+inputs").  The columns have running statistics of their own (`critic_mean_std.*` in the checkpoint's model), updated under the rule of the
+observation statistics.  Checkpoints carry the record under "critic_inputs" (names, columns per name, P); load() refuses a file whose P or
+names differ.  RLGamesPolicy serves such a checkpoint's actor as it stands.  Off by default, and then nothing is built.
 
 The score (GameMeter; C ABI: include/ppenv_ppo_meter.h) is rl_games' game_rewards / game_lengths: AverageMeter(games_to_track) over the
 finished games' unscaled returns (agent 0's row of each env) and lengths, updated once per epoch over the collector's horizon by two
@@ -451,11 +462,19 @@ class PPOTrainer:
     is fixed-range randomisation by the same kernel: the control run.  Checkpoints carry the plan under "randomization" and the
     randomizer's dims, parameters, ranges and per-slot state under "adr"; load() restores the latter and raises ValueError on other dims.
     Both arguments together are a ValueError; a task that arrives with randomize: True is refused as before; with neither, nothing is
-    allocated or launched.  clear_randomization() drops both."""
+    allocated or launched.  clear_randomization() drops both.
+    critic_inputs: a tuple of critic_input.NAMES ("tables", "latency", "raw_obs"), or the CLI's comma-separated text — privileged critic
+    inputs (the module docstring; this build's own rule).  `tables` needs randomization= or adr=, `latency` a delay above 0, `raw_obs` an
+    obs_delay above 0: otherwise a ValueError naming the argument.  The network is then built with num_priv = P, the collector keeps
+    `col.priv` [H + 1, rows, P], minibatch_step() slices it like `obs` (prepare() reads neither), and data-parallel the privileged statistics are broadcast
+    with the others at the start.  critic_inputs() returns the record.  Empty (the default): the trainer is bitwise the trainer without the
+    argument and `col.priv` is None.  clear_randomization() leaves the tables' columns reading the dropped tensors as they last stood."""
 
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
-                 curriculum=None, randomization=None, adr=None):
+                 curriculum=None, randomization=None, adr=None, critic_inputs=()):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
+        from . import critic_input as critic_input_mod
+        critic_inputs = critic_input_mod.parse(critic_inputs)
         if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
         if randomization is not None and randomization is not False and adr is not None:
@@ -480,17 +499,6 @@ class PPOTrainer:
         self.multi = initialised and (dist.get_world_size(group) > 1 or bool(force))
         self.world = dist.get_world_size(group) if self.multi else 1
         self.rank = dist.get_rank(group) if self.multi else 0
-        with torch.random.fork_rng(devices=[]):
-            torch.manual_seed(self.seed)
-            actor, critic = self._mlp(self.num_actions), self._mlp(1)
-        # the log-std gradient in the slots right after the heads' gradients: one collective carries both
-        self.net = NativeActorCritic(actor, critic, self.num_obs, dev, normalize_input=cfg.normalize_input, head_grad_extra=self.num_actions)
-        self.learner = self.net.learner
-        with torch.no_grad():
-            self.net.sigma.fill_(cfg.sigma_init)
-        self.logstd = self.net.sigma.data                                   # a2c_network.sigma of the checkpoint
-        self.value_rms = RunningMeanStd(1, dev) if cfg.normalize_value else None
-        self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
         H, n, mb = cfg.horizon_length, self.rows, cfg.minibatch_size
         self.curriculum = None
         serve_seed = scene.stream_seed(self.seed, scene.STREAM_SERVES)
@@ -512,11 +520,32 @@ class PPOTrainer:
             from .adr import AutoRandomizer
             self.adr = AutoRandomizer(env, **dict(adr), seed=tables_seed, horizon=H)
         randomizer = self.adr if self.adr is not None else (env.reset_randomization if self.randomization is not None else None)
+        # privileged critic inputs: their width sizes the critic's first layer, so it is resolved — with every refusal — before the network is built
+        self._critic_inputs = None
+        if critic_inputs:
+            tabs = env.dr_tables
+            self._critic_inputs = critic_input_mod.columns(critic_inputs, env.DR_TABLE_ROWS, None if tabs is None else
+                                                           [k for k, t in zip(env.DR_TABLE_ROWS, tabs) if t is not None],
+                                                           delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay), self.num_obs)
+        P = self._critic_inputs["P"] if self._critic_inputs else 0
+        with torch.random.fork_rng(devices=[]):
+            torch.manual_seed(self.seed)
+            actor, critic = self._mlp(self.num_actions), self._mlp(1, self.num_obs + P)
+        # the log-std gradient in the slots right after the heads' gradients: one collective carries both
+        self.net = NativeActorCritic(actor, critic, self.num_obs, dev, normalize_input=cfg.normalize_input, head_grad_extra=self.num_actions, num_priv=P)
+        self.learner = self.net.learner
+        with torch.no_grad():
+            self.net.sigma.fill_(cfg.sigma_init)
+        self.logstd = self.net.sigma.data                                   # a2c_network.sigma of the checkpoint
+        self.value_rms = RunningMeanStd(1, dev) if cfg.normalize_value else None
+        self.roll_net = self.learner.net.sibling()                          # the rollout's activation buffers apart from the minibatch's
         self.col = RolloutCollector(env, self.roll_net, horizon=H, gamma=cfg.gamma, tau=cfg.tau, reward_scale=cfg.reward_scale,
                                     sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
                                     action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
                                     env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan,
-                                    randomizer=randomizer)
+                                    randomizer=randomizer, critic_input=critic_inputs or None)
+        if self._critic_inputs is not None:
+            assert self.col.critic_input.record() == self._critic_inputs
         self.g_logstd = self.learner.grad_extra
         self.loss = LossGrad(self.num_actions, mb, dev, cfg, d_logstd=self.g_logstd)
         self.opt = DeviceAdam(self.learner.parameters() + [self.logstd], self.learner.gradients() + [self.g_logstd], cfg.learning_rate,
@@ -543,8 +572,8 @@ class PPOTrainer:
         """Rank 0's fp32 parameters, log-std and input / value statistics (running and the fp32 images the kernels read) to every rank."""
         dist = torch.distributed
         src = dist.get_global_rank(self.group, 0) if self.group is not None else 0
-        tensors = self.learner.parameters() + [self.logstd]
-        for rms in (self.learner.rms, self.value_rms):
+        tensors = self.learner.masters() + [self.logstd]                    # (parameters(), with an asymmetric critic's layer 1 as its one contiguous tensor)
+        for rms in (self.learner.rms, self.value_rms, self.learner.priv_rms):
             if rms is not None:
                 tensors += [rms.running_mean, rms.running_var, rms.count, rms.mean, rms.inv_std]
         for t in tensors:
@@ -552,8 +581,8 @@ class PPOTrainer:
         self.learner.sync_weights()
         self.col.sigma.copy_(torch.exp(self.logstd))
 
-    def _mlp(self, n_out):
-        d, out = self.num_obs, []
+    def _mlp(self, n_out, num_in=None):
+        d, out = self.num_obs if num_in is None else num_in, []
         for u in list(self.cfg.units) + [n_out]:
             lin = torch.nn.Linear(d, u)
             out.append((lin.weight.detach(), lin.bias.detach()))
@@ -615,6 +644,11 @@ class PPOTrainer:
         t = a.table()
         return dict(adr_lo=t["lo"].clone(), adr_hi=t["hi"].clone(), adr_games=t["games"].clone(), adr_mean=t["mean"].clone())
 
+    def critic_inputs(self):
+        """The record of the privileged critic inputs — dict(names=[...], columns=[one count per name], P=the sum) — or None without any."""
+        r = self._critic_inputs
+        return None if r is None else dict(names=list(r["names"]), columns=[int(c) for c in r["columns"]], P=int(r["P"]))
+
     def latency(self):
         """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
         return dict(control_dt=self.env.control_dt, action_delay=list(self.col.action_delay), obs_delay=list(self.col.obs_delay))
@@ -662,7 +696,8 @@ class PPOTrainer:
         mb, total = cfg.minibatch_size, cfg.horizon_length * self.rows
         sl = slice(lo, lo + mb)
         obs = col.obs[:cfg.horizon_length].reshape(total, self.num_obs)[sl]
-        mu, value = self.learner.forward(obs, update_stats=cfg.normalize_input)
+        priv = None if col.priv is None else col.priv[:cfg.horizon_length].reshape(total, col.priv.shape[2])[sl]
+        mu, value = self.learner.forward(obs, priv, update_stats=cfg.normalize_input)
         old_mu = col.head[:cfg.horizon_length].reshape(total, A + 1)[sl, :A]
         d_head = self.loss(mu, value, col.actions.reshape(total, A)[sl], old_mu, col.sigma, self.old_nlp[sl], self.adv[sl], self.old_v[sl],
                            self.ret[sl], self.logstd, self.opt.scale, stats_row)
@@ -771,7 +806,8 @@ class PPOTrainer:
                 model[f"value_mean_std.{k}"] = getattr(self.value_rms, k).detach().clone()
         # the fp32 statistics the kernels read, as the update kernel left them (RunningMeanStd.refresh derives them from the fp64 running
         # statistics in torch and can differ in the last bit): a resumed run normalises exactly as the uninterrupted one
-        stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms))
+        stats = {f"{name}.{k}": getattr(rms, k).detach().clone() for name, rms in (("running_mean_std", self.learner.rms), ("value_mean_std", self.value_rms),
+                                                                                  ("critic_mean_std", self.learner.priv_rms))
                  if rms is not None for k in ("mean", "inv_std")}
         sd = {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
               "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards),
@@ -785,6 +821,8 @@ class PPOTrainer:
                                    "tables": {k: {f: (list(v) if isinstance(v, (tuple, list)) else v) for f, v in t.items()} for k, t in self.randomization["tables"].items()}}
         if self.adr is not None:
             sd["adr"] = self.adr.state_dict()
+        if self._critic_inputs is not None:
+            sd["critic_inputs"] = self.critic_inputs()
         return sd
 
     def save(self, path):
@@ -798,6 +836,8 @@ class PPOTrainer:
         """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame.
         Data-parallel: every rank loads the same file (rank 0's), so all resume identical, each with rank 0's input and value statistics."""
         ck = torch.load(path, map_location=self.device, weights_only=True)
+        from . import critic_input as critic_input_mod
+        critic_input_mod.check_record(ck.get("critic_inputs"), self._critic_inputs)   # first: other privileged columns raise before anything is overwritten
         if self.curriculum is not None and "curriculum" in ck:               # first: other bins raise before anything is overwritten.  A file without one: the table starts fresh
             self.curriculum.load_state_dict(ck["curriculum"])
         if self.adr is not None and "adr" in ck:                             # likewise: other dims raise before anything is overwritten
@@ -808,12 +848,12 @@ class PPOTrainer:
         with torch.no_grad():
             for i in range(len(lr.w32)):
                 for j, layers in enumerate((actor, critic)):
-                    lr.w32[i][j].copy_(layers[i][0])
+                    lr.layer_weights(i)[j].copy_(layers[i][0])              # (layer 1 of an asymmetric critic: the actor's column view)
                     lr.b32[i][j].copy_(layers[i][1])
             lr.mu_w.copy_(actor[-1][0]); lr.mu_b.copy_(actor[-1][1])
             lr.value_w.copy_(critic[-1][0]); lr.value_b.copy_(critic[-1][1])
             self.logstd.copy_(sd["a2c_network.sigma"])
-            for rms, prefix in ((lr.rms, "running_mean_std"), (self.value_rms, "value_mean_std")):
+            for rms, prefix in ((lr.rms, "running_mean_std"), (self.value_rms, "value_mean_std"), (lr.priv_rms, "critic_mean_std")):
                 if rms is not None:
                     for k in ("running_mean", "running_var", "count"):
                         getattr(rms, k).copy_(sd[f"{prefix}.{k}"])
@@ -1000,6 +1040,8 @@ def main(argv=None):
     ap.add_argument("--adr-high", type=float, default=None, help="a boundary whose games' mean return is at or above this moves outward")
     ap.add_argument("--adr-every", type=int, default=0, help="print ADR's range table every so many epochs (0: never)")
     ap.add_argument("--adr-out", default=None, help="a json file rewritten with the table at each print")
+    ap.add_argument("--critic-inputs", default="", metavar="NAME[,NAME...]", help="privileged critic inputs (an asymmetric actor-critic): tables (needs "
+                    "--randomize or --adr), latency (needs --action-delay or --obs-delay), raw_obs (needs --obs-delay); the critic alone sees them")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -1019,6 +1061,8 @@ def main(argv=None):
     action_delay, obs_delay = delay_range("--action-delay", args.action_delay), delay_range("--obs-delay", args.obs_delay)
     try:
         serve_plan, curriculum = serve_cell_parse(args.serve), None
+        from . import critic_input as critic_input_mod
+        critic_inputs = critic_input_mod.parse(args.critic_inputs)
         if args.curriculum:
             if serve_plan is not None:
                 raise ValueError("--serve together with --curriculum: a plan and a curriculum write the same serve override buffer")
@@ -1063,7 +1107,7 @@ def main(argv=None):
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay,
-                    serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr)
+                    serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr, critic_inputs=critic_inputs)
     if rank == 0 and tr.randomization is not None:
         print("reset-time randomisation: " + ", ".join(f"{k} {t['distribution']} {t['operation']} {t['range'][0]:g}..{t['range'][1]:g}"
                                                        for k, t in tr.randomization["tables"].items()), flush=True)
@@ -1076,6 +1120,8 @@ def main(argv=None):
         print(f"serve curriculum: {tr.curriculum.bins} bins, power {tr.curriculum.power}, mix {tr.curriculum.mix:g}, alpha {tr.curriculum.alpha:g}", flush=True)
     if rank == 0 and (action_delay[1] or obs_delay[1]):
         print(latency_text(tr.latency()), flush=True)
+    if rank == 0 and tr.critic_inputs() is not None:
+        print(critic_input_mod.text(tr.critic_inputs(), tr.num_obs), flush=True)
     if args.checkpoint:
         tr.load(args.checkpoint)                                   # every rank: the same file
         if rank == 0:
