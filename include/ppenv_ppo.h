@@ -10,7 +10,8 @@
  *   (the learner's backward)
  *   ppenv_ppo_grad_sumsq     per-workgroup partial sums of the squared, still scaled gradients of every tensor in a table
  *   ppenv_ppo_adam_step      every workgroup sums the partials in the same order; unscale, clip, Adam; a non-finite norm skips the step
- *                            (with ppenv_ppo_adam.world > 1: on the rank means of all-reduced gradient sums)
+ *                            (with ppenv_ppo_adam.world > 1: on the rank means of all-reduced gradient sums); the loss scale stays
+ *                            within bounds (ppenv_ppo_scaler, below)
  *
  * No float atomics anywhere: every sum has a fixed order, so results are bitwise reproducible run to run.  The loss scale and the
  * step count live in a ppenv_ppo_scaler on the device and are never read by the host: ppenv_ppo_adam_step reads `state_in` and writes
@@ -67,14 +68,27 @@ typedef struct ppenv_ppo_tensor {
     int32_t rows, cols, ld_p, ld_g;
 } ppenv_ppo_tensor;
 
-/* GradScaler's state (torch.cuda.amp.GradScaler: init_scale, growth_tracker) and the optimizer's step count */
+/* GradScaler's state (torch.cuda.amp.GradScaler: init_scale, growth_tracker) and the optimizer's step count.
+ *
+ * The scale is BOUNDED, a deliberate departure from torch's GradScaler, which bounds neither end (a long burst of overflowing steps halves
+ * torch's scale down to 0, and the first clean step after it divides by that 0):
+ *   - a dynamic scale (backoff_factor < 1) never leaves ppenv_ppo_adam_step below PPENV_PPO_SCALE_FLOOR, the scale a run without mixed
+ *     precision has throughout; below it a scale only shrinks the gradients ahead of their fp16 cast.  A state found below the floor (a
+ *     checkpoint of a run that had none) is lifted to it by its next update, skipped or clean; reserved[0] counts the updates the floor
+ *     changed;
+ *   - growth is withheld (growth_tracker still restarts) where scale x growth_factor is not finite;
+ *   - a step whose scale is not a normal positive number (0, a denormal, negative, NaN: nothing finite divides it out) is skipped like a step
+ *     with a non-finite norm, so finite gradients never put a non-finite value into a parameter or a moment.
+ * With a constant scale (factors 1.0) and at every scale in [1, 2^126] the arithmetic of a step is unchanged. */
+#define PPENV_PPO_SCALE_FLOOR 1.0f
+
 typedef struct ppenv_ppo_scaler {
     float scale;
     int32_t growth_tracker;    /* clean steps since the last change of the scale */
     int32_t step;              /* Adam steps taken (skipped steps do not count) */
-    int32_t skipped;           /* steps skipped for a non-finite gradient norm */
+    int32_t skipped;           /* steps skipped: a non-finite gradient norm, or a scale that cannot be divided out */
     float grad_norm;           /* the unscaled gradient norm of the last step (before the clip) */
-    int32_t reserved[3];
+    int32_t reserved[3];       /* [0]: updates in which the floor changed the scale; [1], [2]: 0 */
 } ppenv_ppo_scaler;
 
 typedef struct ppenv_ppo_adam {

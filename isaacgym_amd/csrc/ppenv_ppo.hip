@@ -11,8 +11,8 @@
 //     entropy  = sum_j 0.5 + 0.5 log(2 pi) + logstd_j
 //     loss     = mean(a_loss) + 0.5 critic_coef mean(c_loss) - entropy_coef entropy + bounds_loss_coef mean(b_loss)
 // Where torch.max meets a tie (ratio inside the clip range; |v - old_v| <= e) both branches carry the same gradient, so the branch
-// taken on `>=` is the derivative autograd gives.  The row's log-probability and ratio are formed in fp64 (nlp is a difference of sums
-// of about 30 in fp32 otherwise); everything written is fp32.
+// taken on `>=` is the derivative autograd gives.  The row's log-probability and ratio are formed in fp64, sigma included (nlp is a
+// difference of sums of about 30 in fp32 otherwise, of 1e4 and more once mu has run away from the actions); everything written is fp32.
 //
 // -ffinite-math-only is NOT in this unit's flags (isaacgym_amd/_lib.py): the optimizer's skip depends on seeing an inf / nan norm.
 #include <hip/hip_runtime.h>
@@ -32,6 +32,8 @@ constexpr int kLossThreads = 256;                 // 4 waves, one row per lane
 constexpr int kOptThreads = 256;
 constexpr int PS = PPENV_PPO_PARTIAL_STRIDE;
 constexpr double kHalfLog2Pi = 0.91893853320467274178;
+constexpr float kMinNormal = 0x1p-126f;           // the smallest scale whose reciprocal is finite whether or not denormals are flushed
+constexpr float kMaxFinite = 0x1.fffffep+127f;
 
 // ---- loss gradient: one lane per row, one partial row per workgroup -------------------------------------------------------------
 __global__ void __launch_bounds__(kLossThreads) ppo_loss_grad_kernel(ppenv_ppo_loss_args p) {
@@ -52,7 +54,9 @@ __global__ void __launch_bounds__(kLossThreads) ppo_loss_grad_kernel(ppenv_ppo_l
     for (int j = 0; j < A; ++j) {
         const float ls = p.logstd[j], sg = expf(ls), osg = p.old_sigma[j];
         const float m = mu[j];
-        const double z = ((double)act[j] - (double)m) / (double)sg;
+        // sigma in fp64 as well: with mu far from the actions z^2 reaches 1e4 and more, and the 1e-7 of an fp32 sigma then moves nlp by 1e-2,
+        // the ratio with it (tests/test_ppo_runaway_gpu.py)
+        const double z = ((double)act[j] - (double)m) / exp((double)ls);
         nlp += 0.5 * z * z + (double)ls;
         const float dm = omu[j] - m;
         kl += logf(osg / sg + 1e-5f) + (sg * sg + dm * dm) / (2.0f * (osg * osg + 1e-5f)) - 0.5f;
@@ -236,9 +240,12 @@ __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_t
     const double raw = block_sum(part, red);
     const double sumsq = mean ? raw / ((double)hp.world * (double)hp.world) : raw;
     const ppenv_ppo_scaler st = *state_in;
-    const bool finite = finite64(sumsq);
+    // The step is taken on a finite square sum AND a scale that can be divided out: a normal positive number (`>=` is false for a NaN).  At 0
+    // or a denormal — a state loaded from a run whose scale had no floor — the scaled gradients are all 0 or denormal, 1 / scale is inf
+    // (or the gradients are flushed), and g x gmul = 0 x inf would put a NaN into every parameter: skipped instead, and the scale lifted below.
+    const bool finite = finite64(sumsq) && st.scale >= kMinNormal;
     const double norm = sqrt(sumsq) / (double)st.scale;            // of the unscaled gradients
-    if (blockIdx.x == 0 && threadIdx.x == 0) {                   // GradScaler.update, into the OTHER buffer
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                   // GradScaler.update with the two bounds of include/ppenv_ppo.h, into the OTHER buffer
         ppenv_ppo_scaler nx = st;
         nx.grad_norm = (float)norm;
         if (!finite) {
@@ -249,9 +256,14 @@ __global__ void __launch_bounds__(kOptThreads) ppo_adam_kernel(const ppenv_ppo_t
             nx.step = st.step + 1;
             nx.growth_tracker = st.growth_tracker + 1;
             if (nx.growth_tracker >= hp.growth_interval) {
-                nx.scale = st.scale * hp.growth_factor;
+                const float grown = st.scale * hp.growth_factor;
+                if (fabsf(grown) <= kMaxFinite) nx.scale = grown;    // withheld where the product is inf: at inf every later step would be skipped
                 nx.growth_tracker = 0;
             }
+        }
+        if (hp.backoff_factor < 1.0f && !(nx.scale >= PPENV_PPO_SCALE_FLOOR)) {     // a dynamic scale: never below the floor (a NaN is lifted too)
+            nx.scale = PPENV_PPO_SCALE_FLOOR;
+            nx.reserved[0] = st.reserved[0] + 1;
         }
         *state_out = nx;
     }

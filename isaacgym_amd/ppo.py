@@ -18,7 +18,7 @@ Semantics.  The loss terms are restated from rl_games' published a2c_continuous 
 unpinned, the same status as tools/ppo_epoch_bench.py): the clipped surrogate, the clipped value loss, the soft bound loss at +-1.1, and
 loss = mean(a) + 0.5 critic_coef mean(c) - entropy_coef entropy + bounds_loss_coef mean(b).  The gradient-norm clip is
 clip_grad_norm_'s, the optimizer torch.optim.Adam's, the loss scale torch GradScaler's (init 65536, x0.5 and a skipped step on a
-non-finite gradient, x2 after 2000 clean steps).
+non-finite gradient, x2 after 2000 clean steps) — with two bounds GradScaler does not have: never below 1.0, never grown to inf (DeviceAdam).
 
 Deviations from rl_games:
   - rl_games stores the unclamped action draw; the collector stores the CLAMPED actions the env consumed.  The ratio is evaluated on the
@@ -284,6 +284,10 @@ class DeviceAdam:
     Two launches per step (ppenv_ppo_grad_sumsq, ppenv_ppo_adam_step).  `scale` is the device scalar the loss gradient multiplies by;
     the scaler state (include/ppenv_ppo.h ppenv_ppo_scaler) is double-buffered in `state` [2, 8] int32: the step reads row `cur`, writes
     row 1 - cur, and `cur` flips on the host (the host never reads the state).
+    The scale is bounded — a deliberate departure from torch's GradScaler, which bounds neither end (include/ppenv_ppo.h): with dynamic=True
+    it never leaves a step below 1.0 (the scale of dynamic=False; a state loaded from below, load_state_dict included, is lifted by its next
+    step), it does not grow where scale x 2 is not finite, and a step at a scale that is not a normal positive number is skipped, so finite
+    gradients never write a non-finite parameter.  fields()["floor_hits"] counts the steps in which the floor held the scale.
     world: data-parallel ranks.  Above 1, `grads` hold the all-reduced SUMS over the ranks (distributed.GradientBuckets(mean=False)) and the
     kernels step on their rank means fl(g / world); 0 or 1: one rank, bit-identical to the default."""
 
@@ -319,9 +323,10 @@ class DeviceAdam:
         return self.state[self.cur, 0:1].view(torch.float32)
 
     def fields(self):
-        """The current state as 0-dim device tensors: scale, growth_tracker, step, skipped, grad_norm."""
+        """The current state as 0-dim device tensors: scale, growth_tracker, step, skipped, grad_norm, floor_hits."""
         s = self.state[self.cur]
-        return dict(scale=s[0:1].view(torch.float32)[0], growth_tracker=s[1], step=s[2], skipped=s[3], grad_norm=s[4:5].view(torch.float32)[0])
+        return dict(scale=s[0:1].view(torch.float32)[0], growth_tracker=s[1], step=s[2], skipped=s[3], grad_norm=s[4:5].view(torch.float32)[0],
+                    floor_hits=s[5])
 
     def step(self):
         L = _lib.lib()

@@ -1,7 +1,7 @@
 """Plain fp64 restatements (numpy, loops where a loop is the plainest form) of what PPOTrainer does between the rollout and the loss kernel:
 the episode bookkeeping, GAE, the value de-normalisation and prepare().  Written from the rl_games formulas the trainer's docstrings name, not
 from the torch code; tests/test_ppo_bookkeeping_host.py checks them against independent formulations on the CPU, and the GPU tests use them
-as the reference."""
+as the reference.  At the end: the loss scale's rule in numpy float32 and the rows of a policy that has run away (tests/test_ppo_runaway_*.py)."""
 import math
 
 import numpy as np
@@ -136,3 +136,157 @@ def nlp_bound(ref, A):
     """(A + 4) u sum |terms|: each z^2 carries the roundings of the subtraction, the division (twice in the square) and the square (5 u), the
     sum over the actions A - 1 more; the logs one each, their sum and the two additions the same count again."""
     return (A + 4.0) * U32 * ref["nlp_terms"]
+
+
+# ---- the loss scale's rule, and rows where the policy has run away (tests/test_ppo_runaway_*.py) -----------------------------------------
+F32 = np.float32
+SCALE_FLOOR = F32(1.0)                # PPENV_PPO_SCALE_FLOOR (include/ppenv_ppo.h)
+MIN_NORMAL = F32(2.0 ** -126)         # the smallest scale whose reciprocal is finite whether or not denormals are flushed
+SCALER_FIELDS = ("scale", "growth_tracker", "step", "skipped", "floor_hits")
+DYNAMIC = dict(growth_factor=2.0, backoff_factor=0.5, growth_interval=3)
+CONSTANT = dict(growth_factor=1.0, backoff_factor=1.0, growth_interval=3)
+
+
+def scaler_steps(state, finite):
+    """Does ppenv_ppo_adam_step take the step?  `finite`: the square sum of the (scaled) gradients is finite.  A scale that is not a normal
+    positive fp32 number (0, a denormal, negative, NaN) cannot be divided out with a finite reciprocal: the step is skipped."""
+    return bool(finite) and bool(F32(state["scale"]) >= MIN_NORMAL)
+
+
+def scaler_update(state, finite, hp):
+    """include/ppenv_ppo.h's scaler rule in numpy float32: state = dict over SCALER_FIELDS (scale: fp32), hp = dict(growth_factor,
+    backoff_factor, growth_interval) -> the next state.  torch's GradScaler.update, with two bounds torch does not have: a dynamic scale
+    (backoff_factor < 1) never leaves an update below SCALE_FLOOR — a state found below it is lifted — and growth is withheld where
+    scale x growth_factor is not finite."""
+    scale = F32(state["scale"])
+    nx = dict(state)
+    with np.errstate(all="ignore"):
+        if not scaler_steps(state, finite):
+            nx["scale"] = scale * F32(hp["backoff_factor"])
+            nx["growth_tracker"] = 0
+            nx["skipped"] = state["skipped"] + 1
+        else:
+            nx["step"] = state["step"] + 1
+            nx["growth_tracker"] = state["growth_tracker"] + 1
+            if nx["growth_tracker"] >= hp["growth_interval"]:
+                grown = scale * F32(hp["growth_factor"])
+                if np.isfinite(grown):
+                    nx["scale"] = grown
+                nx["growth_tracker"] = 0
+        if hp["backoff_factor"] < 1.0 and not nx["scale"] >= SCALE_FLOOR:       # `not >=`: a NaN scale is lifted too
+            nx["scale"] = SCALE_FLOOR
+            nx["floor_hits"] = state["floor_hits"] + 1
+    nx["scale"] = F32(nx["scale"])
+    return nx
+
+
+def scaler_state(scale, growth_tracker=0, step=0, skipped=0, floor_hits=0):
+    return dict(scale=F32(scale), growth_tracker=growth_tracker, step=step, skipped=skipped, floor_hits=floor_hits)
+
+
+RUNAWAY_C = (-8e3, -100.0, -80.0, -0.6, 0.0, 0.6, 80.0, 100.0, 8e3)      # log ratios: 0, fp32-denormal, normal, inf in fp32 only, inf in fp64
+HEALTHY_C = (-0.6, -0.05, 0.0, 0.05, 0.6)                                 # test_ppo_gpu._batch's
+
+
+def neglogp64(actions, mu, logstd):
+    f = lambda x: np.asarray(x, dtype=np.float64)
+    ls = f(logstd)
+    z = (f(actions) - f(mu)) / np.exp(ls)
+    return 0.5 * (z * z).sum(1) + HALF_LOG_2PI * z.shape[1] + ls.sum()
+
+
+def rows_around(rng, mu, logstd, c, advantages, value, old_values, returns):
+    """test_ppo_gpu._batch's rows around a GIVEN mu [m, a] (drawn, or a network's output): the actions are the clamped samples, old_mu and
+    old_sigma lie near mu and sigma, and old_neglogp = nlp + c + U(+-0.02) with nlp formed in fp64 from the fp32 images, so that the log
+    ratio the kernel sees is c up to old_neglogp's own fp32 rounding.  -> the fp32 batch dict of ppo.loss_grad_reference's arguments."""
+    m, a = mu.shape
+    mu, logstd = np.asarray(mu, dtype=F32), np.asarray(logstd, dtype=F32)
+    sg = np.exp(logstd.astype(np.float64))
+    actions = np.clip(mu + sg * rng.standard_normal((m, a)), -1, 1).astype(F32)
+    old_nlp = neglogp64(actions, mu, logstd) + c + rng.uniform(-0.02, 0.02, m)
+    b = dict(mu=mu, value=value, actions=actions, old_neglogp=old_nlp, old_mu=mu + 0.1 * rng.standard_normal((m, a)),
+             old_sigma=sg * rng.uniform(0.9, 1.1, a), advantages=advantages, old_values=old_values, returns=returns, logstd=logstd)
+    return {k: np.asarray(v, dtype=F32) for k, v in b.items()}
+
+
+def runaway_batch(rng, m, a):
+    """Rows of the regime DESIGN §6 records for seed 43: mu in +-20, log ratios from RUNAWAY_C, advantages of both signs with |adv| >= 0.05,
+    value - old_values in +-[0.06, 0.1], [0.3, 0.5], [3, 5], [30, 50] (inside the value clip and far outside), returns in +-1e3.  The last
+    m // 8 rows have adv == 0 and a log ratio within +-0.6 (an exact zero never meets an infinite ratio: 0 x inf is where numpy's maximum
+    and fmaxf part, and the gradient is 0 either way)."""
+    n0 = m // 8
+    logstd = rng.uniform(-2.2, -1.5, a)
+    mu = rng.uniform(-20.0, 20.0, (m, a))
+    c = rng.choice(RUNAWAY_C, m)
+    c[m - n0:] = rng.choice([-0.6, 0.0, 0.6], n0)
+    adv = rng.choice([-1.0, 1.0], m) * (0.05 + np.abs(rng.standard_normal(m)))
+    adv[m - n0:] = 0.0
+    old_v = rng.standard_normal(m)
+    value = old_v + rng.choice([-50.0, -5.0, -0.5, -0.1, 0.1, 0.5, 5.0, 50.0], m) * rng.uniform(0.6, 1.0, m)
+    return rows_around(rng, mu, logstd, c, adv, value, old_v, rng.uniform(-1e3, 1e3, m))
+
+
+def loss_grad_reference_f32_ratio(b, **kw):
+    """ppo.loss_grad_reference with ONE change: the ratio is rounded to fp32 before it is used, the precision the kernel's header documents
+    ("the ratio is formed in fp64; everything written is fp32").  The reference forms ratio = exp(old_neglogp - nlp) itself, so the rounding
+    goes in through its argument: old_neglogp' = nlp + log(fp32(ratio)) in fp64 (-inf for a ratio of 0, +inf for an infinite one), which
+    the reference's own exp turns back into fp32(ratio) to 1e-11 relatively."""
+    from isaacgym_amd import ppo
+    with np.errstate(all="ignore"):
+        nlp = neglogp64(b["actions"], b["mu"], b["logstd"])
+        ratio = np.exp(b["old_neglogp"].astype(np.float64) - nlp).astype(F32).astype(np.float64)
+        return ppo.loss_grad_reference(**dict(b, old_neglogp=nlp + np.log(ratio)), **kw)
+
+
+RUNAWAY_CASES = [(m, a) for m in (64, 257) for a in (7, 27)]
+RUNAWAY_SCALE = 512.0
+_cases = {}
+
+
+def runaway_case(m, a, clip_value):
+    """One case of the runaway loss test, computed once and shared (nobody writes to it): (batch, PPOConfig, reference, the reference's
+    non-finite rows)."""
+    from isaacgym_amd import ppo
+    if (m, a, clip_value) not in _cases:
+        b = runaway_batch(np.random.default_rng(1000 * m + a), m, a)
+        cfg = ppo.PPOConfig(entropy_coef=0.01, clip_value=clip_value)
+        ref = loss_grad_reference_f32_ratio(b, e_clip=cfg.e_clip, critic_coef=cfg.critic_coef, bounds_loss_coef=cfg.bounds_loss_coef,
+                                            entropy_coef=cfg.entropy_coef, clip_value=clip_value, scale=RUNAWAY_SCALE)
+        _cases[m, a, clip_value] = (b, cfg, ref, nonfinite_rows(ref["d_mu"], ref["d_value"]))
+    return _cases[m, a, clip_value]
+
+
+def log_ratio(b):
+    return b["old_neglogp"].astype(np.float64) - neglogp64(b["actions"], b["mu"], b["logstd"])
+
+
+def assert_runaway_margins(b, e_clip=0.2, margin=1e-3):
+    """On the fp64 reference's own quantities: no row within `margin` of a switch an fp32 rounding could take the other way (the ratio against
+    1 +- e where it is near them at all; |v - old_v| against e; the two value losses, relatively: they reach 1e6), and every kind of row present."""
+    f = lambda k: b[k].astype(np.float64)
+    c = log_ratio(b)
+    near = np.abs(c) < 1.0
+    ratio = np.exp(c[near])
+    assert np.abs(ratio - (1 + e_clip)).min() > margin and np.abs(ratio - (1 - e_clip)).min() > margin
+    d = f("value") - f("old_values")
+    assert np.abs(np.abs(d) - e_clip).min() > margin
+    vc = f("old_values") + np.clip(d, -e_clip, e_clip)
+    cu, cc = (f("value") - f("returns")) ** 2, (vc - f("returns")) ** 2
+    out = np.abs(d) > e_clip
+    assert (np.abs(cu - cc)[out] > 1e-5 * np.maximum(cu, cc)[out]).all()
+    assert (np.abs(d) < e_clip).any() and (np.abs(d) > 30).any() and (cu > cc).any() and (cu < cc).any()
+    adv = f("advantages")
+    assert (np.abs(adv[adv != 0]) >= 0.05).all() and (adv > 0).any() and (adv < 0).any()
+    assert (adv == 0).any() and (np.abs(c[adv == 0]) < 1.0).all()
+    with np.errstate(over="ignore"):
+        r32 = np.exp(c).astype(F32)
+    tiny = np.finfo(F32).tiny
+    for what, rows in (("0", r32 == 0), ("denormal", (r32 > 0) & (r32 < tiny)), ("normal", (r32 >= tiny) & np.isfinite(r32) & ~near),
+                       ("inf in fp32 only", np.isinf(r32) & (c < 709)), ("inf in fp64", c > 710)):
+        assert rows.any(), f"no row with a ratio that is {what}"
+
+
+def nonfinite_rows(d_mu, d_value):
+    """The rows whose fp32 image of d_mu / d_value holds an inf or a NaN (the kernel writes fp32: a value beyond its range is an inf there)."""
+    with np.errstate(all="ignore"):
+        return ~(np.isfinite(np.asarray(d_mu).astype(F32)).all(1) & np.isfinite(np.asarray(d_value).astype(F32)))
