@@ -25,7 +25,7 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip"),
            os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip"), os.path.join(_PKG, "csrc", "ppenv_dr_adr.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_critic_input.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_critic_input.hip"), os.path.join(_PKG, "csrc", "ppenv_history.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -41,6 +41,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_serve_curric_device.h"), os.path.join(ROOT, "include", "ppenv_serve_curric.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_adr_device.h"), os.path.join(ROOT, "include", "ppenv_dr_adr.h"),
            os.path.join(_PKG, "csrc", "ppenv_critic_input_device.h"), os.path.join(ROOT, "include", "ppenv_critic_input.h"),
+           os.path.join(_PKG, "csrc", "ppenv_history_device.h"), os.path.join(ROOT, "include", "ppenv_history.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -50,13 +51,15 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize
 # the actuator accounting rounds t * t and t * v before adding them, as its host build does, and its largest excursion starts at -inf;
 # the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does;
 # ADR draws with the reset-time plan's arithmetic, stages returns as the serve curriculum does and rounds every operation of its update on its own;
-# the privileged critic inputs copy a float bit for bit (a negative zero keeps its sign) and round the normaliser's two operations on their own
+# the privileged critic inputs copy a float bit for bit (a negative zero keeps its sign) and round the normaliser's two operations on their own;
+# the observation and action history moves words bit for bit, and its clamp keeps a negative zero's sign and turns a NaN action into lo
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve_curric.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_dr_adr.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_critic_input.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_history.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
@@ -249,6 +252,7 @@ class AdrState(C.Structure):
 
 CRITIC_MAX_SOURCES, CRITIC_MAX_COLS = 16, 1024                                           # PP_CRITIC_MAX_SOURCES, PP_CRITIC_MAX_COLS
 CRITIC_F32, CRITIC_I32, CRITIC_ROW_MAJOR, CRITIC_TABLE_MAJOR = 0, 1, 0, 1                # PP_CRITIC_F32 / _I32, PP_CRITIC_ROW_MAJOR / _TABLE_MAJOR
+HISTORY_MAX, HISTORY_MAX_WIDTH = 8, 16256                                                # PP_HISTORY_MAX, PP_HISTORY_MAX_WIDTH
 
 
 class CriticSource(C.Structure):
@@ -559,6 +563,10 @@ def load(path):
     L.pp_critic_input_upload.argtypes = [C.POINTER(CriticTable), vp, vp]
     L.pp_critic_input_gather.argtypes = [vp, i32, i32, vp, i64, vp]
     L.pp_critic_input_prepare.argtypes = [vp, i64, i32, i32, vp, vp, f32, vp, i32, i32, vp]
+    # ---- include/ppenv_history.h
+    L.pp_history_width.restype = i32
+    L.pp_history_width.argtypes = [i32, i32, i32, i32]
+    L.pp_history_push.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp, i64, i32, i32, i32, i32, i32, i32, f32, f32, vp]
     return L
 
 

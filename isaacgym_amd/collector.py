@@ -19,6 +19,7 @@ import ctypes as C
 import torch
 
 from . import _lib
+from . import history as history_mod
 from .latency import COMMAND, SENSING, DelayLine, delay_range
 
 
@@ -65,16 +66,35 @@ class RolloutCollector:
     every forward reads priv[t] beside obs[t].  Row t + 1 is gathered — one launch, straight into the slice — after the env step, the
     delay-line pushes and the serve / randomizer hooks of step t, so it shows the tables and delays the env will play step t + 1 with; row
     0 is gathered once at construction; next_horizon() carries row H to row 0.  None or empty (the default): nothing is allocated or
-    launched, and `priv` and `critic_input` are None."""
+    launched, and `priv` and `critic_input` are None.
+
+    history: an observation and action history for the policy's input (history.parse: (Ho, Ha), dict(obs=, actions=) or the CLI's text;
+    include/ppenv_history.h).  `obs` is then [H+1, N, W], W = (Ho + 1) * num_obs + Ha * A, and `net` must have been built with num_obs = W.
+    The env step writes a contiguous [N, num_obs] buffer — `cur_obs`, or with a sensing line `raw_obs` as before, the line's output then
+    going to `seen_obs` [N, num_obs] — and one more launch builds obs[t + 1] from obs[t], that observation, actions[t] and dones[t]
+    (history.HistoryStack.push), after the delay-line pushes and before the serve, randomizer and critic-input hooks.  Row 0 of the first
+    horizon is pushed with no previous row: every env starts.  next_horizon() is unchanged, and the `raw_obs` critic input keeps width
+    num_obs.  Not with a fuse_input network, whose layer 1 reads the env's observation in place.  None (the default): nothing is
+    allocated or launched, and `history`, `cur_obs` and `seen_obs` are None."""
 
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0, action_delay=0, obs_delay=0,
-                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None, critic_input=None):
+                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None, critic_input=None, history=None):
         self.action_delay, self.obs_delay = delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay)
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
         n, dev, a = env.num_rows, env.device, net.num_actions        # actor rows: A * N for the 4-actor variant
         z = lambda *shape, dt=torch.float32: torch.zeros(shape, dtype=dt, device=dev)
-        self.obs = z(self.h + 1, n, env.obs_buf.shape[1])
+        num_obs = env.obs_buf.shape[1]
+        self.history = self.cur_obs = self.seen_obs = None
+        record = history_mod.parse(history, num_obs, a)
+        if record is not None:
+            if getattr(net, "fuse_input", False):
+                raise ValueError("history: not with a fuse_input network, whose layer 1 reads the env's observation in place")
+            if net.num_obs != record["width"]:
+                raise ValueError(f"history: {record['obs']} observations + {record['actions']} actions back make rows of {record['width']} columns, but the "
+                                 f"network was built with num_obs={net.num_obs}")
+            self.history = history_mod.HistoryStack(n, num_obs, a, record["obs"], record["actions"], dev, env.num_agents)
+        self.obs = z(self.h + 1, n, num_obs if record is None else record["width"])
         self.head = z(self.h + 1, n, a + 1)                     # mu | value, as the heads launch writes them
         self.mu, self.values = self.head[:, :, :a], self.head[:, :, a]
         self.actions, self.neglogp = z(self.h, n, a), z(self.h, n)
@@ -91,11 +111,19 @@ class RolloutCollector:
         if self.action_delay[1] > 0:
             self.act_line, self.applied = line(a, self.action_delay, COMMAND), z(n, a)
         if self.obs_delay[1] > 0:
-            self.obs_line, self.raw_obs = line(env.obs_buf.shape[1], self.obs_delay, SENSING), z(n, env.obs_buf.shape[1])
+            self.obs_line, self.raw_obs = line(num_obs, self.obs_delay, SENSING), z(n, num_obs)
             self.raw_obs.copy_(env.obs_buf)
-            self.obs_line.push(self.raw_obs, None, self.obs[0])
-        else:
+            if self.history is None:
+                self.obs_line.push(self.raw_obs, None, self.obs[0])
+            else:
+                self.seen_obs = z(n, num_obs)
+                self.history.push(self.obs_line.push(self.raw_obs, None, self.seen_obs), None, None, None, self.obs[0])
+        elif self.history is None:
             self.obs[0].copy_(env.obs_buf)
+        else:
+            self.cur_obs = z(n, num_obs)
+            self.cur_obs.copy_(env.obs_buf)
+            self.history.push(self.cur_obs, None, None, None, self.obs[0])
         self.critic_input = self.priv = None
         if critic_input:
             from .critic_input import CriticInput
@@ -117,7 +145,15 @@ class RolloutCollector:
             self.counter += 1
             self._forward(t, sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
             act = self.actions[t] if self.act_line is None else self.act_line.push(self.actions[t], self._done_prev, self.applied)
-            if self.obs_line is None:
+            if self.history is not None:
+                seen = self.cur_obs
+                if self.obs_line is None:
+                    self.env.step(act, obs=seen, rew=self.rewards[t], reset=self.dones[t])
+                else:
+                    self.env.step(act, obs=self.raw_obs, rew=self.rewards[t], reset=self.dones[t])
+                    seen = self.obs_line.push(self.raw_obs, self.dones[t], self.seen_obs)
+                self.history.push(seen, self.actions[t], self.dones[t], self.obs[t], self.obs[t + 1])
+            elif self.obs_line is None:
                 self.env.step(act, obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
             else:
                 self.env.step(act, obs=self.raw_obs, rew=self.rewards[t], reset=self.dones[t])

@@ -74,6 +74,11 @@ the player without the feature byte for byte.  The result gains `latency` = dict
 Training under latency is the trainer's: PPOTrainer(action_delay=, obs_delay=) with isaacgym_amd.latency.DelayLine (include/ppenv_train_delay.h),
 fixed or drawn per episode, in this player's order — a fixed delay trains under exactly what the sweep axes above measure.
 
+Observation and action history.  A checkpoint trained with PPOTrainer(history=) carries a "history" record (include/ppenv_history.h); there is no
+play flag, the checkpoint decides.  The player then stacks the seen observations and the policy's own last actions on the device, one launch per
+control step and distinct record (history.HistoryStack.advance, after the sensing line, before the policy), and the result gains `history`.
+With --against a history checkpoint and a plain one play the same balls in one pass.  Without such a checkpoint nothing is built.
+
 Out of scope: delays drawn per episode in the player (fixed-delay sweeps evaluate a policy trained under them), action hold / policy decimation,
 per-cell observation or action noise, a VecTask-level latency setting; sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
 paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games

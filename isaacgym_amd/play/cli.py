@@ -142,6 +142,8 @@ def print_report(args, task, res, recorder):
     print(f"av reward: {res['av_reward']} av steps: {res['av_steps']}")
     if "latency" in res:
         print(latency_line(res["latency"]))
+    for k, rec in enumerate(res.get("history", ())):                          # the checkpoints decide: one line per distinct policy
+        print(f"history: checkpoint {k}: " + ("none" if rec is None else f"{rec['obs']} observations + {rec['actions']} actions back, {rec['num_obs']} -> {rec['width']} columns"))
     if args.outcomes:
         print("\n".join(outcome_lines(res["outcomes"])) if res["outcomes"]["windows"] > 0 else "no env has reset: no outcome window yet")
     for a, p in enumerate(res["per_agent"]):

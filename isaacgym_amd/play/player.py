@@ -69,6 +69,13 @@ class Player:
     policy's raw output (the actuator report's clip share reads it), `applied_actions` is what the env consumed, `policy_obs` what the
     policy saw.  The lines sit between the policy and the task and compose with everything above, a `randomize: True` task included.  With
     a line in use the result gains `latency` = dict(control_dt, action_delay=[per cell], obs_delay=[per cell]).
+    A policy with an observation and action history (policy.history: the checkpoint decides, there is no argument here; include/
+    ppenv_history.h) is accepted when its base_num_obs is the task's num_obs and its network is history["width"] wide.  The player then
+    keeps one history.HistoryStack per distinct record over ALL rows, and per control step: seen = obs_line.push(...) or the raw obs;
+    wide = stack.advance(seen, the policy output of the previous step, done_prev); act on wide.  start() resets the stacks, so the first
+    push starts every row.  With per-cell policies each run of cells reads its own record's rows of `wide`, or `seen` — a history
+    checkpoint plays A/B against one without.  `policy_obs` stays what the policy saw: with mixed records, the widest.  The result gains
+    `history`, the record (or None) of each distinct policy.  Without such a policy nothing is built and the player is today's byte for byte.
     Without a sweep the player is ONE cell, `{}`, over all envs — the actuators, the delays and the result are assembled over `_cells`
     either way — but it is not a one-cell Sweep: its `stats` is an EpisodeStats (the outcome latch needs its one struct), its totals are
     that struct's own, and start() / end_sweep() leave the task's randomisation and serve plan alone."""
@@ -100,9 +107,11 @@ class Player:
         for p in self.policies:
             if torch.device(p.device) != sim:
                 raise ValueError(f"the policy lives on {p.device}, the task on {sim}")
-            if p.net.num_obs != task.num_obs or p.net.num_actions != task.num_actions:
-                raise ValueError(f"the policy maps {p.net.num_obs} observations to {p.net.num_actions} actions, the task has "
-                                 f"{task.num_obs} and {task.num_actions}")
+            hist = getattr(p, "history", None)
+            if getattr(p, "base_num_obs", p.net.num_obs) != task.num_obs or p.net.num_actions != task.num_actions or \
+                    p.net.num_obs != (task.num_obs if hist is None else hist["width"]):
+                raise ValueError(f"the policy maps {getattr(p, 'base_num_obs', p.net.num_obs)} observations to {p.net.num_actions} actions, the task has "
+                                 f"{task.num_obs} and {task.num_actions}" + ("" if hist is None else f" (history {hist}: a network of {p.net.num_obs} columns)"))
         self.task, self.policy = task, self.policies[0]
         self.games_num, self.poll_every, self.max_steps = int(games_num), int(poll_every), int(max_steps)
         self.deterministic, self.seed = bool(deterministic), int(seed)
@@ -145,6 +154,13 @@ class Player:
         self._act_line = Delay(rows, task.num_actions, per_row["action_delay"], sim, A) if per_row["action_delay"].any() else None
         self._obs_line = Delay(rows, task.num_obs, per_row["obs_delay"], sim, A) if per_row["obs_delay"].any() else None
         self._done_prev = None
+        # one stack per distinct history record, each over all rows: a policy without a history builds none
+        self._stacks, self._wide = {}, {}
+        for p in self.policies:
+            hist = getattr(p, "history", None)
+            if hist is not None and self._key(p) not in self._stacks:
+                from ..history import HistoryStack
+                self._stacks[self._key(p)] = HistoryStack(rows, task.num_obs, task.num_actions, hist["obs"], hist["actions"], sim, A)
         self._runs = self._cell_actions = None
         if per_cell:                                                     # runs of consecutive cells that hold the same object: (policy, first row, end row)
             w, runs = A * S, []
@@ -164,6 +180,16 @@ class Player:
         self.steps_played = 0
         self.actions = self.applied_actions = self.policy_obs = None
         self._obs = None
+
+    @staticmethod
+    def _key(policy):
+        """Which stack a policy reads: (Ho, Ha), or None for the plain observation."""
+        hist = getattr(policy, "history", None)
+        return None if hist is None else (hist["obs"], hist["actions"])
+
+    def history(self):
+        """run()'s `history`: the record of each distinct policy, None for one without."""
+        return [None if getattr(p, "history", None) is None else dict(p.history) for p in self._distinct]
 
     def end_sweep(self):
         """The task as the sweep found it: the plain step kernel (clear_randomization), no serve plan, and the episode counters of before
@@ -199,6 +225,8 @@ class Player:
         for line in (self._act_line, self._obs_line):
             if line is not None:
                 line.reset()
+        for stack in self._stacks.values():
+            stack.reset()
         self._done_prev = None
         for p in self._distinct:
             p._counter = 0
@@ -207,11 +235,12 @@ class Player:
 
     def _act_per_cell(self, obs):
         """Every run of cells under its own policy, into ONE [rows, num_actions] tensor: a policy owns its output buffer and may serve
-        several runs, so each result is copied out before the next act()."""
+        several runs, so each result is copied out before the next act().  A policy with a history reads its record's wide rows."""
         if self._cell_actions is None:
             self._cell_actions = torch.empty((obs.shape[0], self.task.num_actions), dtype=torch.float32, device=obs.device)
         for p, r0, r1 in self._runs:
-            a, _ = p.act(obs[r0:r1], deterministic=self.deterministic, seed=self.seed)
+            x = obs if self._key(p) is None else self._wide[self._key(p)]
+            a, _ = p.act(x[r0:r1], deterministic=self.deterministic, seed=self.seed)
             self._cell_actions[r0:r1].copy_(a)
         return self._cell_actions
 
@@ -219,11 +248,15 @@ class Player:
         """One control step: (obs line ->) policy (-> action line) -> task.step -> accumulate (-> record, with paired_diff).  No host read."""
         if self._obs is None:
             self.start()
-        self.policy_obs = self._obs if self._obs_line is None else self._obs_line.push(self._obs, self._done_prev)
+        seen = self._obs if self._obs_line is None else self._obs_line.push(self._obs, self._done_prev)
+        self.policy_obs = seen
+        if self._stacks:                                                  # self.actions: the policies' output of the previous step, not read on a start
+            self._wide = {k: stack.advance(seen, self.actions, self._done_prev) for k, stack in self._stacks.items()}
+            self.policy_obs = max(self._wide.values(), key=lambda w: w.shape[1])      # with mixed records: the widest (any is wider than `seen`)
         if self._runs is None:
             self.actions, _ = self.policy.act(self.policy_obs, deterministic=self.deterministic, seed=self.seed)
         else:
-            self.actions = self._act_per_cell(self.policy_obs)
+            self.actions = self._act_per_cell(seen)
         self.applied_actions = self.actions if self._act_line is None else self._act_line.push(self.actions, self._done_prev)
         obs, rew, done, _ = self.task.step(self.applied_actions)
         self._done_prev = done
@@ -298,6 +331,8 @@ class Player:
                 out["actuators"] = self.read_actuators()
             if self._act_line is not None or self._obs_line is not None:
                 out["latency"] = self.latency()
+            if self._stacks:
+                out["history"] = self.history()
             return out
         finally:
             self.end_sweep()

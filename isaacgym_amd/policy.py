@@ -754,12 +754,22 @@ class RLGamesPolicy:
     """A trained rl_games continuous-action policy served by NativeMLP: input normalisation (running_mean_std, eval mode), actor and
     critic, fixed log-std sigma (`continuous_a2c_logstd`: sigma = exp(a2c_network.sigma)), value de-normalisation (value_mean_std,
     `normalize_value: True`).  `act(obs)` is what rl_games' player does per step: mu (deterministic) or a Normal(mu, sigma) draw,
-    clamped to [-1, 1]."""
+    clamped to [-1, 1].
+    history: the checkpoint's record of an observation and action history (history.parse's; include/ppenv_history.h) or None.  The network's
+    rows are then `history["width"]` wide — the caller stacks them (history.HistoryStack; play.Player does) — and `base_num_obs` is the
+    env's observation width; without one `history` is None and base_num_obs == net.num_obs."""
 
-    def __init__(self, state_dict, device, max_rows=None, eps=1e-5):
+    def __init__(self, state_dict, device, max_rows=None, eps=1e-5, history=None):
         sd = state_dict
         actor, critic = layers_from_rlgames_state_dict(sd)
         num_obs = actor[0][0].shape[1]
+        self.history, self.base_num_obs = None, num_obs
+        if history is not None:
+            from . import history as history_mod
+            self.history = history_mod.parse(dict(history), history["num_obs"], history["num_actions"])
+            if self.history["width"] != num_obs or self.history["num_actions"] != actor[-1][0].shape[0]:
+                raise ValueError(f"history: the record {self.history} does not describe this network, which maps {num_obs} columns to {actor[-1][0].shape[0]} actions")
+            self.base_num_obs = self.history["num_obs"]
         mean, var = sd.get("running_mean_std.running_mean"), sd.get("running_mean_std.running_var")
         if mean is None:                                       # normalize_input: False
             mean, var = torch.zeros(num_obs), torch.ones(num_obs) - eps
@@ -779,7 +789,7 @@ class RLGamesPolicy:
     def load(cls, path, device, max_rows=None):
         """A checkpoint file written by rl_games (`nn/<name>.pth`): tensors only are read (weights_only)."""
         ckpt = torch.load(path, map_location="cpu", weights_only=True)
-        return cls(ckpt["model"] if "model" in ckpt else ckpt, device, max_rows=max_rows)
+        return cls(ckpt["model"] if "model" in ckpt else ckpt, device, max_rows=max_rows, history=ckpt.get("history") if "model" in ckpt else None)
 
     def act(self, obs, deterministic=True, seed=0):
         """obs [M, num_obs] fp32 on the device -> (actions [M, A] in [-1, 1], value [M, 1] de-normalised).  seed: the user's; the draws are

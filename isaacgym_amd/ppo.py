@@ -32,7 +32,7 @@ Deviations from rl_games:
     critic tower of the one network reads extra first-layer columns, and loss, optimizer, schedule and minibatches are the ones above.
 
 Checkpoints are rl_games' layout: {"model": network + value_mean_std.*, "epoch", "frame", "optimizer"}; RLGamesPolicy.load serves them.
-They also carry "meter" (the score meter's struct), "last_mean_rewards" (the best score so far) and "latency" (the two delay ranges the
+They also carry "history" (the record of an observation and action history, below), "meter" (the score meter's struct), "last_mean_rewards" (the best score so far) and "latency" (the two delay ranges the
 run trained under, {"action_delay": [lo, hi], "obs_delay": [lo, hi]}: a record — load() accepts files without any of them, and the
 trainer that loads keeps the delays it was built with).
 
@@ -51,6 +51,10 @@ the actor's weights over them are exactly zero and never reach the optimizer (po
 inputs").  The columns have running statistics of their own (`critic_mean_std.*` in the checkpoint's model), updated under the rule of the
 observation statistics.  Checkpoints carry the record under "critic_inputs" (names, columns per name, P); load() refuses a file whose P or
 names differ.  RLGamesPolicy serves such a checkpoint's actor as it stands.  Off by default, and then nothing is built.
+
+Observation and action history (PPOTrainer(history=(Ho, Ha)), --obs-history Ho --action-history Ha): the network's input rows become the
+observation the policy sees now, the Ho it saw before and its own last Ha actions, stacked on the device (history.HistoryStack;
+include/ppenv_history.h; DESIGN §5d "Observation and action history").  Off by default, and then nothing is built.
 
 The score (GameMeter; C ABI: include/ppenv_ppo_meter.h) is rl_games' game_rewards / game_lengths: AverageMeter(games_to_track) over the
 finished games' unscaled returns (agent 0's row of each env) and lengths, updated once per epoch over the collector's horizon by two
@@ -473,10 +477,18 @@ class PPOTrainer:
     obs_delay above 0: otherwise a ValueError naming the argument.  The network is then built with num_priv = P, the collector keeps
     `col.priv` [H + 1, rows, P], minibatch_step() slices it like `obs` (prepare() reads neither), and data-parallel the privileged statistics are broadcast
     with the others at the start.  critic_inputs() returns the record.  Empty (the default): the trainer is bitwise the trainer without the
-    argument and `col.priv` is None.  clear_randomization() leaves the tables' columns reading the dropped tensors as they last stood."""
+    argument and `col.priv` is None.  clear_randomization() leaves the tables' columns reading the dropped tensors as they last stood.
+    history: an observation and action history as the policy's input — (Ho, Ha), dict(obs=Ho, actions=Ha) or the CLI's text (history.parse;
+    include/ppenv_history.h — this build's own rule): the network's rows become the observation the policy sees now, the Ho it saw before and
+    its own last Ha clamped actions, W = (Ho + 1) * n + Ha * A columns, built on the device by one more launch per control step
+    (RolloutCollector(history=)).  Actor and critic are both built with num_obs = W — `num_obs` is then W, `base_num_obs` the env's n —, the
+    input statistics are W wide, privileged columns start at W and a `raw_obs` critic input keeps width n.  history() returns the record,
+    checkpoints carry it under "history", load() refuses a file whose record differs, and RLGamesPolicy / Player serve such a checkpoint
+    with a stack of their own.  Data-parallel training needs nothing new.  None (the default): the trainer is bitwise the trainer without
+    the argument."""
 
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
-                 curriculum=None, randomization=None, adr=None, critic_inputs=()):
+                 curriculum=None, randomization=None, adr=None, critic_inputs=(), history=None):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         from . import critic_input as critic_input_mod
         critic_inputs = critic_input_mod.parse(critic_inputs)
@@ -494,7 +506,10 @@ class PPOTrainer:
         self.device = dev = torch.device(env.device)
         self.rows = env.num_rows                  # actor rows: num_envs x num_agents (T4: 2 actors per env)
         cfg.check(self.rows)
-        self.num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
+        self.base_num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
+        from . import history as history_mod
+        self._history = history_mod.parse(history, self.base_num_obs, self.num_actions)      # the width of the network's rows: resolved, with every refusal, first
+        self.num_obs = self.base_num_obs if self._history is None else self._history["width"]
         self.seed = int(seed)
         dist = torch.distributed
         initialised = dist.is_available() and dist.is_initialized()
@@ -531,7 +546,7 @@ class PPOTrainer:
             tabs = env.dr_tables
             self._critic_inputs = critic_input_mod.columns(critic_inputs, env.DR_TABLE_ROWS, None if tabs is None else
                                                            [k for k, t in zip(env.DR_TABLE_ROWS, tabs) if t is not None],
-                                                           delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay), self.num_obs)
+                                                           delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay), self.base_num_obs)
         P = self._critic_inputs["P"] if self._critic_inputs else 0
         with torch.random.fork_rng(devices=[]):
             torch.manual_seed(self.seed)
@@ -548,7 +563,7 @@ class PPOTrainer:
                                     sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
                                     action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
                                     env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan,
-                                    randomizer=randomizer, critic_input=critic_inputs or None)
+                                    randomizer=randomizer, critic_input=critic_inputs or None, history=self._history)
         if self._critic_inputs is not None:
             assert self.col.critic_input.record() == self._critic_inputs
         self.g_logstd = self.learner.grad_extra
@@ -653,6 +668,10 @@ class PPOTrainer:
         """The record of the privileged critic inputs — dict(names=[...], columns=[one count per name], P=the sum) — or None without any."""
         r = self._critic_inputs
         return None if r is None else dict(names=list(r["names"]), columns=[int(c) for c in r["columns"]], P=int(r["P"]))
+
+    def history(self):
+        """The record of the observation and action history — dict(obs=Ho, actions=Ha, num_obs=n, num_actions=A, width=W) — or None without one."""
+        return None if self._history is None else dict(self._history)
 
     def latency(self):
         """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
@@ -828,6 +847,8 @@ class PPOTrainer:
             sd["adr"] = self.adr.state_dict()
         if self._critic_inputs is not None:
             sd["critic_inputs"] = self.critic_inputs()
+        if self._history is not None:
+            sd["history"] = self.history()
         return sd
 
     def save(self, path):
@@ -843,6 +864,8 @@ class PPOTrainer:
         ck = torch.load(path, map_location=self.device, weights_only=True)
         from . import critic_input as critic_input_mod
         critic_input_mod.check_record(ck.get("critic_inputs"), self._critic_inputs)   # first: other privileged columns raise before anything is overwritten
+        from . import history as history_mod
+        history_mod.check_record(ck.get("history"), self._history)           # likewise: another history is another first layer
         if self.curriculum is not None and "curriculum" in ck:               # first: other bins raise before anything is overwritten.  A file without one: the table starts fresh
             self.curriculum.load_state_dict(ck["curriculum"])
         if self.adr is not None and "adr" in ck:                             # likewise: other dims raise before anything is overwritten
@@ -1047,6 +1070,9 @@ def main(argv=None):
     ap.add_argument("--adr-out", default=None, help="a json file rewritten with the table at each print")
     ap.add_argument("--critic-inputs", default="", metavar="NAME[,NAME...]", help="privileged critic inputs (an asymmetric actor-critic): tables (needs "
                     "--randomize or --adr), latency (needs --action-delay or --obs-delay), raw_obs (needs --obs-delay); the critic alone sees them")
+    ap.add_argument("--obs-history", type=int, default=0, metavar="Ho", help="the policy also sees the Ho observations it saw before (0..8): a frame stack "
+                    "built on the device, for training under --obs-delay / --action-delay / --randomize / --adr")
+    ap.add_argument("--action-history", type=int, default=0, metavar="Ha", help="... and its own last Ha clamped actions (0..8)")
     ap.add_argument("--capture-video", action="store_true", default=None, help="record videos of the training envs to <out>/videos (train.py: capture_video)")
     ap.add_argument("--capture-video-freq", type=int, default=None, help="control steps between the starts of two recordings (1464)")
     ap.add_argument("--capture-video-len", type=int, default=None, help="control steps one recording covers (100)")
@@ -1068,6 +1094,8 @@ def main(argv=None):
         serve_plan, curriculum = serve_cell_parse(args.serve), None
         from . import critic_input as critic_input_mod
         critic_inputs = critic_input_mod.parse(args.critic_inputs)
+        from . import history as history_mod
+        history = history_mod.parse((args.obs_history, args.action_history))
         if args.curriculum:
             if serve_plan is not None:
                 raise ValueError("--serve together with --curriculum: a plan and a curriculum write the same serve override buffer")
@@ -1112,7 +1140,8 @@ def main(argv=None):
     else:
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay,
-                    serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr, critic_inputs=critic_inputs)
+                    serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr, critic_inputs=critic_inputs,
+                    history=history)
     if rank == 0 and tr.randomization is not None:
         print("reset-time randomisation: " + ", ".join(f"{k} {t['distribution']} {t['operation']} {t['range'][0]:g}..{t['range'][1]:g}"
                                                        for k, t in tr.randomization["tables"].items()), flush=True)
@@ -1125,6 +1154,8 @@ def main(argv=None):
         print(f"serve curriculum: {tr.curriculum.bins} bins, power {tr.curriculum.power}, mix {tr.curriculum.mix:g}, alpha {tr.curriculum.alpha:g}", flush=True)
     if rank == 0 and (action_delay[1] or obs_delay[1]):
         print(latency_text(tr.latency()), flush=True)
+    if rank == 0 and tr.history() is not None:
+        print(history_mod.text(tr.history()), flush=True)
     if rank == 0 and tr.critic_inputs() is not None:
         print(critic_input_mod.text(tr.critic_inputs(), tr.num_obs), flush=True)
     if args.checkpoint:
