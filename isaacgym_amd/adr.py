@@ -4,15 +4,16 @@ pinned to one boundary of one table; finished games are credited to that boundar
 above `t_high` moves outward by its `step`, every one whose games score at or below `t_low` moves back in.  After OpenAI's ADR and
 DeXtreme; the rule is this project's own specification (the header states it).
 
-`AutoRandomizer` is built like curriculum.ServeCurriculum: the tables (handed to env.set_randomization), the per-env and per-slot state,
-the staging rows of one horizon and the launches — one per control step (`step`), two per epoch (`fold`, `update`).  torch owns the
-memory; nothing here reads the device on the host."""
+`AutoRandomizer` is a curriculum.HorizonStage, as curriculum.ServeCurriculum is: the tables (handed to env.set_randomization), the per-env
+and per-slot state and the launches of its own — one per control step (`step`), one per epoch (`update`) — over the base's staging rows of
+one horizon and its `fold`.  torch owns the memory; nothing here reads the device on the host."""
 import ctypes as C
 import math
 
 import torch
 
 from . import _lib, dr, scene
+from .curriculum import HorizonStage
 
 
 def check_parameters(boundary_frac, min_games, t_low, t_high):
@@ -90,7 +91,7 @@ def parse(flags):
     return out
 
 
-class AutoRandomizer:
+class AutoRandomizer(HorizonStage):
     def __init__(self, env, dims, boundary_frac=0.25, min_games=256, t_low=0.0, t_high=0.0, seed=None, horizon=32):
         """env: a PPEnv or TAEnv with no randomisation set.  dims: {table name: dict(start=(lo, hi), limit=(lo, hi), step=x)}, the names
         dr.TABLE_NAMES, the row counts env.DR_TABLE_ROWS.  t_low, t_high: mean returns (agent 0's, unscaled) at or below / above which a
@@ -122,9 +123,7 @@ class AutoRandomizer:
         self.draws, self.slot, self.ret = z(n, dt=torch.int32), z(n, dt=torch.int32), z(n, dt=torch.float32)
         self.acc_n, self.acc_q, self.games, self.dropped = (z(S, dt=torch.int64) for _ in range(4))
         self.mean, self.widened, self.narrowed = z(S, dt=torch.float32), z(S, dt=torch.int32), z(S, dt=torch.int32)
-        self.fin_slot, self.fin_q = torch.full((self.horizon, n), -1, dtype=torch.int32, device=dev), z(self.horizon, n, dt=torch.int64)
-        self.tot = z(3, S, dt=torch.int64)
-        self._partial = z(int(self.L.pp_serve_curric_fold_bytes(self.horizon * n)), dt=torch.uint8)
+        self.fin_slot = self._staging(S)
         self._state = _lib.AdrState(*(t.data_ptr() for t in (self.range, self.draws, self.slot, self.ret, self.acc_n, self.acc_q, self.games, self.dropped,
                                                              self.mean, self.widened, self.narrowed)))
         host = _lib.Adr(num_envs=n, env_id_offset=self.env_id_offset, seed=self.seed, reset_rows=self.reset_rows, num_agents=self.num_agents, dims=D, thr=0,
@@ -146,29 +145,24 @@ class AutoRandomizer:
     def step(self, t, rew_t, reset_t):
         """The per-step launch (pp_dr_adr_step) after the env step that wrote rew_t [A*N] f32 (unscaled) and reset_t [reset_rows*N] int64;
         stages row t of the horizon.  One launch, no synchronisation; it can be captured."""
-        assert 0 <= t < self.horizon
-        assert rew_t.dtype == torch.float32 and rew_t.is_contiguous() and rew_t.numel() == self.num_agents * self.num_envs
-        assert reset_t.dtype == torch.int64 and reset_t.is_contiguous() and reset_t.numel() == self.reset_rows * self.num_envs
+        self._check_step(t, rew_t, reset_t)
         _lib.check(self.L.pp_dr_adr_step(self.adr_dev.data_ptr(), self.num_envs, rew_t.data_ptr(), reset_t.data_ptr(), C.byref(self._state),
                                          self.fin_slot[t].data_ptr(), self.fin_q[t].data_ptr(), _lib.stream(self.device)), self.L)
-
-    def fold(self):
-        """The staged horizon -> `tot` [3, S] int64: games, sum of q, dropped games per slot (pp_serve_curric_fold, generic over bins)."""
-        _lib.check(self.L.pp_serve_curric_fold(self.fin_slot.data_ptr(), self.fin_q.data_ptr(), self.horizon * self.num_envs, self.slots, self.tot.data_ptr(),
-                                               self._partial.data_ptr() if self._partial.numel() else None, _lib.stream(self.device)), self.L)
-        return self.tot
 
     def update(self, tot=None):
         """The totals (default: this rank's `tot`; data-parallel: their sum over the ranks) into the per-slot state, and the boundaries moved
         (pp_dr_adr_update)."""
-        tot = self.tot if tot is None else tot
-        assert tot.dtype == torch.int64 and tot.is_contiguous() and tuple(tot.shape) == (3, self.slots) and tot.device == self.games.device
+        tot = self._totals(tot)
         _lib.check(self.L.pp_dr_adr_update(self.adr_dev.data_ptr(), self.D, tot.data_ptr(), C.byref(self._state), _lib.stream(self.device)), self.L)
 
     def table(self):
         """dict of device tensors: lo, hi [D] (views of `range`), and games, mean, dropped, widened, narrowed [S]."""
         return dict(lo=self.range[:, 0], hi=self.range[:, 1], games=self.games, mean=self.mean, dropped=self.dropped, widened=self.widened,
                     narrowed=self.narrowed)
+
+    def outputs(self):
+        t = self.table()
+        return dict(adr_lo=t["lo"].clone(), adr_hi=t["hi"].clone(), adr_games=t["games"].clone(), adr_mean=t["mean"].clone())
 
     _SLOT_STATE = ("range", "acc_n", "acc_q", "games", "dropped", "mean", "widened", "narrowed")
 

@@ -112,18 +112,13 @@ class RolloutCollector:
             self.act_line, self.applied = line(a, self.action_delay, COMMAND), z(n, a)
         if self.obs_delay[1] > 0:
             self.obs_line, self.raw_obs = line(num_obs, self.obs_delay, SENSING), z(n, num_obs)
-            self.raw_obs.copy_(env.obs_buf)
-            if self.history is None:
-                self.obs_line.push(self.raw_obs, None, self.obs[0])
-            else:
+            if self.history is not None:
                 self.seen_obs = z(n, num_obs)
-                self.history.push(self.obs_line.push(self.raw_obs, None, self.seen_obs), None, None, None, self.obs[0])
-        elif self.history is None:
-            self.obs[0].copy_(env.obs_buf)
-        else:
+        elif self.history is not None:
             self.cur_obs = z(n, num_obs)
-            self.cur_obs.copy_(env.obs_buf)
-            self.history.push(self.cur_obs, None, None, None, self.obs[0])
+        self._env_obs = self.raw_obs if self.obs_line is not None else self.cur_obs      # where the env step writes; None: straight into obs[t + 1]
+        (self.obs[0] if self._env_obs is None else self._env_obs).copy_(env.obs_buf)
+        self._observe(0, None, None, None)
         self.critic_input = self.priv = None
         if critic_input:
             from .critic_input import CriticInput
@@ -132,6 +127,16 @@ class RolloutCollector:
                 raise ValueError(f"critic_input: {self.critic_input.P} privileged columns, but the network was built with num_priv={getattr(net, 'num_priv', 0)}")
             self.priv = z(self.h + 1, n, self.critic_input.P)
             self.critic_input.gather(self.priv[0])
+
+    def _observe(self, row, done, prev, action):
+        """The env's buffer (`_env_obs`) holds a new observation -> obs[row]: the sensing line's push, then the history's, where there is
+        one.  done: the dones of the step that wrote it; prev, action: obs[row - 1] and the actions that step took.  All None for the
+        first row.  With neither a line nor a history the env wrote obs[row] itself and nothing is launched."""
+        seen = self._env_obs
+        if self.obs_line is not None:
+            seen = self.obs_line.push(seen, done, self.obs[row] if self.history is None else self.seen_obs)
+        if self.history is not None:
+            self.history.push(seen, action, done, prev, self.obs[row])
 
     def _forward(self, t, **kw):
         if self.priv is None:
@@ -145,19 +150,8 @@ class RolloutCollector:
             self.counter += 1
             self._forward(t, sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
             act = self.actions[t] if self.act_line is None else self.act_line.push(self.actions[t], self._done_prev, self.applied)
-            if self.history is not None:
-                seen = self.cur_obs
-                if self.obs_line is None:
-                    self.env.step(act, obs=seen, rew=self.rewards[t], reset=self.dones[t])
-                else:
-                    self.env.step(act, obs=self.raw_obs, rew=self.rewards[t], reset=self.dones[t])
-                    seen = self.obs_line.push(self.raw_obs, self.dones[t], self.seen_obs)
-                self.history.push(seen, self.actions[t], self.dones[t], self.obs[t], self.obs[t + 1])
-            elif self.obs_line is None:
-                self.env.step(act, obs=self.obs[t + 1], rew=self.rewards[t], reset=self.dones[t])
-            else:
-                self.env.step(act, obs=self.raw_obs, rew=self.rewards[t], reset=self.dones[t])
-                self.obs_line.push(self.raw_obs, self.dones[t], self.obs[t + 1])
+            self.env.step(act, obs=self.obs[t + 1] if self._env_obs is None else self._env_obs, rew=self.rewards[t], reset=self.dones[t])
+            self._observe(t + 1, self.dones[t], self.obs[t], self.actions[t])
             if self.serve is not None:
                 self.serve.step(t, self.rewards[t], self.dones[t])
             if self.randomizer is not None:

@@ -4,7 +4,8 @@ policy currently scores worst on.  The reference has no serve curriculum: the ru
 
 `ServeCurriculum` is what PPEnv.set_serve_curriculum and TAEnv.set_serve_curriculum return, built like serve.ServePlan: the override buffer
 (`out`), the per-env and per-bin state, the staging rows of one horizon and the launches — one per control step (`step`), two per epoch
-(`fold`, `update`).  torch owns the memory; nothing here reads the device on the host."""
+(`fold`, `update`).  The staging, the fold and the epoch's sequence are `HorizonStage`'s, which adr.AutoRandomizer shares.  torch owns
+the memory; nothing here reads the device on the host."""
 import ctypes as C
 import math
 
@@ -67,7 +68,49 @@ def grid_parse(flags):
     return out
 
 
-class ServeCurriculum:
+class HorizonStage:
+    """What ServeCurriculum and adr.AutoRandomizer share: the staging of one horizon — per control step and env the slot (a bin; an ADR
+    boundary) a finished game is credited to, -1 for none, and its quantised return —, the fold of a staged horizon into per-slot totals,
+    and the epoch's sequence fold -> (the ranks' sum) -> update.  A subclass sets L, device, num_envs, num_agents, reset_rows and horizon,
+    calls _staging(K), and has its own step(), update(tot) and outputs()."""
+
+    def _staging(self, K):
+        """Allocates `fin` [H, N] int32 (all -1), `fin_q` [H, N] int64, `tot` [3, K] int64 and the fold's scratch.  -> fin."""
+        n, z = self.num_envs, lambda *shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+        self.fin, self.fin_q = torch.full((self.horizon, n), -1, dtype=torch.int32, device=self.device), z(self.horizon, n, dt=torch.int64)
+        self.tot = z(3, K, dt=torch.int64)
+        self._partial = z(int(self.L.pp_serve_curric_fold_bytes(self.horizon * n)), dt=torch.uint8)
+        return self.fin
+
+    def _check_step(self, t, rew_t, reset_t):
+        assert 0 <= t < self.horizon
+        assert rew_t.dtype == torch.float32 and rew_t.is_contiguous() and rew_t.numel() == self.num_agents * self.num_envs
+        assert reset_t.dtype == torch.int64 and reset_t.is_contiguous() and reset_t.numel() == self.reset_rows * self.num_envs
+
+    def _totals(self, tot):
+        """update()'s argument: this rank's `tot` by default, checked."""
+        tot = self.tot if tot is None else tot
+        assert tot.dtype == torch.int64 and tot.is_contiguous() and tot.shape == self.tot.shape and tot.device == self.tot.device
+        return tot
+
+    def fold(self):
+        """The staged horizon -> `tot` [3, K] int64: games, sum of q, dropped games per slot (pp_serve_curric_fold, generic over K)."""
+        _lib.check(self.L.pp_serve_curric_fold(self.fin.data_ptr(), self.fin_q.data_ptr(), self.horizon * self.num_envs, self.tot.shape[1], self.tot.data_ptr(),
+                                               self._partial.data_ptr() if self._partial.numel() else None, _lib.stream(self.device)), self.L)
+        return self.tot
+
+    @torch.no_grad()
+    def epoch(self, reduce=None):
+        """The collected horizon into the stage: fold, reduce(tot) in place where given (data-parallel: the ranks' sum), update.  -> the
+        epoch's named outputs for train_epoch()."""
+        tot = self.fold()
+        if reduce is not None:
+            reduce(tot)
+        self.update(tot)
+        return self.outputs()
+
+
+class ServeCurriculum(HorizonStage):
     grid = staticmethod(grid)
 
     def __init__(self, env, bins, power=1, mix=0.25, alpha=0.3, seed=None, horizon=32):
@@ -92,9 +135,7 @@ class ServeCurriculum:
         z = lambda *shape, dt: torch.zeros(shape, dtype=dt, device=dev)
         self.count, self.next_bin, self.cur_bin, self.ret = z(n, dt=torch.int32), z(n, dt=torch.int32), z(n, dt=torch.int32), z(n, dt=torch.float32)
         self.games, self.mean, self.dropped, self.cdf = z(B, dt=torch.int64), z(B, dt=torch.float32), z(B, dt=torch.int64), z(B, dt=torch.int32)
-        self.fin_bin, self.fin_q = torch.full((self.horizon, n), -1, dtype=torch.int32, device=dev), z(self.horizon, n, dt=torch.int64)
-        self.tot = z(3, B, dt=torch.int64)
-        self._partial = z(int(self.L.pp_serve_curric_fold_bytes(self.horizon * n)), dt=torch.uint8)
+        self.fin_bin = self._staging(B)
         self._state = _lib.ServeCurricState(*(t.data_ptr() for t in (self.count, self.next_bin, self.cur_bin, self.ret, self.games, self.mean,
                                                                      self.dropped, self.cdf)))
         host = _lib.ServeCurric(num_envs=n, env_id_offset=int(tgt["env_id_offset"]), seed=self.seed, form=int(tgt["form"]), layout=self.layout,
@@ -114,23 +155,14 @@ class ServeCurriculum:
     def step(self, t, rew_t, reset_t):
         """The per-step launch (pp_serve_curric_step) after the env step that wrote rew_t [A*N] f32 (unscaled) and reset_t [reset_rows*N]
         int64; stages row t of the horizon.  One launch, no synchronisation; it can be captured."""
-        assert 0 <= t < self.horizon
-        assert rew_t.dtype == torch.float32 and rew_t.is_contiguous() and rew_t.numel() == self.num_agents * self.num_envs
-        assert reset_t.dtype == torch.int64 and reset_t.is_contiguous() and reset_t.numel() == self.reset_rows * self.num_envs
+        self._check_step(t, rew_t, reset_t)
         _lib.check(self.L.pp_serve_curric_step(self.curric_dev.data_ptr(), self.num_envs, rew_t.data_ptr(), reset_t.data_ptr(), C.byref(self._state),
                                                self.out.data_ptr(), self.fin_bin[t].data_ptr(), self.fin_q[t].data_ptr(), _lib.stream(self.device)), self.L)
-
-    def fold(self):
-        """The staged horizon -> `tot` [3, B] int64: games, sum of q, dropped games per bin (pp_serve_curric_fold)."""
-        _lib.check(self.L.pp_serve_curric_fold(self.fin_bin.data_ptr(), self.fin_q.data_ptr(), self.horizon * self.num_envs, self.bins, self.tot.data_ptr(),
-                                               self._partial.data_ptr() if self._partial.numel() else None, _lib.stream(self.device)), self.L)
-        return self.tot
 
     def update(self, tot=None):
         """The totals (default: this rank's `tot`; data-parallel: their sum over the ranks) into mean / games / dropped, and the new table
         (pp_serve_curric_update)."""
-        tot = self.tot if tot is None else tot
-        assert tot.dtype == torch.int64 and tot.is_contiguous() and tuple(tot.shape) == (3, self.bins) and tot.device == self.games.device
+        tot = self._totals(tot)
         _lib.check(self.L.pp_serve_curric_update(self.curric_dev.data_ptr(), self.bins, tot.data_ptr(), C.byref(self._state), _lib.stream(self.device)), self.L)
 
     def table(self):
@@ -138,6 +170,10 @@ class ServeCurriculum:
         cdf = self.cdf.to(torch.int64)
         prob = torch.diff(cdf, prepend=cdf.new_zeros(1)).double() / float(1 << 24)
         return dict(games=self.games, mean=self.mean, dropped=self.dropped, prob=prob)
+
+    def outputs(self):
+        t = self.table()
+        return dict(curriculum_games=t["games"].clone(), curriculum_mean=t["mean"].clone(), curriculum_prob=t["prob"])
 
     def state_dict(self):
         """The resolved bins, the parameters and the per-bin table.  The per-env state is not part of it: the envs restart on resume."""

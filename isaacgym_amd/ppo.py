@@ -89,12 +89,16 @@ import time
 import numpy as np
 import torch
 
-from . import _lib, scene
+from . import _lib, cfgyaml, scene
+from . import adr as adr_mod
+from . import critic_input as critic_input_mod
+from . import curriculum as curriculum_mod
 from . import distributed as D
+from . import history as history_mod
 from ._lib import PPOAdam, PPOLossArgs, PPOMeter, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h and ppenv_ppo_meter.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
 from .latency import delay_range, latency_text
-from .policy import UNITS, NativeActorCritic, RunningMeanStd, sampler_stream_seed
+from .policy import UNITS, NativeActorCritic, RunningMeanStd, layers_from_rlgames_state_dict, sampler_stream_seed
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
 STATS = ("loss", "a_loss", "c_loss", "b_loss", "entropy", "kl", "clip_frac")     # ppenv_ppo_loss_grad's stats[] (include/ppenv_ppo.h)
@@ -490,7 +494,6 @@ class PPOTrainer:
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
                  curriculum=None, randomization=None, adr=None, critic_inputs=(), history=None):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
-        from . import critic_input as critic_input_mod
         critic_inputs = critic_input_mod.parse(critic_inputs)
         if task.randomize:
             raise ValueError("task.randomize: True is not supported by PPOTrainer: it drives the native env below VecTask.step's randomisation hook")
@@ -507,7 +510,6 @@ class PPOTrainer:
         self.rows = env.num_rows                  # actor rows: num_envs x num_agents (T4: 2 actors per env)
         cfg.check(self.rows)
         self.base_num_obs, self.num_actions = env.obs_buf.shape[1], int(task.num_actions)
-        from . import history as history_mod
         self._history = history_mod.parse(history, self.base_num_obs, self.num_actions)      # the width of the network's rows: resolved, with every refusal, first
         self.num_obs = self.base_num_obs if self._history is None else self._history["width"]
         self.seed = int(seed)
@@ -537,8 +539,7 @@ class PPOTrainer:
             rr = env.set_reset_randomization(randomization, seed=tables_seed)
             rr.apply(torch.zeros(rr.reset_rows * env.num_envs, dtype=torch.int64, device=dev))   # the first application draws every env's columns: training starts randomised
         elif adr is not None:
-            from .adr import AutoRandomizer
-            self.adr = AutoRandomizer(env, **dict(adr), seed=tables_seed, horizon=H)
+            self.adr = adr_mod.AutoRandomizer(env, **dict(adr), seed=tables_seed, horizon=H)
         randomizer = self.adr if self.adr is not None else (env.reset_randomization if self.randomization is not None else None)
         # privileged critic inputs: their width sizes the critic's first layer, so it is resolved — with every refusal — before the network is built
         self._critic_inputs = None
@@ -634,17 +635,6 @@ class PPOTrainer:
         self.env.clear_serve_curriculum()
         self.curriculum = None
 
-    @torch.no_grad()
-    def _curriculum_epoch(self):
-        """The collected horizon into the curriculum: fold, the ranks' totals summed, update.  -> the epoch's three [B] tensors."""
-        cur = self.curriculum
-        tot = cur.fold()
-        if self.multi:
-            torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
-        cur.update(tot)
-        t = cur.table()
-        return dict(curriculum_games=t["games"].clone(), curriculum_mean=t["mean"].clone(), curriculum_prob=t["prob"])
-
     def clear_randomization(self):
         """No randomisation again: the plan or the ADR state is dropped, the env's tables are cleared and the collector launches nothing for
         them any more."""
@@ -652,17 +642,6 @@ class PPOTrainer:
         if self.adr is not None or self.randomization is not None:
             self.env.clear_randomization()
         self.adr = self.randomization = None
-
-    @torch.no_grad()
-    def _adr_epoch(self):
-        """The collected horizon into ADR: fold, the ranks' totals summed, update.  -> the epoch's adr_lo, adr_hi [D], adr_games, adr_mean [S]."""
-        a = self.adr
-        tot = a.fold()
-        if self.multi:
-            torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)
-        a.update(tot)
-        t = a.table()
-        return dict(adr_lo=t["lo"].clone(), adr_hi=t["hi"].clone(), adr_games=t["games"].clone(), adr_mean=t["mean"].clone())
 
     def critic_inputs(self):
         """The record of the privileged critic inputs — dict(names=[...], columns=[one count per name], P=the sum) — or None without any."""
@@ -788,8 +767,9 @@ class PPOTrainer:
         skipped0 = self.opt.fields()["skipped"].clone()
         self.net.train()
         self.collect()
-        curric = self._curriculum_epoch() if self.curriculum is not None else None
-        adr = self._adr_epoch() if self.adr is not None else None
+        # the horizon into the curriculum, then into ADR (curriculum.HorizonStage.epoch): data-parallel, the ranks' totals are summed in that order
+        reduce = (lambda tot: torch.distributed.all_reduce(tot, op=torch.distributed.ReduceOp.SUM, group=self.group)) if self.multi else None
+        staged = [stage.epoch(reduce) for stage in (self.curriculum, self.adr) if stage is not None]
         self.meter.update(self.col.rewards, self.col.dones)
         score = self.meter.snapshot()
         ep = self._episodes()
@@ -816,10 +796,8 @@ class PPOTrainer:
         out.update(meter_return=score["mean_reward"], meter_length=score["mean_length"], meter_games=score["current_size"])
         if self.outcome is not None:
             out.update(self._outcomes())
-        if curric is not None:
-            out.update(curric)
-        if adr is not None:
-            out.update(adr)
+        for named in staged:
+            out.update(named)
         return out
 
     # -- checkpoints --
@@ -836,19 +814,13 @@ class PPOTrainer:
         sd = {"model": model, "epoch": self.epoch, "frame": self.frame, "optimizer": self.opt.state_dict(), "normalizer": stats,
               "meter": self.meter.state_dict(), "last_mean_rewards": float(self.last_mean_rewards),
               "latency": {k: v for k, v in self.latency().items() if k != "control_dt"}}
-        if self.task._serve_plan is not None:
-            sd["serve"] = self.serve()
-        if self.curriculum is not None:
-            sd["curriculum"] = self.curriculum.state_dict()
-        if self.randomization is not None:
-            sd["randomization"] = {"frequency": int(self.randomization["frequency"]),
-                                   "tables": {k: {f: (list(v) if isinstance(v, (tuple, list)) else v) for f, v in t.items()} for k, t in self.randomization["tables"].items()}}
-        if self.adr is not None:
-            sd["adr"] = self.adr.state_dict()
-        if self._critic_inputs is not None:
-            sd["critic_inputs"] = self.critic_inputs()
-        if self._history is not None:
-            sd["history"] = self.history()
+        rz, state = self.randomization, lambda stage: None if stage is None else stage.state_dict()
+        plan = None if rz is None else {"frequency": int(rz["frequency"]),
+                                        "tables": {k: {f: (list(v) if isinstance(v, (tuple, list)) else v) for f, v in t.items()} for k, t in rz["tables"].items()}}
+        for key, record in (("serve", self.serve()), ("curriculum", state(self.curriculum)), ("randomization", plan), ("adr", state(self.adr)),
+                            ("critic_inputs", self.critic_inputs()), ("history", self.history())):
+            if record is not None:                                           # an absent feature leaves no key
+                sd[key] = record
         return sd
 
     def save(self, path):
@@ -862,16 +834,12 @@ class PPOTrainer:
         """Resume from save(): network, input and value statistics, log-std, optimizer moments, step count and loss scale, epoch / frame.
         Data-parallel: every rank loads the same file (rank 0's), so all resume identical, each with rank 0's input and value statistics."""
         ck = torch.load(path, map_location=self.device, weights_only=True)
-        from . import critic_input as critic_input_mod
         critic_input_mod.check_record(ck.get("critic_inputs"), self._critic_inputs)   # first: other privileged columns raise before anything is overwritten
-        from . import history as history_mod
         history_mod.check_record(ck.get("history"), self._history)           # likewise: another history is another first layer
-        if self.curriculum is not None and "curriculum" in ck:               # first: other bins raise before anything is overwritten.  A file without one: the table starts fresh
-            self.curriculum.load_state_dict(ck["curriculum"])
-        if self.adr is not None and "adr" in ck:                             # likewise: other dims raise before anything is overwritten
-            self.adr.load_state_dict(ck["adr"])
+        for key, stage in (("curriculum", self.curriculum), ("adr", self.adr)):
+            if stage is not None and key in ck:                              # likewise: other bins, then other dims, raise before anything else is overwritten.  A file without the key: the table starts fresh
+                stage.load_state_dict(ck[key])
         sd, lr = ck["model"], self.learner
-        from .policy import layers_from_rlgames_state_dict
         actor, critic = layers_from_rlgames_state_dict(sd)
         with torch.no_grad():
             for i in range(len(lr.w32)):
@@ -933,6 +901,17 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, c
         paths[kind] = path
         written.append(path)
 
+    def table(module, stage, every, path, epoch, last):
+        """Rank 0, every `every` epochs and at the end: the table of the trainer's `stage` ("curriculum" / "adr"; the module's table_json /
+        table_lines) printed and `path` rewritten."""
+        if every and getattr(trainer, stage) is not None and (epoch % every == 0 or last) and trainer.rank == 0:
+            rows = module.table_json(getattr(trainer, stage), epoch)
+            print("\n".join(module.table_lines(rows)), flush=True)
+            if path:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as fh:
+                    json.dump(rows, fh, indent=1)
+
     while trainer.epoch < total and not stopped:
         res = trainer.train_epoch()
         ran += 1
@@ -960,22 +939,8 @@ def fit(trainer, out_dir, name, print_every=10, max_epochs=None, capture=None, c
                    f" ({vals['outcome_windows']:.0f} windows)" if "outcome_windows" in vals else ""), flush=True)
             if stopped:
                 print(f"score {score} above score_to_win {cfg.score_to_win}: stopping", flush=True)
-        if curriculum_every and trainer.curriculum is not None and (epoch % curriculum_every == 0 or last) and trainer.rank == 0:
-            from .curriculum import table_json, table_lines
-            rows = table_json(trainer.curriculum, epoch)
-            print("\n".join(table_lines(rows)), flush=True)
-            if curriculum_out:
-                os.makedirs(os.path.dirname(os.path.abspath(curriculum_out)), exist_ok=True)
-                with open(curriculum_out, "w") as fh:
-                    json.dump(rows, fh, indent=1)
-        if adr_every and trainer.adr is not None and (epoch % adr_every == 0 or last) and trainer.rank == 0:
-            from . import adr as adr_mod
-            rows = adr_mod.table_json(trainer.adr, epoch)
-            print("\n".join(adr_mod.table_lines(rows)), flush=True)
-            if adr_out:
-                os.makedirs(os.path.dirname(os.path.abspath(adr_out)), exist_ok=True)
-                with open(adr_out, "w") as fh:
-                    json.dump(rows, fh, indent=1)
+        table(curriculum_mod, "curriculum", curriculum_every, curriculum_out, epoch, last)
+        table(adr_mod, "adr", adr_every, adr_out, epoch, last)
     out = dict(epochs=ran, epoch=trainer.epoch, stopped=stopped, reason="score_to_win" if stopped else "max_epochs",
                best_score=trainer.last_mean_rewards, paths=paths, written=written)
     if capture is not None:
@@ -1092,14 +1057,11 @@ def main(argv=None):
     action_delay, obs_delay = delay_range("--action-delay", args.action_delay), delay_range("--obs-delay", args.obs_delay)
     try:
         serve_plan, curriculum = serve_cell_parse(args.serve), None
-        from . import critic_input as critic_input_mod
         critic_inputs = critic_input_mod.parse(args.critic_inputs)
-        from . import history as history_mod
         history = history_mod.parse((args.obs_history, args.action_history))
         if args.curriculum:
             if serve_plan is not None:
                 raise ValueError("--serve together with --curriculum: a plan and a curriculum write the same serve override buffer")
-            from . import curriculum as curriculum_mod
             curriculum_mod.check_parameters(args.curriculum_power, args.curriculum_mix, args.curriculum_alpha)
             curriculum = dict(bins=curriculum_mod.grid(curriculum_mod.grid_parse(args.curriculum)), power=args.curriculum_power, mix=args.curriculum_mix,
                               alpha=args.curriculum_alpha)
@@ -1109,7 +1071,6 @@ def main(argv=None):
                 raise ValueError("--randomize together with --adr: a reset-time plan and ADR write the same randomisation tables")
             if args.adr_low is None or args.adr_high is None:
                 raise ValueError("--adr needs --adr-low and --adr-high: the mean returns at which a boundary moves back in / outward")
-            from . import adr as adr_mod
             frac, games, low, high = adr_mod.check_parameters(args.adr_boundary_frac, args.adr_min_games, args.adr_low, args.adr_high)
             adr = dict(dims=adr_mod.check_dims(adr_mod.parse(args.adr)), boundary_frac=frac, min_games=games, t_low=low, t_high=high)
     except ValueError as e:
@@ -1123,7 +1084,6 @@ def main(argv=None):
                               ("score_to_win", args.score_to_win), ("games_to_track", args.games_to_track)) if v is not None}
     task_cfg = None
     if args.cfg_dir:
-        from . import cfgyaml
         composed = cfgyaml.compose(args.task, args.cfg_dir, overrides={"num_envs": args.num_envs})
         task_cfg = composed["task"]
         for key in ("capture_video", "capture_video_freq", "capture_video_len"):        # the composed cfg's keys are the defaults
@@ -1146,8 +1106,7 @@ def main(argv=None):
         print("reset-time randomisation: " + ", ".join(f"{k} {t['distribution']} {t['operation']} {t['range'][0]:g}..{t['range'][1]:g}"
                                                        for k, t in tr.randomization["tables"].items()), flush=True)
     if rank == 0 and adr is not None:
-        from .adr import table_json, table_lines
-        print("\n".join(table_lines(table_json(tr.adr))), flush=True)
+        print("\n".join(adr_mod.table_lines(adr_mod.table_json(tr.adr))), flush=True)
     if rank == 0 and serve_plan is not None:
         print("serve plan: " + ", ".join(f"{k} {v[0]:g}..{v[1]:g}" for k, v in tr.serve()["cells"][0].items()), flush=True)
     if rank == 0 and curriculum is not None:

@@ -52,7 +52,7 @@ def main():
     def horizon():
         tr.collect()
         if getattr(tr, "adr", None) is not None:
-            tr._adr_epoch()
+            tr.adr.epoch() if hasattr(tr.adr, "epoch") else tr._adr_epoch()      # (--root: a checkout from before HorizonStage.epoch)
         tr.meter.update(tr.col.rewards, tr.col.dones)
         tr.col.next_horizon()
     for _ in range(3):                      # a run that has been going for a while (tools/ppo_epoch_bench.py)

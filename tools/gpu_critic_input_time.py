@@ -44,7 +44,7 @@ def main():
 
     def horizon():
         tr.collect()
-        tr._adr_epoch()
+        tr.adr.epoch() if hasattr(tr.adr, "epoch") else tr._adr_epoch()          # (--root: a checkout from before HorizonStage.epoch)
         tr.meter.update(tr.col.rewards, tr.col.dones)
         tr.col.next_horizon()
 

@@ -46,7 +46,7 @@ def main():
     def horizon():
         tr.collect()
         if getattr(tr, "curriculum", None) is not None:
-            tr._curriculum_epoch()
+            tr.curriculum.epoch() if hasattr(tr.curriculum, "epoch") else tr._curriculum_epoch()      # (--root: a checkout from before HorizonStage.epoch)
         tr.meter.update(tr.col.rewards, tr.col.dones)
         tr.col.next_horizon()
     for _ in range(3):                      # a run that has been going for a while (tools/ppo_epoch_bench.py)
