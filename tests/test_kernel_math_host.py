@@ -69,7 +69,8 @@ def test_single_step_parity_vs_oracle(oracle_lib, variant):
 
 
 def test_gentle_policy_single_step_is_tight(oracle_lib):
-    """With small smooth actions (no flailing at the limits) plain rtol 1e-4 / atol 1e-5 holds."""
+    """With small smooth actions (no flailing at the limits) plain rtol 1e-4 / atol 1e-5 holds.  (The stops, the speed cap and the torque limit
+    themselves are not left to flailing: tests/joint_limit_scenarios.py scripts and counts them, tests/test_joint_limits_host.py / _gpu.py.)"""
     n = 128
     cfg = scene.build_config("TT", num_envs=n, seed=3)
     o = oracle_lib.OracleEnv(cfg)

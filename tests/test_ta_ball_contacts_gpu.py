@@ -18,10 +18,11 @@ from isaacgym_amd import scene
 from test_ta_ball_contacts_host import N, SEED
 
 
-def run_kernel(oracle_lib, env, n, dr, per_env_irb, label, oa):
+def run_kernel(oracle_lib, env, n, dr, per_env_irb, label, oa, run=None):
+    """run: (params, irb, tables, steps) of another scripted suite's oracle_run with this module's step dicts (tests/test_ta_joint_limits_gpu.py)."""
     import torch
     cfg, m = scene.build_ta_scene(n), scene.build_ta_model()
-    p, irb, tables, steps = sc.oracle_run(n, SEED, dr, per_env_irb)
+    p, irb, tables, steps = sc.oracle_run(n, SEED, dr, per_env_irb) if run is None else run
     assert env.initial_rb_states.shape == irb.shape
     env.initial_rb_states.copy_(torch.from_numpy(irb))
     log = ExclusionLog(label, bound=sc.EXCLUDED_BOUND)
