@@ -25,7 +25,8 @@ SOURCES = [os.path.join(_PKG, "csrc", "ppenv.hip"), os.path.join(_PKG, "csrc", "
            os.path.join(_PKG, "csrc", "ppenv_play_pair.hip"), os.path.join(_PKG, "csrc", "ppenv_play_act.hip"),
            os.path.join(_PKG, "csrc", "ppenv_play_delay.hip"), os.path.join(_PKG, "csrc", "ppenv_train_delay.hip"),
            os.path.join(_PKG, "csrc", "ppenv_serve_curric.hip"), os.path.join(_PKG, "csrc", "ppenv_dr_adr.hip"),
-           os.path.join(_PKG, "csrc", "ppenv_critic_input.hip"), os.path.join(_PKG, "csrc", "ppenv_history.hip")]
+           os.path.join(_PKG, "csrc", "ppenv_critic_input.hip"), os.path.join(_PKG, "csrc", "ppenv_history.hip"),
+           os.path.join(_PKG, "csrc", "ppenv_sensor.hip")]
 HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1.h"), os.path.join(_PKG, "csrc", "ppenv_ta_device.h"), os.path.join(_PKG, "csrc", "ppenv_ta_task.h"), os.path.join(_PKG, "csrc", "ppenv_ta_chain.h"), os.path.join(_PKG, "csrc", "ppenv_model_g1_ta.h"),
            os.path.join(ROOT, "include", "ppenv.h"), os.path.join(ROOT, "include", "ppenv_policy.h"), os.path.join(ROOT, "include", "ppenv_ppo.h"),
            os.path.join(_PKG, "csrc", "ppenv_dr_device.h"), os.path.join(ROOT, "include", "ppenv_dr.h"),
@@ -42,6 +43,7 @@ HEADERS = [os.path.join(_PKG, "csrc", "ppenv_device.h"), os.path.join(_PKG, "csr
            os.path.join(_PKG, "csrc", "ppenv_dr_adr_device.h"), os.path.join(ROOT, "include", "ppenv_dr_adr.h"),
            os.path.join(_PKG, "csrc", "ppenv_critic_input_device.h"), os.path.join(ROOT, "include", "ppenv_critic_input.h"),
            os.path.join(_PKG, "csrc", "ppenv_history_device.h"), os.path.join(ROOT, "include", "ppenv_history.h"),
+           os.path.join(_PKG, "csrc", "ppenv_sensor_device.h"), os.path.join(ROOT, "include", "ppenv_sensor.h"),
            os.path.join(_PKG, "csrc", "ppenv_host.h"), os.path.join(_PKG, "csrc", "ppenv_reduce_device.h"), os.path.join(_PKG, "csrc", "ppenv_play_host.h")]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize", "-mllvm", "-disable-vector-combine", "-fno-signed-zeros", "-ffinite-math-only", "-fPIC", "-shared"]
 # per translation unit, after HIPCC_FLAGS: the optimizer's step skip must see an inf / nan gradient norm; the play totals' minima / maxima start at +-inf;
@@ -52,7 +54,8 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-slp-vectorize
 # the serve curriculum draws with the serve plan's arithmetic and rounds every fp64 operation of its table on its own, as its host build does;
 # ADR draws with the reset-time plan's arithmetic, stages returns as the serve curriculum does and rounds every operation of its update on its own;
 # the privileged critic inputs copy a float bit for bit (a negative zero keeps its sign) and round the normaliser's two operations on their own;
-# the observation and action history moves words bit for bit, and its clamp keeps a negative zero's sign and turns a NaN action into lo
+# the observation and action history moves words bit for bit, and its clamp keeps a negative zero's sign and turns a NaN action into lo;
+# the sensor line rounds s * g before adding it, and its level draws' product before their sum, as its host build does, and a row of zero amplitude copies bits
 SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["-fno-finite-math-only"], "ppenv_render.hip": ["-fno-finite-math-only"],
                 "ppenv_ppo_meter.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_serve.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
@@ -60,6 +63,7 @@ SOURCE_FLAGS = {"ppenv_ppo.hip": ["-fno-finite-math-only"], "ppenv_play.hip": ["
                 "ppenv_dr_adr.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_critic_input.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_history.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
+                "ppenv_sensor.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_pair.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"],
                 "ppenv_play_act.hip": ["-fno-finite-math-only", "-fsigned-zeros", "-ffp-contract=off"]}
 
@@ -145,6 +149,12 @@ PLAY_DELAY_MAX, PLAY_DELAY_MAX_WIDTH = 15, 512                                  
 class TrainDelayConsts(C.Structure):
     """ctypes mirror of pp_train_delay_consts (include/ppenv_train_delay.h)."""
     _fields_ = [("lo", C.c_int32), ("hi", C.c_int32), ("seed", C.c_uint64), ("env_id_offset", C.c_int32), ("channel", C.c_int32)]
+
+
+class SensorConsts(C.Structure):
+    """ctypes mirror of pp_sensor_consts (include/ppenv_sensor.h)."""
+    _fields_ = [("sigma_lo", C.c_float), ("sigma_hi", C.c_float), ("drop_lo", C.c_float), ("drop_hi", C.c_float), ("draw", C.c_int32), ("seed", C.c_uint64),
+                ("env_id_offset", C.c_int32), ("key_period", C.c_int32), ("channel", C.c_int32)]
 
 
 class PlayActLimit(C.Structure):
@@ -523,6 +533,12 @@ def load(path):
     L.pp_train_delay_table_bytes.argtypes = [i32]
     L.pp_train_delay_reset.argtypes = [i32, vp, vp, vp]
     L.pp_train_delay_push.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(TrainDelayConsts), vp, vp, vp, vp, vp, i64, vp]
+    # ---- include/ppenv_sensor.h
+    L.pp_sensor_table_bytes.restype = L.pp_sensor_held_bytes.restype = sz
+    L.pp_sensor_table_bytes.argtypes = [i32]
+    L.pp_sensor_held_bytes.argtypes = [i32, i32]
+    L.pp_sensor_reset.argtypes = [i32, vp, vp, vp]
+    L.pp_sensor_push.argtypes = [vp, i64, vp, i32, i32, i32, C.POINTER(SensorConsts), vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     # ---- include/ppenv_ppo_meter.h
     L.ppo_meter_partial_bytes.restype = sz
     L.ppo_meter_partial_bytes.argtypes = [i32, i32]

@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from . import history as history_mod
+from . import sensor as sensor_mod
 from .latency import COMMAND, SENSING, DelayLine, delay_range
 
 
@@ -52,6 +53,18 @@ class RolloutCollector:
     `applied`.  A path whose hi is 0 is not built — no allocation, no launch, the attribute is None — so the default collector is the
     collector without the feature.
 
+    obs_noise, action_noise (an amplitude S, or a (lo, hi) range), obs_drop, action_drop (a probability, or a range): sensor noise and sample
+    dropouts, the levels drawn anew per row at every episode start on the device (sensor.SensorLine with draw = 1; include/ppenv_sensor.h,
+    keyed by `sensor_seed` — a STREAM seed, scene.stream_seed(seed, STREAM_SENSOR) — and `env_id_offset`; scene.sensor_draws predicts
+    them).  sensor_columns: dict(obs_noise_columns=, obs_drop_columns=, action_noise_columns=, action_drop_columns=) of column specs
+    (sensor.columns / sensor.hold_columns; `task` names the observation's column groups).  The order is the Player's: sensed =
+    obs_sensor.push(obs, done_prev); seen = obs_line.push(sensed, ...); (history); a = policy(...); delayed = act_line.push(a, ...);
+    a_applied = act_sensor.push(delayed, done_prev); env.step(a_applied).  With a sensing sensor line (`obs_sensor`) the env writes the
+    clean `raw_obs`, which stays the `raw_obs` critic input, and the line's output goes to the next stage's input (`sensed_obs`) or, where
+    it is the last stage, straight into obs[t + 1]: `out` is the caller's pointer, no copy.  The command line (`act_sensor`) writes
+    `applied`; actions[t] stays the policy's own.  A path whose amplitude and dropout ranges are both (0, 0) is not built — no
+    allocation, no launch, the attribute is None.
+
     serve: what keeps the env's serve override buffer — a serve.ServePlan or a curriculum.ServeCurriculum set on `env` — an object with
     step(t, rew_t, reset_t), called right after the env step of row t with rewards[t] (unscaled) and dones[t]: one launch, no copy.  A
     plan runs its apply(dones[t]); a curriculum also credits the games that ended and stages row t for the trainer's fold().  None (the
@@ -78,8 +91,16 @@ class RolloutCollector:
     allocated or launched, and `history`, `cur_obs` and `seen_obs` are None."""
 
     def __init__(self, env, net, horizon=32, gamma=0.99, tau=0.95, reward_scale=0.01, sigma=None, seed=0, action_delay=0, obs_delay=0,
-                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None, critic_input=None, history=None):
+                 latency_seed=0, env_id_offset=0, serve=None, randomizer=None, critic_input=None, history=None, obs_noise=0.0, obs_drop=0.0, action_noise=0.0,
+                 action_drop=0.0, sensor_columns=None, sensor_seed=0, task=None):
         self.action_delay, self.obs_delay = delay_range("action_delay", action_delay), delay_range("obs_delay", obs_delay)
+        self.sensor_levels = dict(obs_noise=sensor_mod.sigma_range("obs_noise", obs_noise), obs_drop=sensor_mod.drop_range("obs_drop", obs_drop),
+                                  action_noise=sensor_mod.sigma_range("action_noise", action_noise), action_drop=sensor_mod.drop_range("action_drop", action_drop))
+        names = tuple(f"{axis}_columns" for axis in sensor_mod.AXES)
+        unknown = [k for k in (sensor_columns or {}) if k not in names]
+        if unknown:
+            raise ValueError(f"sensor_columns: unknown key {unknown[0]!r}; the keys are {', '.join(names)}")
+        self.sensor_columns = {k: (sensor_columns or {}).get(k) for k in names}
         self.env, self.net, self.h = env, net, int(horizon)
         self.gamma, self.tau, self.reward_scale, self.seed = float(gamma), float(tau), float(reward_scale), int(seed)   # yaml:55-59: scale_value 0.01, gamma 0.99, tau 0.95
         n, dev, a = env.num_rows, env.device, net.num_actions        # actor rows: A * N for the 4-actor variant
@@ -106,17 +127,36 @@ class RolloutCollector:
         self.randomizer = randomizer
         self.on_step = None                   # called with no arguments right after every env.step of collect() (render.TrainingCapture.on_step)
         self.act_line = self.obs_line = self.applied = self.raw_obs = None
+        self.obs_sensor = self.act_sensor = self.sensed_obs = self.delayed = None
         self._done_prev = None                # the dones of the last env step (a row of `dones`); None before any step
         line = lambda width, rng, channel: DelayLine(n, width, rng[0], rng[1], dev, env.num_agents, latency_seed, env_id_offset, channel)
+
+        def sensor_line(path, width, channel):
+            scale = sensor_mod.columns(task, self.sensor_columns[f"{path}_noise_columns"], width, channel, name=f"{path}_noise_columns")
+            hold = sensor_mod.hold_columns(task, self.sensor_columns[f"{path}_drop_columns"], width, channel, name=f"{path}_drop_columns")
+            sg, dp = self.sensor_levels[f"{path}_noise"], self.sensor_levels[f"{path}_drop"]
+            if sg[1] == 0.0 and dp[1] == 0.0:
+                return None
+            return sensor_mod.SensorLine(n, width, dev, num_agents=env.num_agents, sigma=sg, drop=dp, columns=scale, hold_columns=hold, seed=sensor_seed,
+                                         env_id_offset=env_id_offset, channel=channel)
+        self.obs_sensor, self.act_sensor = sensor_line("obs", num_obs, sensor_mod.SENSING), sensor_line("action", a, sensor_mod.COMMAND)
         if self.action_delay[1] > 0:
-            self.act_line, self.applied = line(a, self.action_delay, COMMAND), z(n, a)
+            self.act_line = line(a, self.action_delay, COMMAND)
+        if self.act_line is not None or self.act_sensor is not None:
+            self.applied = z(n, a)
+        if self.act_line is not None and self.act_sensor is not None:
+            self.delayed = z(n, a)                              # the command line's output, the command sensor's input
         if self.obs_delay[1] > 0:
-            self.obs_line, self.raw_obs = line(num_obs, self.obs_delay, SENSING), z(n, num_obs)
-            if self.history is not None:
+            self.obs_line = line(num_obs, self.obs_delay, SENSING)
+        if self.obs_line is not None or self.obs_sensor is not None:
+            self.raw_obs = z(n, num_obs)
+            if self.obs_line is not None and self.history is not None:
                 self.seen_obs = z(n, num_obs)
+            if self.obs_sensor is not None and (self.obs_line is not None or self.history is not None):
+                self.sensed_obs = z(n, num_obs)
         elif self.history is not None:
             self.cur_obs = z(n, num_obs)
-        self._env_obs = self.raw_obs if self.obs_line is not None else self.cur_obs      # where the env step writes; None: straight into obs[t + 1]
+        self._env_obs = self.raw_obs if self.raw_obs is not None else self.cur_obs      # where the env step writes; None: straight into obs[t + 1]
         (self.obs[0] if self._env_obs is None else self._env_obs).copy_(env.obs_buf)
         self._observe(0, None, None, None)
         self.critic_input = self.priv = None
@@ -129,10 +169,13 @@ class RolloutCollector:
             self.critic_input.gather(self.priv[0])
 
     def _observe(self, row, done, prev, action):
-        """The env's buffer (`_env_obs`) holds a new observation -> obs[row]: the sensing line's push, then the history's, where there is
-        one.  done: the dones of the step that wrote it; prev, action: obs[row - 1] and the actions that step took.  All None for the
-        first row.  With neither a line nor a history the env wrote obs[row] itself and nothing is launched."""
+        """The env's buffer (`_env_obs`) holds a new observation -> obs[row]: the sensing sensor's push, then the sensing line's, then the
+        history's, where there is one; the last stage writes obs[row] itself.  done: the dones of the step that wrote it; prev, action:
+        obs[row - 1] and the actions that step took.  All None for the first row.  With no stage the env wrote obs[row] itself and nothing
+        is launched."""
         seen = self._env_obs
+        if self.obs_sensor is not None:
+            seen = self.obs_sensor.push(seen, done, self.obs[row] if self.sensed_obs is None else self.sensed_obs)
         if self.obs_line is not None:
             seen = self.obs_line.push(seen, done, self.obs[row] if self.history is None else self.seen_obs)
         if self.history is not None:
@@ -149,7 +192,11 @@ class RolloutCollector:
         for t in range(self.h):
             self.counter += 1
             self._forward(t, sample=dict(actions=self.actions[t], sigma=self.sigma, seed=self.seed, counter=self.counter, neglogp=self.neglogp[t]))
-            act = self.actions[t] if self.act_line is None else self.act_line.push(self.actions[t], self._done_prev, self.applied)
+            act = self.actions[t]
+            if self.act_line is not None:
+                act = self.act_line.push(act, self._done_prev, self.applied if self.act_sensor is None else self.delayed)
+            if self.act_sensor is not None:
+                act = self.act_sensor.push(act, self._done_prev, self.applied)
             self.env.step(act, obs=self.obs[t + 1] if self._env_obs is None else self._env_obs, rew=self.rewards[t], reset=self.dones[t])
             self._observe(t + 1, self.dones[t], self.obs[t], self.actions[t])
             if self.serve is not None:

@@ -79,8 +79,18 @@ play flag, the checkpoint decides.  The player then stacks the seen observations
 control step and distinct record (history.HistoryStack.advance, after the sensing line, before the policy), and the result gains `history`.
 With --against a history checkpoint and a plain one play the same balls in one pass.  Without such a checkpoint nothing is built.
 
-Out of scope: delays drawn per episode in the player (fixed-delay sweeps evaluate a policy trained under them), action hold / policy decimation,
-per-cell observation or action noise, a VecTask-level latency setting; sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
+Sensor noise and dropouts.  `--obs-noise S --obs-drop P --action-noise S --action-drop P`, or the sweep axes obs_noise, obs_drop, action_noise,
+action_drop (`--sweep obs_noise=0,0.01,0.02 --paired`): a sensor line on the sensing path and one on the command path (isaacgym_amd.sensor.SensorLine;
+include/ppenv_sensor.h holds the rule) add per-cell Gaussian noise with a per-column scale and drop samples with a per-cell probability, holding
+the last delivered values; `--obs-noise-columns "ball_pos=1,ball_vel=4"` and `--obs-drop-columns ball_pos,ball_vel` say which columns (the camera's,
+say) — NAME[=SCALE] or LO:HI[=SCALE], default all.  One launch per line and control step, keyed (seed, env, episode, step): with --paired the cells
+see the same standard normals and drop draws.  The sensing line comes before the observation delay, the command line after the action delay; the
+env's own clamp still applies.  The result gains `sensor`, the summary a `sensor:` line, and --sweep-out / --paired-out carry the axes in each
+`cell`.  A line whose levels are all zero is not built.  This is not the step kernels' by-value noise (one amplitude per simulation): those stay.
+
+Out of scope: sensor levels drawn per episode in the player (fixed-level sweeps evaluate a policy trained under drawn ones, as with delays),
+correlated or coloured noise, bias, drift, quantisation; delays drawn per episode in the player (fixed-delay sweeps evaluate a policy trained under them), action hold / policy decimation,
+a VecTask-level latency setting; sweeping noise amplitudes or gravity (one by-value constant per simulation: several passes), per-group outcome counts,
 paired sampler noise, anything in the trainer; capturing the play loop in a HIP graph (VecTask.step cannot be captured); multi-rank play; the rl_games
 `Runner` / `player_factory` shim (rl_games itself is absent); mp4 output (a run is captured to GIF / PNG / npy: `Player(recorder=...)`,
 `--capture`, isaacgym_amd.render); the observer, PBT and W&B hooks.
@@ -96,5 +106,5 @@ from .cli import actuator_option, main, make_recorder, make_renderer, parse_args
 from .player import Player, actuator_limits, control_dt_of
 from .report import (ACT_INT_FIELDS, ACT_MAX_FIELDS, ACT_SUM_FIELDS, OUTCOME_PRINTS, act_totals_dict, actuator_summary, actuator_table, cell_text,
                      group_line, group_summary, latency_line, outcome_lines, outcomes_dict, pair_line, pair_summary, pair_totals_dict, sum_act_totals,
-                     sum_totals, summarize, totals_dict)
-from .sweep import DELAY_AXES, SERVE_AXES, Sweep, baseline_cells, delay_steps
+                     sensor_line, sum_totals, summarize, totals_dict)
+from .sweep import DELAY_AXES, SENSOR_AXES, SERVE_AXES, Sweep, baseline_cells, delay_steps, sensor_level

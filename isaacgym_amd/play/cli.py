@@ -4,8 +4,8 @@ import json
 
 from .accounting import ACT_THRESHOLDS, DELAY_MAX
 from .player import Player
-from .report import actuator_table, cell_text, group_line, latency_line, outcome_lines, pair_line
-from .sweep import Sweep
+from .report import actuator_table, cell_text, group_line, latency_line, outcome_lines, pair_line, sensor_line
+from .sweep import SENSOR_AXES, Sweep, sensor_level
 
 
 def parse_args(argv=None):
@@ -25,7 +25,8 @@ def parse_args(argv=None):
                     "one axis each; the envs are split into one group per cell and --games is per cell): AXIS is dof_stiffness_scale, dof_damping_scale, "
                     "link_mass_scale, restitution_scale or friction_scale, or one row of a table as NAME[ROW], or a serve axis: serve_speed, serve_tilt, "
                     "serve_tilt_z (degrees; may be negative), ball_y, ball_z (27-dof task), or a latency axis in whole control steps (0..15): action_delay, "
-                    "obs_delay; SPEC is lo:hi:count (inclusive) or v0,v1,...")
+                    "obs_delay, or a sensor axis: obs_noise, action_noise (an amplitude >= 0), obs_drop, action_drop (a probability 0..1); SPEC is lo:hi:count "
+                    "(inclusive) or v0,v1,...")
     ap.add_argument("--paired", action="store_true", help="with --sweep: env i of every cell is served the same sequence of balls (common random numbers), "
                     "so the serve noise cancels in the difference of two cells")
     ap.add_argument("--sweep-out", default=None, metavar="FILE.json", help="with --sweep: write the per-cell results (the result's `groups`) to FILE.json")
@@ -48,6 +49,15 @@ def parse_args(argv=None):
                     "name action_delay")
     ap.add_argument("--obs-delay", type=int, default=0, metavar="K", help=f"control latency of the sensing path: the policy sees the observation of K control "
                     f"steps ago (0..{DELAY_MAX}); with --sweep, the value of the cells that do not name obs_delay")
+    for path, what in (("obs", "the observations the policy sees (before --obs-delay)"), ("action", "the commands the env consumes (after --action-delay)")):
+        ap.add_argument(f"--{path}-noise", type=float, default=0.0, metavar="S", help=f"Gaussian noise of amplitude S x the column's scale on {what}, drawn on the "
+                        f"device per env, episode and step; with --sweep, the value of the cells that do not name {path}_noise")
+        ap.add_argument(f"--{path}-drop", type=float, default=0.0, metavar="P", help=f"each control step, with probability P (0..1), {what} are the last delivered "
+                        f"ones again in the hold columns (never an episode's first sample); with --sweep, the value of the cells that do not name {path}_drop")
+        ap.add_argument(f"--{path}-noise-columns", default=None, metavar="SPEC", help=f"the noised columns and their scales: comma-separated NAME[=SCALE] or "
+                        "LO:HI[=SCALE] (HI exclusive), e.g. ball_pos=1,ball_vel=4,60:67=0.5; NAME is all" +
+                        (", body_pos, body_vel, dof_pos, dof_vel, ball_pos, ball_vel (7-dof and 4-actor tasks)" if path == "obs" else "") + "; default all=1")
+        ap.add_argument(f"--{path}-drop-columns", default=None, metavar="SPEC", help="the columns a dropout holds: comma-separated NAME or LO:HI; default all")
     ap.add_argument("--capture", default=None, metavar="FILE", help="record the run to FILE: .gif, .png (numbered files) or .npy (isaacgym_amd.render)")
     ap.add_argument("--capture-envs", default="0", help="comma-separated env ids to draw, side by side (at most 16)")
     ap.add_argument("--capture-len", type=int, default=300, help="frames kept: the last this many")
@@ -85,6 +95,16 @@ def parse_args(argv=None):
     for flag, axis in (("--action-delay", "action_delay"), ("--obs-delay", "obs_delay")):
         if not 0 <= getattr(args, axis) <= DELAY_MAX:
             ap.error(f"{flag} is a number of whole control steps 0..{DELAY_MAX}")
+    for axis in SENSOR_AXES:
+        try:
+            sensor_level(axis, getattr(args, axis))
+        except ValueError as e:
+            ap.error("--" + axis.replace("_", "-") + str(e).split(":", 1)[1])
+    try:
+        from .. import sensor
+        sensor.check_specs(args.task, {f"{a}_columns": getattr(args, f"{a}_columns") for a in SENSOR_AXES}, flag=lambda key: "--" + key.replace("_", "-"))
+    except ValueError as e:
+        ap.error(str(e))
     if args.sweep:
         try:
             Sweep.parse(args.sweep)
@@ -142,6 +162,8 @@ def print_report(args, task, res, recorder):
     print(f"av reward: {res['av_reward']} av steps: {res['av_steps']}")
     if "latency" in res:
         print(latency_line(res["latency"]))
+    if "sensor" in res:
+        print(sensor_line(res["sensor"]))
     for k, rec in enumerate(res.get("history", ())):                          # the checkpoints decide: one line per distinct policy
         print(f"history: checkpoint {k}: " + ("none" if rec is None else f"{rec['obs']} observations + {rec['actions']} actions back, {rec['num_obs']} -> {rec['width']} columns"))
     if args.outcomes:
@@ -167,7 +189,7 @@ def print_report(args, task, res, recorder):
         print(f"wrote {args.sweep_out}")
     if args.paired_out:
         with open(args.paired_out, "w") as fh:
-            json.dump(dict(res["paired_diff"], latency=res["latency"]) if "latency" in res else res["paired_diff"], fh, indent=1)
+            json.dump(dict(res["paired_diff"], **{k: res[k] for k in ("latency", "sensor") if k in res}), fh, indent=1)
         print(f"wrote {args.paired_out}")
     print(f"{res['steps_played']} control steps x {task.num_envs} envs in {res['seconds']:.3f} s", flush=True)
     if recorder is not None and args.capture_trajectory:
@@ -195,7 +217,8 @@ def main(argv=None):
         (policy, sweep, baseline), paired_diff = against_cells(args, task, policy, sweep), True
     pl = Player(task, policy, games_num=args.games, deterministic=not args.stochastic, seed=args.seed, poll_every=args.poll_every,
                 max_steps=args.max_steps, sigma=args.sigma, recorder=recorder, outcomes=args.outcomes, sweep=sweep, paired_diff=paired_diff,
-                baseline=baseline, actuators=actuator_option(args), action_delay=args.action_delay, obs_delay=args.obs_delay)
+                baseline=baseline, actuators=actuator_option(args), action_delay=args.action_delay, obs_delay=args.obs_delay,
+                **{k: getattr(args, k) for k in SENSOR_AXES + tuple(f"{a}_columns" for a in SENSOR_AXES)})
     last = dict(games=0, steps=0, reward=[0.0])
 
     def on_poll(tot):                     # rl_games prints `reward: ... steps: ...` per finished batch: here, the games since the last poll

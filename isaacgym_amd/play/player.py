@@ -5,10 +5,11 @@ import time
 import numpy as np
 import torch
 
+from .. import scene, sensor
 from .._lib import TAOutcome
 from .accounting import ACT_THRESHOLDS, ActuatorStats, Delay, EpisodeStats, GroupStats, PairStats, _read_structs
 from .report import actuator_summary, group_summary, outcomes_dict, pair_summary, sum_act_totals, sum_totals, summarize
-from .sweep import baseline_cells, cell_delays
+from .sweep import SENSOR_AXES, baseline_cells, cell_delays, cell_sensors
 
 
 def actuator_limits(task):
@@ -69,6 +70,20 @@ class Player:
     policy's raw output (the actuator report's clip share reads it), `applied_actions` is what the env consumed, `policy_obs` what the
     policy saw.  The lines sit between the policy and the task and compose with everything above, a `randomize: True` task included.  With
     a line in use the result gains `latency` = dict(control_dt, action_delay=[per cell], obs_delay=[per cell]).
+    obs_noise, action_noise (an amplitude >= 0), obs_drop, action_drop (a probability 0 .. 1): sensor noise and sample dropouts, for every
+    env — or, with a sweep, for the cells that do not name the axis of that name (SENSOR_AXES).  Two sensor lines (sensor.SensorLine;
+    include/ppenv_sensor.h) sit beside the delay lines, the sensing one BEFORE the delay and the command one AFTER it:
+    sensed = obs_sensor.push(obs, done_prev); seen = obs_line.push(sensed, ...); (history); a = policy.act(...); delayed =
+    act_line.push(a, ...); a_applied = act_sensor.push(delayed, done_prev); task.step(a_applied) — the env's own clamp still applies.
+    Row r of a line adds level[r] * col_scale[c] * N(0, 1) to column c and, with probability drop[r] per control step (never on an episode's
+    first sample), delivers in its hold columns what it delivered last; the draws are keyed (seed, env, episode, step).  *_noise_columns
+    gives col_scale and *_drop_columns the hold columns, as sensor.columns / sensor.hold_columns parse them ("ball_pos=1,ball_vel=4,60:67=0.5";
+    default every column, scale 1; the command path takes `all` and ranges).  With sweep.paired the lines get key_period = the envs per
+    cell: env i of every cell sees the same standard normals and the same drop draws, so cells of equal values stay bitwise replicas.  A
+    line whose amplitudes and dropout probabilities are all zero is not built — no allocation, no launch — so the defaults are the player
+    without the feature byte for byte.  `policy_obs` / `applied_actions` keep their meaning: what the policy saw, what the env consumed.
+    With a line in use the result gains `sensor` = dict(obs_noise=[per cell], obs_drop=[...], action_noise=[...], action_drop=[...],
+    columns={the four specs}).  The levels are fixed per cell: a policy trained under per-episode drawn levels is evaluated on a grid.
     A policy with an observation and action history (policy.history: the checkpoint decides, there is no argument here; include/
     ppenv_history.h) is accepted when its base_num_obs is the task's num_obs and its network is history["width"] wide.  The player then
     keeps one history.HistoryStack per distinct record over ALL rows, and per control step: seen = obs_line.push(...) or the raw obs;
@@ -81,7 +96,9 @@ class Player:
     that struct's own, and start() / end_sweep() leave the task's randomisation and serve plan alone."""
 
     def __init__(self, task, policy, games_num=2000, deterministic=True, seed=0, poll_every=64, max_steps=108000, sigma=None, recorder=None,
-                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None, actuators=False, action_delay=0, obs_delay=0):
+                 outcomes=False, sweep=None, paired_diff=False, baseline=0, pair_episodes=None, actuators=False, action_delay=0, obs_delay=0,
+                 obs_noise=0.0, obs_drop=0.0, action_noise=0.0, action_drop=0.0, obs_noise_columns=None, obs_drop_columns=None, action_noise_columns=None,
+                 action_drop_columns=None):
         for name, v in (("games_num", games_num), ("poll_every", poll_every), ("max_steps", max_steps)):
             if int(v) != v or int(v) < 1:
                 raise ValueError(f"{name}: {v!r} is not a positive integer")
@@ -153,6 +170,13 @@ class Player:
         # a line whose delays are all zero is not built: that path is the player without the feature
         self._act_line = Delay(rows, task.num_actions, per_row["action_delay"], sim, A) if per_row["action_delay"].any() else None
         self._obs_line = Delay(rows, task.num_obs, per_row["obs_delay"], sim, A) if per_row["obs_delay"].any() else None
+        # a sensor line whose amplitude and dropout tables are all zero is not built either
+        self._cell_sensors = cell_sensors(self._cells, obs_noise, obs_drop, action_noise, action_drop)
+        self._sensor_columns = dict(obs_noise_columns=obs_noise_columns, obs_drop_columns=obs_drop_columns, action_noise_columns=action_noise_columns,
+                                    action_drop_columns=action_drop_columns)
+        self.sensor_seed = scene.stream_seed(self.seed, scene.STREAM_SENSOR)
+        self._obs_sensor, self._act_sensor = (self._sensor_line(path, width, channel, A * S, S if sweep is not None and sweep.paired else 0)
+                                              for path, width, channel in (("obs", task.num_obs, sensor.SENSING), ("action", task.num_actions, sensor.COMMAND)))
         self._done_prev = None
         # one stack per distinct history record, each over all rows: a policy without a history builds none
         self._stacks, self._wide = {}, {}
@@ -180,6 +204,21 @@ class Player:
         self.steps_played = 0
         self.actions = self.applied_actions = self.policy_obs = None
         self._obs = None
+
+    def _sensor_line(self, path, width, channel, rows_per_cell, key_period):
+        """The sensor line of one path ("obs" or "action") over all rows, or None where every cell's amplitude and dropout are zero.  The
+        column specs are parsed either way: a bad one is refused whether or not it is used."""
+        scale = sensor.columns(self.task, self._sensor_columns[f"{path}_noise_columns"], width, channel, name=f"{path}_noise_columns")
+        hold = sensor.hold_columns(self.task, self._sensor_columns[f"{path}_drop_columns"], width, channel, name=f"{path}_drop_columns")
+        sigma, drop = (np.repeat(np.asarray(self._cell_sensors[f"{path}_{kind}"], np.float32), rows_per_cell) for kind in ("noise", "drop"))
+        if not sigma.any() and not drop.any():
+            return None
+        return sensor.SensorLine(sigma.size, width, torch.device(self.task.device), num_agents=self.num_agents, sigma=sigma, drop=drop, columns=scale,
+                                 hold_columns=hold, seed=self.sensor_seed, key_period=key_period, channel=channel)
+
+    def sensors(self):
+        """run()'s `sensor`: per cell (one entry without a sweep) the four levels, and the four column specs as given."""
+        return dict(**{axis: list(per) for axis, per in self._cell_sensors.items()}, columns=dict(self._sensor_columns))
 
     @staticmethod
     def _key(policy):
@@ -222,7 +261,7 @@ class Player:
             self.pairs.reset()
         if self.act is not None:
             self.act.reset()
-        for line in (self._act_line, self._obs_line):
+        for line in (self._act_line, self._obs_line, self._obs_sensor, self._act_sensor):
             if line is not None:
                 line.reset()
         for stack in self._stacks.values():
@@ -245,10 +284,12 @@ class Player:
         return self._cell_actions
 
     def step(self):
-        """One control step: (obs line ->) policy (-> action line) -> task.step -> accumulate (-> record, with paired_diff).  No host read."""
+        """One control step: (obs sensor -> obs line ->) policy (-> action line -> action sensor) -> task.step -> accumulate (-> record, with
+        paired_diff).  No host read."""
         if self._obs is None:
             self.start()
-        seen = self._obs if self._obs_line is None else self._obs_line.push(self._obs, self._done_prev)
+        sensed = self._obs if self._obs_sensor is None else self._obs_sensor.push(self._obs, self._done_prev)
+        seen = sensed if self._obs_line is None else self._obs_line.push(sensed, self._done_prev)
         self.policy_obs = seen
         if self._stacks:                                                  # self.actions: the policies' output of the previous step, not read on a start
             self._wide = {k: stack.advance(seen, self.actions, self._done_prev) for k, stack in self._stacks.items()}
@@ -258,6 +299,8 @@ class Player:
         else:
             self.actions = self._act_per_cell(seen)
         self.applied_actions = self.actions if self._act_line is None else self._act_line.push(self.actions, self._done_prev)
+        if self._act_sensor is not None:
+            self.applied_actions = self._act_sensor.push(self.applied_actions, self._done_prev)
         obs, rew, done, _ = self.task.step(self.applied_actions)
         self._done_prev = done
         if self.outcome is not None:
@@ -331,6 +374,8 @@ class Player:
                 out["actuators"] = self.read_actuators()
             if self._act_line is not None or self._obs_line is not None:
                 out["latency"] = self.latency()
+            if self._obs_sensor is not None or self._act_sensor is not None:
+                out["sensor"] = self.sensors()
             if self._stacks:
                 out["history"] = self.history()
             return out

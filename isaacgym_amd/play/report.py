@@ -193,3 +193,10 @@ def latency_line(lat):
     ms = 1000.0 * lat["control_dt"]
     return f"latency: control dt {ms:.6g} ms; " + "; ".join(
         f"{axis} {','.join(str(k) for k in lat[axis])} steps = {','.join(f'{k * ms:.6g}' for k in lat[axis])} ms" for axis in DELAY_AXES)
+
+
+def sensor_line(sen):
+    """The CLI's head line for run()'s `sensor`: per axis the cells' levels, then the column specs that were given."""
+    from .sweep import SENSOR_AXES
+    cols = "".join(f"; {k} {v}" for k, v in sen.get("columns", {}).items() if v)
+    return "sensor: " + "; ".join(f"{axis} {','.join(f'{v:g}' for v in sen[axis])}" for axis in SENSOR_AXES) + cols

@@ -44,6 +44,11 @@ Domain randomisation (PPOTrainer(randomization=, adr=), --randomize / --adr TABL
 domain randomisation, a device-resident curriculum over the tables' ranges (adr.AutoRandomizer; include/ppenv_dr_adr.h), run from the
 collector's per-step hook (DESIGN §5d "Randomisation and ADR in training").  Off by default, and then nothing is built.
 
+Sensor noise and dropouts (PPOTrainer(obs_noise=, obs_drop=, action_noise=, action_drop=, sensor_columns=), --obs-noise / --obs-drop / --action-noise /
+--action-drop S | LO:HI, --obs-noise-columns / --obs-drop-columns / --action-noise-columns / --action-drop-columns SPEC): the rollout runs with a sensor
+line on the sensing path and one on the command path (sensor.SensorLine; include/ppenv_sensor.h holds the rule; DESIGN §5e "Sensor noise and
+dropouts").  Off by default, and then nothing is built.
+
 Privileged critic inputs (PPOTrainer(critic_inputs=("tables", "latency", "raw_obs")), --critic-inputs tables,latency,raw_obs): an asymmetric
 actor-critic.  The named quantities — the env's randomisation tables, its delays, its undelayed observation — are gathered per control step
 into `col.priv` (critic_input.CriticInput; include/ppenv_critic_input.h) and feed first-layer columns that only the critic's weights read;
@@ -98,6 +103,7 @@ from . import history as history_mod
 from ._lib import PPOAdam, PPOLossArgs, PPOMeter, PPOTensor     # the ctypes mirrors of include/ppenv_ppo.h and ppenv_ppo_meter.h (bound in _lib.load)
 from .collector import RolloutCollector, gae
 from .latency import delay_range, latency_text
+from . import sensor as sensor_mod
 from .policy import UNITS, NativeActorCritic, RunningMeanStd, layers_from_rlgames_state_dict, sampler_stream_seed
 
 HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
@@ -448,6 +454,17 @@ class PPOTrainer:
     delays 0 (the default) no line is built and the run is bitwise the run without the arguments.  A fixed delay K trains under exactly
     what `python -m isaacgym_amd.play --sweep action_delay=...` measures.  Checkpoints carry the two ranges under "latency"; the lines'
     state is not checkpointed (the envs restart on resume).
+    obs_noise, action_noise (an amplitude S >= 0, or a (lo, hi) range), obs_drop, action_drop (a probability 0 .. 1, or a range): train under
+    sensor noise and sample dropouts (RolloutCollector; include/ppenv_sensor.h — this build's own rule, the reference adds no such noise).
+    A range is drawn anew per env at every episode start, on the device.  sensor_columns: dict(obs_noise_columns=, obs_drop_columns=,
+    action_noise_columns=, action_drop_columns=) of column specs ("ball_pos=1,ball_vel=4,60:67=0.5"; sensor.columns).  The sensing line
+    comes before the observation delay and the history, the command line after the action delay; the policy sees — and the learner trains
+    on — the noised observation, the env consumes the noised command, the stored actions are the policy's own and the `raw_obs` critic
+    input stays the clean observation.  The draws are keyed scene.stream_seed(seed, scene.STREAM_SENSOR) and the task's env_id_offset, so
+    data-parallel shards reproduce one handle's rows and ranks under seed + r share none.  sensor() returns the record, checkpoints carry
+    it under "sensor" (a record, like "latency": load() accepts files without it and play does not read it).  With every value zero (the
+    default) nothing is allocated or launched and the run is bitwise the run without the arguments.  A fixed level trains under exactly
+    what `python -m isaacgym_amd.play --sweep obs_noise=...` measures.
     serve_plan, serve_paired: train on a serve plan (include/ppenv_serve.h) — cells of serve ranges over equal env groups, as
     env.set_serve_plan takes them — keyed scene.stream_seed(seed, scene.STREAM_SERVES) and the task's env_id_offset, so ranks under seed + r
     share no serves.  The collector runs the plan's launch after every env step.  A task that arrives with a plan set (task.set_serve_plan)
@@ -492,7 +509,8 @@ class PPOTrainer:
     the argument."""
 
     def __init__(self, task, cfg=None, seed=0, group=None, force=False, outcomes=False, action_delay=0, obs_delay=0, serve_plan=None, serve_paired=False,
-                 curriculum=None, randomization=None, adr=None, critic_inputs=(), history=None):
+                 curriculum=None, randomization=None, adr=None, critic_inputs=(), history=None, obs_noise=0.0, obs_drop=0.0, action_noise=0.0, action_drop=0.0,
+                 sensor_columns=None):
         self.cfg = cfg = PPOConfig() if cfg is None else cfg
         critic_inputs = critic_input_mod.parse(critic_inputs)
         if task.randomize:
@@ -564,7 +582,9 @@ class PPOTrainer:
                                     sigma=torch.exp(self.logstd), seed=sampler_stream_seed(self.seed),   # ranks under seed + r share no exploration noise, and none is the env's noise
                                     action_delay=action_delay, obs_delay=obs_delay, latency_seed=scene.stream_seed(self.seed, scene.STREAM_LATENCY),
                                     env_id_offset=task._env_id_offset, serve=self.curriculum if self.curriculum is not None else task._serve_plan,
-                                    randomizer=randomizer, critic_input=critic_inputs or None, history=self._history)
+                                    randomizer=randomizer, critic_input=critic_inputs or None, history=self._history, obs_noise=obs_noise, obs_drop=obs_drop,
+                                    action_noise=action_noise, action_drop=action_drop, sensor_columns=sensor_columns,
+                                    sensor_seed=scene.stream_seed(self.seed, scene.STREAM_SENSOR), task=task)
         if self._critic_inputs is not None:
             assert self.col.critic_input.record() == self._critic_inputs
         self.g_logstd = self.learner.grad_extra
@@ -584,6 +604,7 @@ class PPOTrainer:
         self.last_mean_rewards = NO_SCORE                                  # the score of the best checkpoint so far (fit)
         self.epoch, self.frame = 0, 0
         self.loaded_latency = None                                         # load(): the "latency" of the checkpoint resumed from
+        self.loaded_sensor = None                                          # load(): its "sensor", likewise
         self.outcome = task.enable_outcomes() if outcomes else None         # pp_ta_outcome, int64 [16] (include/ppenv_ta_outcome.h)
         if self.multi:
             self._broadcast_start()
@@ -655,6 +676,13 @@ class PPOTrainer:
     def latency(self):
         """The control dt in seconds and the two delay ranges [lo, hi] in control steps ([0, 0]: that path is not delayed)."""
         return dict(control_dt=self.env.control_dt, action_delay=list(self.col.action_delay), obs_delay=list(self.col.obs_delay))
+
+    def sensor(self):
+        """The four level ranges [lo, hi] ([0, 0] twice: that path has no sensor line) and the four column specs as given, or None with
+        no sensor line at all."""
+        if self.col.obs_sensor is None and self.col.act_sensor is None:
+            return None
+        return dict(**{axis: list(r) for axis, r in self.col.sensor_levels.items()}, columns=dict(self.col.sensor_columns))
 
     # -- the steps of an epoch --
     def collect(self):
@@ -818,7 +846,7 @@ class PPOTrainer:
         plan = None if rz is None else {"frequency": int(rz["frequency"]),
                                         "tables": {k: {f: (list(v) if isinstance(v, (tuple, list)) else v) for f, v in t.items()} for k, t in rz["tables"].items()}}
         for key, record in (("serve", self.serve()), ("curriculum", state(self.curriculum)), ("randomization", plan), ("adr", state(self.adr)),
-                            ("critic_inputs", self.critic_inputs()), ("history", self.history())):
+                            ("critic_inputs", self.critic_inputs()), ("history", self.history()), ("sensor", self.sensor())):
             if record is not None:                                           # an absent feature leaves no key
                 sd[key] = record
         return sd
@@ -865,6 +893,7 @@ class PPOTrainer:
             self.meter.load_state_dict(ck["meter"])
         self.last_mean_rewards = float(ck.get("last_mean_rewards", NO_SCORE))
         self.loaded_latency = ck.get("latency")                              # what the file's run trained under; None: a file from before the key
+        self.loaded_sensor = ck.get("sensor")                                # likewise; None: a run without a sensor line, or a file from before the key
 
 
 
@@ -1012,6 +1041,14 @@ def main(argv=None):
     ap.add_argument("--action-delay", default="0", metavar="K|LO:HI", help="train under control latency of the command path: the env consumes the action of K "
                     "control steps ago (0..15), or of LO..HI steps ago, drawn per env at every episode start")
     ap.add_argument("--obs-delay", default="0", metavar="K|LO:HI", help="... of the sensing path: the policy sees the observation of K (or LO..HI) control steps ago")
+    for path, what in (("obs", "the observations the policy sees"), ("action", "the commands the env consumes")):
+        ap.add_argument(f"--{path}-noise", default="0", metavar="S|LO:HI", help=f"train under Gaussian noise of amplitude S x the column's scale on {what}, or of an "
+                        "amplitude in LO..HI drawn per env at every episode start")
+        ap.add_argument(f"--{path}-drop", default="0", metavar="P|LO:HI", help=f"... under sample dropouts: each control step, with probability P (0..1, or drawn in "
+                        f"LO..HI per episode), {what} are the last delivered ones again in the hold columns")
+        ap.add_argument(f"--{path}-noise-columns", default=None, metavar="SPEC", help="the noised columns and their scales: comma-separated NAME[=SCALE] or "
+                        "LO:HI[=SCALE], e.g. ball_pos=1,ball_vel=4,60:67=0.5; default all=1")
+        ap.add_argument(f"--{path}-drop-columns", default=None, metavar="SPEC", help="the columns a dropout holds: comma-separated NAME or LO:HI; default all")
     ap.add_argument("--serve", action="append", default=[], metavar="AXIS=V|AXIS=LO:HI", help="train on a serve plan: pin a serve axis (serve_speed, serve_tilt, "
                     "serve_tilt_z; the 27-dof task also ball_y, ball_z) or give its range; repeatable, all flags together are one cell over all envs")
     ap.add_argument("--curriculum", action="append", default=[], metavar="AXIS=LO:HI:BINS", help="an adaptive serve curriculum: cut the axis into BINS equal "
@@ -1055,6 +1092,10 @@ def main(argv=None):
     if args.force_dist and not args.multi_gpu:
         ap.error("--force-dist belongs to --multi-gpu")
     action_delay, obs_delay = delay_range("--action-delay", args.action_delay), delay_range("--obs-delay", args.obs_delay)
+    flag = lambda key: "--" + key.replace("_", "-")
+    sensors = {axis: (sensor_mod.drop_range if axis.endswith("_drop") else sensor_mod.sigma_range)(flag(axis), getattr(args, axis)) for axis in sensor_mod.AXES}
+    sensor_columns = {f"{axis}_columns": getattr(args, f"{axis}_columns") for axis in sensor_mod.AXES}
+    sensor_mod.check_specs(args.task, sensor_columns, flag)
     try:
         serve_plan, curriculum = serve_cell_parse(args.serve), None
         critic_inputs = critic_input_mod.parse(args.critic_inputs)
@@ -1101,7 +1142,9 @@ def main(argv=None):
         task = isaacgym_amd.make(seed=seed, task=args.task, num_envs=args.num_envs, cfg=task_cfg)
     tr = PPOTrainer(task, cfg, seed=seed, force=args.force_dist, outcomes=args.outcomes, action_delay=action_delay, obs_delay=obs_delay,
                     serve_plan=serve_plan, curriculum=curriculum, randomization=True if args.randomize else None, adr=adr, critic_inputs=critic_inputs,
-                    history=history)
+                    history=history, sensor_columns=sensor_columns, **sensors)
+    if rank == 0 and tr.sensor() is not None:
+        print(sensor_mod.sensor_text(tr.sensor()), flush=True)
     if rank == 0 and tr.randomization is not None:
         print("reset-time randomisation: " + ", ".join(f"{k} {t['distribution']} {t['operation']} {t['range'][0]:g}..{t['range'][1]:g}"
                                                        for k, t in tr.randomization["tables"].items()), flush=True)

@@ -1030,6 +1030,44 @@ def latency_draws(stream_seed, gids, episodes, channel, lo, hi):
     return (lo + (((h >> u32(8)).astype(u64) * u64(hi - lo + 1)) >> u64(24)).astype(np.int64)).astype(np.int32)
 
 
+STREAM_SENSOR = 0xBE5466CF34E90C6C                                                                       # the sensor line's noise, dropouts and per-episode levels (include/ppenv_sensor.h)
+SENSOR_NOISE, SENSOR_DROP, SENSOR_LEVEL = 0, 1, 2                                                        # PP_SENSOR_NOISE / _DROP / _LEVEL
+
+
+def sensor_uniform(stream_seed, channel, part, keys, episodes, k):
+    """Host restatement of the sensor line's U(part, key, n, k) (include/ppenv_sensor.h): rng_uniform(s_part, key, n, k) with
+    s_part = mix64(stream_seed + 0x9E3779B97F4A7C15 * (1 + 3 * channel + part)), over the broadcast of `keys`, `episodes` and `k`
+    (arrays of non-negative integers, taken modulo 2^32) -> float32 array, bit for bit the device's."""
+    u32 = np.uint32
+    sd = _mix64((int(stream_seed) + 0x9E3779B97F4A7C15 * (1 + 3 * int(channel) + int(part))) & 0xFFFFFFFFFFFFFFFF)
+
+    def hash32(x):                                              # (uint32 arrays wrap silently)
+        x = (x ^ (x >> u32(16))) * u32(0x7FEB352D)
+        x = (x ^ (x >> u32(15))) * u32(0x846CA68B)
+        return x ^ (x >> u32(16))
+    key, n, k = np.broadcast_arrays(*((np.atleast_1d(np.asarray(v, np.int64)) & 0xFFFFFFFF).astype(u32) for v in (keys, episodes, k)))
+    h = hash32(key ^ u32(sd & 0xFFFFFFFF))
+    h = hash32(h + n * u32(0x9E3779B9) + u32(sd >> 32))
+    h = hash32(h + (k + u32(1)) * u32(0x85EBCA6B))
+    return (h >> u32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+
+
+def sensor_draws(stream_seed, gids, episodes, channel, sigma, drop, num_agents=1, agent=0):
+    """Host restatement of the sensor line's LEVEL draws (include/ppenv_sensor.h; pp::sensor_book): the amplitude and the dropout
+    probability that row `agent` of global env id `gids` holds in its episode number `episodes` (arrays, broadcast against each other) on
+    `channel` (0: the command path, 1: the sensing path) under the STREAM seed `stream_seed` (stream_seed(seed, STREAM_SENSOR)), with the
+    ranges sigma = (lo, hi) and drop = (lo, hi) -> two float32 arrays.  The key is the ROW: num_agents * gid + agent.  lo == hi gives lo."""
+    f32 = np.float32
+    (s_lo, s_hi), (d_lo, d_hi) = (f32(sigma[0]), f32(sigma[1])), (f32(drop[0]), f32(drop[1]))
+    A, agent = int(num_agents), int(agent)
+    if not (0 <= s_lo <= s_hi < np.inf and 0 <= d_lo <= d_hi <= 1) or channel not in (0, 1) or A not in (1, 2) or not 0 <= agent < A:
+        raise ValueError(f"sensor_draws: finite 0 <= sigma lo <= hi, 0 <= drop lo <= hi <= 1, channel 0 or 1 and agent < num_agents (1 or 2), not "
+                         f"sigma {sigma}, drop {drop}, channel {channel}, agent {agent}, num_agents {num_agents}")
+    keys = np.atleast_1d(np.asarray(gids, np.int64)) * A + agent
+    u0, u1 = (sensor_uniform(stream_seed, channel, SENSOR_LEVEL, keys, episodes, k) for k in (0, 1))
+    return (s_lo + ((s_hi - s_lo) * u0).astype(f32)).astype(f32), (d_lo + ((d_hi - d_lo) * u1).astype(f32)).astype(f32)
+
+
 def adr_draws(stream_seed, gids, draws, dims, ranges, thr):
     """Host restatement of ADR's DRAW (include/ppenv_dr_adr.h; pp::adr_draw) in numpy: what redraw number `draws` of the global env ids
     `gids` (arrays, broadcast against each other) writes under the STREAM seed `stream_seed` (stream_seed(seed, STREAM_TABLES)).  dims: the
